@@ -7,7 +7,8 @@ PBS 2^7 x 3, KS 2^2 x 8), inputs resident in HBM before the timed region.  The d
 FFT64 (tfhe-rs's arithmetic: f64 negacyclic FFT external product over the native 2^64 torus,
 pbs_fft.hip); --preset gate runs the same workload on the Goldilocks NTT transform (pbs_kernels.hip).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--cpu-sample S] [--preset gate_fft|gate|fhevm|fhevm_fft]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--preset gate_fft|gate|fhevm|fhevm_fft]
+                  [--dump-outputs DIR] [--full [--cpu-sample S]]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
 
 Multi-GPU: weak scaling.  Rank 0 generates the key set, uploads it to its GPU and broadcasts the
@@ -29,9 +30,18 @@ The SURVEY §8d key-streaming byte model (61,952,960 B per PBS at r = 1) is repo
 N=2048, PBS 2^23 x 1, KS 2^4 x 4, KS -> PBS; shortint messages m < 16, identity LUT) as a secondary
 line; the headline metric is P-GATE.
 
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, a decryption check of
+the last step's outputs, the result line.  --full adds the CPU leg:
 cpu_baseline: rank 0 at N=1 only — the oracle's C restatement (oracle/, -O3, OpenMP, one PBS per
 thread) on a bounded sample of the same inputs, same keys; the sample's outputs are also
 compared bit-for-bit with the GPU's ("sample_bitexact").
+
+--dump-outputs DIR: after the timed steps rank 0 writes the output ciphertexts of the last timed step (what a
+caller of Engine.pbs_async receives: [rows, lwe_dim + 1] torus words) as float64 arrays DIR/pbs_out_hi32.npy and
+DIR/pbs_out_lo32.npy -- the high and the low 32 bits of every u64 word, each exact in a float64
+(word = hi32 * 2^32 + lo32) -- and DIR/pbs_out_rows.npy, the batch indices of the rows written: all of them
+while the two arrays fit in 48 MB, otherwise a fixed seeded sample in ascending order.  Keys and inputs come from
+fixed seeds, so two runs with the same arguments write identical files.
 """
 from __future__ import annotations
 
@@ -60,6 +70,8 @@ BR_BYTES_PER_PBS_FHEVM = 60_162_048 + 7_352 + 16_384 + 16_392
 FHEVM_MM = 16                                            # message 2 bits x carry 2 bits
 C3_MASK = 0b10110010                                     # --config c3: bits bootstrapped with the NOT LUT
 HBM_PEAK_GBS = 8000.0
+DUMP_SEED = 0xD0A7                                       # --dump-outputs row sample
+DUMP_BUDGET = 48 << 20                                   # bytes over the two float64 halves
 
 
 def log(msg: str) -> None:
@@ -223,6 +235,20 @@ def cpu_baseline(cts: np.ndarray, gpu_out: np.ndarray, sample: int, threads: int
     }, exact, digest
 
 
+def dump_outputs(path: str, out: np.ndarray) -> None:
+    """--dump-outputs: the last timed step's output ciphertexts `out` ([rows, words] u64) as exact float64 halves."""
+    os.makedirs(path, exist_ok=True)
+    keep = max(1, DUMP_BUDGET // (16 * out.shape[1]))
+    rows = np.arange(out.shape[0])
+    if keep < out.shape[0]:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(out.shape[0], keep, replace=False))
+    sel = out[rows]
+    np.save(os.path.join(path, "pbs_out_hi32.npy"), (sel >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(path, "pbs_out_lo32.npy"), (sel & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(path, "pbs_out_rows.npy"), rows.astype(np.float64))
+    log(f"dumped {len(rows)} of {out.shape[0]} output ciphertexts to {path}")
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -232,8 +258,15 @@ def main() -> int:
     ap.add_argument("--global-batch", type=int, default=0,
                     help="strong scaling: this many PBS in total, contiguous slices of ~G/N per rank (SURVEY 8e: "
                          "C4 = 65,536 -> 8,192 per GPU on 8 GPUs)")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="PBS in the CPU baseline sample (0 = auto)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline (the oracle's port on host cores) and compare "
+                         "its sample bit-for-bit with the GPU's outputs; off by default: a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output ciphertexts as DIR/pbs_out_{hi32,lo32,rows}.npy (float64)")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="PBS in the CPU baseline sample of --full (0 = auto)")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="kept for command lines from before --full: a plain run has no CPU leg, so this only cancels "
+                         "the CPU baseline of --full")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) on GPUs; gloo only for rehearsals")
     ap.add_argument("--preset", choices=["gate", "gate_fft", "fhevm", "fhevm_fft"], default="gate_fft",
                     help="gate_fft (default) = the BASELINE metric on the FFT64 transform (P-GATE, tfhe-rs's f64-FFT "
@@ -372,6 +405,8 @@ def main() -> int:
     elapsed_max = float(t_max.item())
 
     out = d_out.cpu().numpy().view(np.uint64)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     if fhevm:
         correct = bool(np.array_equal(ck.decrypt(out, FHEVM_MM), msgs))
     elif c3:
@@ -422,7 +457,7 @@ def main() -> int:
             "keyswitch_ms": round(ks_ms / max(ks_n, 1), 3),
             "decrypt_ok": bool(ok.item()),
         }
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             threads, how = host_cores()
             log(f"cpu baseline on {threads} host cores ({how})")
             sample = args.cpu_sample or (256 * threads if fft else 40 * threads)   # whole FheUint8 values: x 8
@@ -481,7 +516,7 @@ def main() -> int:
             "dist": {"backend": dist.get_backend() if dist_on else None, "world_size": world},
             "decrypt_ok": bool(ok.item()),
         }
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             threads, how = host_cores()
             log(f"cpu baseline on {threads} host cores ({how})")
             # ~10-20 s of CPU work: the oracle does ~3.5 PBS/s per thread on the NTT at P-GATE, ~23 on

@@ -1,11 +1,13 @@
 """tfhe-rs compact ciphertext list ingest (tfhe_amd/ctlist.py) on CPU.
 
-Pinned against the reference's own files, read in place (the test skips where /root/reference is absent):
-  * the four ProvenCompactCiphertextList fixtures -- sdk/relayer/src/test/v1/ciphertext.ts:1 and
+Pinned against the reference's own files:
+  * the four ProvenCompactCiphertextList fixtures, stored under tests/golden/relayer/ -- v1_ciphertext.bin (the
+    bytes of the hex string at sdk/relayer/src/test/v1/ciphertext.ts:1) and the reference's
     src/test/assets/input-proof-payload-{1,2,3}.json `ciphertextWithInputVerification` -- parse to LWE
     compact lists whose DataKinds equal each payload's declared fheTypeEncryptionBitwidths and whose
     ciphertext counts equal ceil(blocks / 2) (packed: two 2-bit blocks per LWE);
-  * the expansion convention: a compact list encrypted with the reference's real CompactPublicKey
+  * the expansion convention (key files read in place; this test skips where the reference is absent, its key
+    pair stays out of this repository): a compact list encrypted with the reference's real CompactPublicKey
     (src/test/keys/publicKey.bin) expands to LWEs that decrypt, under the compact-PKE secret key ingested
     from the paired ClientKey (privateKey.bin), to the packed values with noise far below Delta -- and a
     wrong convention does not.
@@ -14,7 +16,6 @@ privateKey.bin with any convention), so their bits are parsed, not decrypted.
 """
 import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -22,15 +23,16 @@ import pytest
 from tfhe_amd import ctlist, keyio
 
 REF = "/root/reference/sdk/relayer/src/test"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "relayer")
 
 
 def _fixtures():
     out = []
-    t = open(os.path.join(REF, "v1", "ciphertext.ts")).read()
-    out.append(("v1/ciphertext.ts", bytes.fromhex(re.findall(r"'([0-9a-f]+)'", t)[0]), [32], None))
+    with open(os.path.join(GOLDEN, "v1_ciphertext.bin"), "rb") as f:
+        out.append(("v1/ciphertext.ts", f.read(), [32], None))
     for i in (1, 2, 3):
-        d = json.load(open(os.path.join(REF, "assets", f"input-proof-payload-{i}.json")))
+        with open(os.path.join(GOLDEN, f"input-proof-payload-{i}.json")) as f:
+            d = json.load(f)
         h = d["ciphertextWithInputVerification"]
         out.append((f"input-proof-payload-{i}.json", bytes.fromhex(h[2:] if h.startswith("0x") else h),
                     d["fheTypeEncryptionBitwidths"], d.get("values")))
@@ -53,6 +55,7 @@ def test_reference_lists_parse_and_match_declared_types():
         assert ex.shape == (cl.count, 2049)
 
 
+@pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present")
 def test_expansion_convention_against_reference_key_pair():
     tk = keyio.load_client_key(os.path.join(REF, "keys", "privateKey.bin"))
     cpk = keyio.load_compact_public_key(os.path.join(REF, "keys", "publicKey.bin"))

@@ -1,9 +1,10 @@
 #!/bin/bash
 # Profile one bench preset on the GPU box: a rocprofv3 kernel-trace summary of the bench command, one SQ
 # counter pass, the FETCH/WRITE passes for the HBM-traffic field and an SQ instruction-mix pass; then
-# tools/roofline_summary.py folds them into gpurun_out/<TAG>_roofline.json tagged with the tree's source_id,
-# and finally the bench line itself (with the CPU baseline) reads that summary (bench.py uses a profile under
-# profiles/ only while its source_id matches its own).  Each GPU step has its own time
+# tools/roofline_summary.py folds them into <TAG>_roofline.json tagged with the tree's source_id and copies it
+# under profiles/, and finally the bench line itself (bench.py --full: with the CPU baseline) reads that summary
+# (bench.py uses a profile under profiles/ only while its source_id matches its own) and is printed; its JSON and
+# log stay under $TMPDIR.  Each GPU step has its own time
 # limit; the script stops at the first failure.
 #   TAG=r02_fft1 PRESET=gate_fft tools/profile_round.sh
 #   TAG=r06_c3 PRESET=gate_fft ARGS="--config c3" BATCH=32768 tools/profile_round.sh   (BASELINE configs[2]: the
@@ -39,8 +40,8 @@ python tools/roofline_summary.py $TAG gpurun_out/${TAG}_kernel_stats.csv gpurun_
 # of this very build (same source_id) -- round 4's P-FHEVM line ran before its profile existed and carried nulls
 if [ "$BENCH" = "1" ]; then
   cp gpurun_out/${TAG}_roofline.json profiles/${TAG}_roofline.json
-  timeout -k 10 300 python bench.py $B > gpurun_out/bench_${TAG}.json 2> gpurun_out/bench_${TAG}.err || { echo "bench failed"; tail -30 gpurun_out/bench_${TAG}.err; exit 1; }
-  cat gpurun_out/bench_${TAG}.json
+  timeout -k 10 300 python bench.py $B --full > $TMPDIR/bench_${TAG}.json 2> $TMPDIR/bench_${TAG}.err || { echo "bench failed"; tail -30 $TMPDIR/bench_${TAG}.err; exit 1; }
+  cat $TMPDIR/bench_${TAG}.json
 fi
 rm -rf gpurun_out/prof_${TAG} gpurun_out/pmc_*_${TAG}   # raw rocprofv3 directories: the summaries above are kept
 echo ALL_OK
