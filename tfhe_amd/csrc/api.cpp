@@ -141,6 +141,7 @@ struct DeviceGuard {
 // One device's slice of an engine.
 struct tfhe_shard {
   int device = 0;
+  int cus = 0;                  // compute units (queried once, shard_init)
   hipStream_t stream = nullptr;
   u64* d_bsk = nullptr;         // transform domain (NTT layout x N^-1, or Fourier)
   u64* d_ksk = nullptr;         // standard KSK (VALU keyswitch; RCCL broadcast source / target)
@@ -246,7 +247,7 @@ hipError_t launch_br(tfhe_ctx* c, shard& s, const u64* in, size_t B, const u64* 
                                            (const double*)s.d_tw, out_big, out_acc, st, c->lat_max);
   if (is_fft(c->p))
     return tfhe::launch_blind_rotate_fft(in, B, (int)c->p.n, luts, idx, (int)n_lut, (const double*)s.d_bsk,
-                                         (const double*)s.d_tw, out_big, out_acc, st, c->lat_max);
+                                         (const double*)s.d_tw, out_big, out_acc, st, c->lat_max, s.cus);
   if (c->p.N == 2048)
     return tfhe::launch_blind_rotate_2048(in, B, (int)c->p.n, luts, idx, (int)n_lut, s.d_bsk, s.d_tw, out_big, out_acc,
                                           st, c->lat_max);
@@ -500,6 +501,7 @@ int shard_init(tfhe_ctx* c, shard& s) {
   DeviceGuard g(s.device);
   HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
   HIP_TRY(hipEventCreateWithFlags(&s.ws_free, hipEventDisableTiming));
+  HIP_TRY(hipDeviceGetAttribute(&s.cus, hipDeviceAttributeMultiprocessorCount, s.device));
   const tfhe_params& p = c->p;
   using namespace tfhe;
   if (is_fft(p)) {  // FFT64: twist / pass tables (pbs_fft.hip: make_fft_tables)

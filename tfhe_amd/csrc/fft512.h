@@ -446,6 +446,91 @@ __device__ __forceinline__ void dft512_inv_rb(double (&xr)[8], double (&xi)[8], 
   dft8<true>(xr, xi);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Round 7: the pair kernel's transforms with the LDS traffic of each transpose placed by hand (pbs_fft.hip uses
+// dft512_fwd_rab_p / dft512_inv_rb_p; every other kernel keeps the bodies above).  Pure placement of stores, loads
+// and waits: the f64 operations, their operands and their order are those of dft512_fwd_rab / dft512_inv_rb.
+// FFT_XPOSE_OVERLAP 1: per slot, the twiddle multiply and then that slot's transpose store, the order pinned, so a
+//   ds_write_b128 goes out under the next slot's four f64 instructions (hipcc's own schedule is all eight multiplies,
+//   a full drain, then eight stores back to back with the wave issuing nothing else).
+// FFT_XPOSE_NOWAIT 1: no s_waitcnt between a wave's transpose stores and its reads of the same private area (DS
+//   operations of one wave execute in issue order; the ordering left is compiler-only), the eight reads pinned as
+//   ONE group in the order the next DFT8's first stage consumes them (0, 4, 1, 5, 2, 6, 3, 7) and consumed under
+//   hipcc's counted lgkmcnt waits.  FFT_LDS_WAIT = 0 above lost because it left the reads free to scatter.
+// 0 = the round-6 code in each case.  Measured on MI355X, same box, three interleaved rounds, ms per 4096-PBS blind
+// rotation (profiles/r07b_ab_steps.txt): the two pay only TOGETHER.  On top of FFT_MAC_PIPE (22.73): OVERLAP alone
+// 22.80, OVERLAP + NOWAIT 22.61 (the default; round-6 code 22.90); NOWAIT without OVERLAP is slower than round 6
+// (23.13 against 22.95 on another box).  Reading the inverse's eight pass-B' twiddles as one early group was measured
+// too and lost 0.05-0.12 ms: tools/ab_patches/r07_twi_group.patch.
+#ifndef FFT_XPOSE_OVERLAP
+#define FFT_XPOSE_OVERLAP 1
+#endif
+#ifndef FFT_XPOSE_NOWAIT
+#define FFT_XPOSE_NOWAIT 1
+#endif
+// one transpose of the wave-private area: slots E0.. times w (INV: conj w), stores at Tw[WS e], reads from Tr[RS e]
+template <bool INV, int E0, int WS, int RS>
+__device__ __forceinline__ void xpose_p(double (&xr)[8], double (&xi)[8], const double2 (&w)[8], double2* Tw,
+                                        const double2* Tr) {
+#if FFT_XPOSE_OVERLAP
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    if (e >= E0) cmul<INV>(xr[e], xi[e], w[e]);
+    Tw[WS * e] = make_double2(xr[e], xi[e]);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#else
+#pragma unroll
+  for (int e = E0; e < 8; e++) cmul<INV>(xr[e], xi[e], w[e]);
+#pragma unroll
+  for (int e = 0; e < 8; e++) Tw[WS * e] = make_double2(xr[e], xi[e]);
+#endif
+#if FFT_XPOSE_NOWAIT
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int e = (k >> 1) + 4 * (k & 1);
+    const double2 v = Tr[RS * e];
+    xr[e] = v.x;
+    xi[e] = v.y;
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#else
+  lds_order();
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    const double2 v = Tr[RS * e];
+    xr[e] = v.x;
+    xi[e] = v.y;
+  }
+  lds_order();
+#endif
+}
+
+template <bool TWIN = false>
+__device__ __forceinline__ void dft512_fwd_rab_p(double (&xr)[8], double (&xi)[8], double2* T, int lane, TBase tb,
+                                                 const double2 (&wa)[8], const double2 (&wb)[8]) {
+  if constexpr (TWIN) twist_dft8_fwd(xr, xi);
+  else dft8<false>(xr, xi);
+  xpose_p<false, 0, S1, 8>(xr, xi, wa, T + lane, T + tb.b1);
+  dft8<false>(xr, xi);
+  xpose_p<false, 1, S2, 1>(xr, xi, wb, T + lane, T + tb.b2);
+  dft8<false>(xr, xi);
+}
+
+__device__ __forceinline__ void dft512_inv_rb_p(double (&xr)[8], double (&xi)[8], double2* T, int lane, TBase tb,
+                                                const double2 (&wb)[8], const double2* twI) {
+  dft8<true>(xr, xi);
+  xpose_p<true, 1, 1, S2>(xr, xi, wb, T + tb.b2, T + lane);
+  dft8<true>(xr, xi);
+  double2 wi[8];  // pass B' twiddles: a constant LDS table, read where hipcc places them (between the multiplies)
+#pragma unroll
+  for (int e = 0; e < 8; e++) wi[e] = twI[64 * e + lane];
+  xpose_p<true, 0, 8, S1>(xr, xi, wi, T + tb.b1, T + lane);
+  dft8<true>(xr, xi);
+}
+
 // Round 6 (three waves per SIMD): every twiddle read from LDS, pass B's from the COMPACT table.  TW_B[e][L] =
 // w512^(8 (L & 7) e) depends on L & 7 only, so the 64 distinct values sit in 1 KB as [e][L & 7]: a lane reads
 // twBc[8 e] from its base twBc + (L & 7) (8 distinct addresses per instruction, broadcast, conflict-free), the same

@@ -185,6 +185,25 @@ __global__ __launch_bounds__(64) void fft_inv_kernel(const double2* __restrict__
 #ifndef FFT_PRIO
 #define FFT_PRIO 3
 #endif
+// The dispatch half-round of a workgroup on a part with `cus` compute units and two workgroups per CU: 0 = the first
+// workgroup each CU receives, 1 = the second, 2, 3 = the next round's.  FFT_PRIO 3 raises the odd half-rounds,
+// FFT_STAGGER delays half-round 1.  One division per workgroup, outside the CMUX loop.
+constexpr unsigned dispatch_half(unsigned wg, unsigned cus) { return wg / cus; }
+constexpr bool wg_prio_hi(unsigned wg, unsigned cus) { return dispatch_half(wg, cus) & 1u; }
+constexpr bool wg_staggered(unsigned wg, unsigned cus) { return dispatch_half(wg, cus) == 1u; }
+namespace dh_check {
+// on 256 CUs (MI355X): exactly rounds 1 to 6's bit 8 of the workgroup index and the range [256, 512)
+constexpr bool same_as_bit8(unsigned n) {
+  for (unsigned w = 0; w < n; w++)
+    if (wg_prio_hi(w, 256) != (((w >> 8) & 1u) != 0) || wg_staggered(w, 256) != (w < 512 && ((w >> 8) & 1u))) return false;
+  return true;
+}
+static_assert(same_as_bit8(4096), "dispatch_half(., 256) must reproduce the 256-CU split");
+static_assert(!wg_prio_hi(31, 32) && wg_prio_hi(32, 32) && wg_prio_hi(63, 32) && !wg_prio_hi(64, 32) && wg_prio_hi(96, 32), "32 CUs");
+static_assert(!wg_staggered(31, 32) && wg_staggered(32, 32) && wg_staggered(63, 32) && !wg_staggered(64, 32) && !wg_staggered(96, 32), "32 CUs");
+static_assert(!wg_prio_hi(303, 304) && wg_prio_hi(304, 304) && wg_prio_hi(607, 304) && !wg_prio_hi(608, 304) && wg_prio_hi(912, 304), "304 CUs");
+static_assert(!wg_staggered(303, 304) && wg_staggered(304, 304) && wg_staggered(607, 304) && !wg_staggered(608, 304) && !wg_staggered(912, 304), "304 CUs");
+}  // namespace dh_check
 
 // Component-pair batch kernel (round 3, the default above the latency range): workgroup = CTS ciphertexts x 2
 // waves (CTS = 2 by default, 4 in round 3), wave (p, c) owns COMPONENT c of ciphertext p.  Per CMUX i:
@@ -258,6 +277,20 @@ struct FpShared<CTS, false> {
 #endif
 #ifndef FFT_XCHPRIO
 #define FFT_XCHPRIO 0
+#endif
+// FFT_MAC_PIPE (round 7; 0 = the parent's loop): the key words of level steps q = 1 and q = 2 software-pipelined, this
+// many slots ahead.  hipcc's own schedule reads one slot's two words into the same registers eight times per level and
+// waits for each pair (eight exposed LDS round trips per level, at the MAC's raised priority and right before a
+// workgroup barrier); q = 0 already has all sixteen reads in flight (its partial sums are not live yet).  One slot ahead
+// at q = 1 and two at q = 2 (FFT_MAC_PIPE_Q2: the 16 decomposition states are dead there) is what 256 VGPRs hold: 255
+// used, none spilled; 2 / 3 spills one register, 2 / 2 five.  Measured alone 22.90 -> 22.73 ms per 4096-PBS blind
+// rotation, and 0.29 ms of the round-7 default's gain when taken out of it (same box, three interleaved rounds each,
+// profiles/r07b_ab_steps.txt).
+#ifndef FFT_MAC_PIPE
+#define FFT_MAC_PIPE 1
+#endif
+#ifndef FFT_MAC_PIPE_Q2
+#define FFT_MAC_PIPE_Q2 (FFT_MAC_PIPE ? 2 : 0)
 #endif
 typedef __attribute__((address_space(3))) u64 lds_u64;
 
@@ -346,7 +379,10 @@ __device__ __forceinline__ void rotate_states(const u64 (&v)[16], int a, int lan
 
 // the partial-sum exchange of wave c (compile-time): publish O_(1-c)^c in this wave's area, add O_c^(1-c) from
 // the partner's (two workgroup barriers)
-template <int C>
+// GROUP (round 7, the pair kernel with FFT_XPOSE_OVERLAP): the eight reads of the partner's area pinned as one group
+// (the published half of the partial sums has just died, so their registers are free) and added under counted waits;
+// hipcc's own schedule for C = 1 reads two, waits, adds, four times over
+template <int C, bool GROUP = false>
 __device__ __forceinline__ void exchange_partials(const double (&o0r)[8], const double (&o0i)[8], const double (&o1r)[8],
                                                   const double (&o1i)[8], double (&xr)[8], double (&xi)[8], double2* T,
                                                   const double2* Tp, int lane) {
@@ -357,11 +393,24 @@ __device__ __forceinline__ void exchange_partials(const double (&o0r)[8], const 
     xi[e] = C ? o1i[e] : o0i[e];
   }
   __syncthreads();
+  if constexpr (GROUP) {
+    double2 w[8];
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-  for (int e = 0; e < 8; e++) {
-    const double2 w = Tp[64 * e + lane];
-    xr[e] = xr[e] + w.x;
-    xi[e] = xi[e] + w.y;
+    for (int e = 0; e < 8; e++) w[e] = Tp[64 * e + lane];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      xr[e] = xr[e] + w[e].x;
+      xi[e] = xi[e] + w[e].y;
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      const double2 w = Tp[64 * e + lane];
+      xr[e] = xr[e] + w.x;
+      xi[e] = xi[e] + w.y;
+    }
   }
   __syncthreads();  // the partner has read this wave's area before the inverse overwrites it
 }
@@ -409,7 +458,7 @@ template <int CTS, bool WRITE_ACC, bool WRITE_BIG>
 __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kernel(
     const u64* __restrict__ lwe_in, int n, size_t B, const u64* __restrict__ luts, const u32* __restrict__ lut_index,
     int n_lut, const double2* __restrict__ bsk, const double2* __restrict__ tw_g, u64* __restrict__ out_big,
-    u64* __restrict__ out_acc) {
+    u64* __restrict__ out_acc, int n_cus) {
   constexpr int NW = 2 * CTS;
   constexpr bool LDS_TW = CTS == 4 && FFT_PAIR_LDSTW;
   __shared__ __attribute__((aligned(16))) FpShared<CTS> sh;
@@ -485,9 +534,9 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
 #if FFT_PRIO == 1
   const bool prio_hi = NW > 4 && wave_s >= 4;  // the 4-wave CTS = 2 workgroup has no second wave per SIMD
 #elif FFT_PRIO == 3
-  // with two workgroups per CU, one of them (by dispatch half-round) at the higher priority.  Bit 8 of the
-  // workgroup index is the second dispatch half on a 256-CU part (MI355X only; other CU counts just alternate)
-  const bool prio_hi = (blockIdx.x >> 8) & 1;
+  // with two workgroups per CU, one of them (by dispatch half-round) at the higher priority: bit 8 of the
+  // workgroup index on a 256-CU part (MI355X), the same half-rounds on any other CU count
+  const bool prio_hi = wg_prio_hi(blockIdx.x, (unsigned)n_cus);
 #elif FFT_PRIO == 6
   [[maybe_unused]] constexpr bool prio_hi = false;  // the per-CMUX alternation below
 #elif FFT_PRIO == 5
@@ -526,10 +575,10 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
 #endif
   base_prio();
 #if FFT_STAGGER
-  // round 6 (default 1): the second workgroup of each CU in the first dispatch round (blockIdx bit 8 on 256 CUs) starts
+  // round 6 (default 1): the second workgroup of each CU in the first dispatch round (dispatch half-round 1) starts
   // FFT_STAGGER x ~3.4 us late, so the two workgroups of a CU do not run their phases in lockstep from the start
   // (with FFT_PRIO 3: 23.04 -> 22.97 ms per 4096, C2 6.24 -> 6.19 ms; alone 24.04 -> 23.87 ms; 2 and 4 x 3.4 us: neutral)
-  if (blockIdx.x < 512 && ((blockIdx.x >> 8) & 1))
+  if (wg_staggered(blockIdx.x, (unsigned)n_cus))
     for (int k = 0; k < FFT_STAGGER; k++) __builtin_amdgcn_s_sleep(127);
 #endif
   for (int i = 0; i < n; i++) {
@@ -577,7 +626,9 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
         }
       }
       // the slot twist rides in pass A's twisted DFT8 (twist_dft8_fwd)
-#if FFT_PAIR_TWREG >= 2
+#if FFT_PAIR_TWREG >= 2 && (FFT_XPOSE_OVERLAP || FFT_XPOSE_NOWAIT)
+      dft512_fwd_rab_p<true>(xr, xi, T, lane, tb, wa, wb);
+#elif FFT_PAIR_TWREG >= 2
       dft512_fwd_rab<true>(xr, xi, T, lane, tb, wa, wb);
 #elif FFT_PAIR_TWREG
       dft512_fwd_ra<true>(xr, xi, T, lane, tb, wa, twB);
@@ -590,6 +641,31 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
 #endif
       const double2* k0 = sh.K[LDS_TW ? (g & 1) : 0] + c * (2 * M) + lane;
       const double2* k1 = k0 + M;
+#if FFT_MAC_PIPE
+      if constexpr (q > 0) {
+        // a rotating window of D slots' key words ahead of the slot being consumed, the order pinned: the reads of
+        // slot e + D go out before slot e's eight fma, which wait (counted) for slot e's pair only
+        constexpr int D = q == 2 ? FFT_MAC_PIPE_Q2 : FFT_MAC_PIPE;
+        double2 ku[8], kv[8];
+#pragma unroll
+        for (int e = 0; e < D; e++) {
+          ku[e] = k0[64 * e];
+          kv[e] = k1[64 * e];
+        }
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          if (e + D < 8) {
+            ku[e + D] = k0[64 * (e + D)];
+            kv[e + D] = k1[64 * (e + D)];
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          mac_next(o0r[e], o0i[e], xr[e], xi[e], ku[e]);
+          mac_next(o1r[e], o1i[e], xr[e], xi[e], kv[e]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        return;
+      }
+#endif
 #pragma unroll
       for (int e = 0; e < 8; e++) {
         const double2 u = k0[64 * e], v = k1[64 * e];
@@ -610,12 +686,14 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
 #endif
     // exchange the partial sums: publish O_(1-c)^c, take O_c^(1-c) (c wave-uniform: a scalar branch, no selects)
     double xr[8], xi[8];
-    if (c_s) exchange_partials<1>(o0r, o0i, o1r, o1i, xr, xi, T, Tp, lane);
-    else exchange_partials<0>(o0r, o0i, o1r, o1i, xr, xi, T, Tp, lane);
+    if (c_s) exchange_partials<1, FFT_XPOSE_OVERLAP != 0>(o0r, o0i, o1r, o1i, xr, xi, T, Tp, lane);
+    else exchange_partials<0, FFT_XPOSE_OVERLAP != 0>(o0r, o0i, o1r, o1i, xr, xi, T, Tp, lane);
 #if FFT_MACPRIO && FFT_XCHPRIO
     base_prio();  // A/B: the partial-sum exchange still at the MAC's priority
 #endif
-#if FFT_PAIR_TWREG >= 2
+#if FFT_PAIR_TWREG >= 2 && (FFT_XPOSE_OVERLAP || FFT_XPOSE_NOWAIT)
+    dft512_inv_rb_p(xr, xi, T, lane, tb, wb, twI);
+#elif FFT_PAIR_TWREG >= 2
     dft512_inv_rb(xr, xi, T, lane, tb, wb, twI);
 #else
     dft512_inv_t(xr, xi, T, lane, tb, twB, twI);
@@ -1155,9 +1233,10 @@ hipError_t launch_bsk_to_fourier(const u64* bsk_std, double* bsk_f, size_t polys
 
 hipError_t launch_blind_rotate_fft(const u64* lwe_in, size_t B, int n, const u64* luts, const u32* lut_index,
                                    int n_lut, const double* bsk_f, const double* tw, u64* out_big, u64* out_acc,
-                                   hipStream_t s, size_t latency_max_batch) {
+                                   hipStream_t s, size_t latency_max_batch, int n_cus) {
   using namespace fftk;
   if (B == 0) return hipSuccess;
+  if (n_cus <= 0) n_cus = 256;
   const double2 *bk = (const double2*)bsk_f, *t = (const double2*)tw;
   if (B <= latency_max_batch) {
     dim3 grid((unsigned)B), block(FL_THREADS);
@@ -1198,13 +1277,13 @@ hipError_t launch_blind_rotate_fft(const u64* lwe_in, size_t B, int n, const u64
   dim3 grid((unsigned)((B + CTS - 1) / CTS)), block(128 * CTS);
   if (out_acc && out_big)
     hipLaunchKernelGGL((blind_rotate_fft_pair_kernel<CTS, true, true>), grid, block, 0, s, lwe_in, n, B, luts,
-                       lut_index, n_lut, bk, t, out_big, out_acc);
+                       lut_index, n_lut, bk, t, out_big, out_acc, n_cus);
   else if (out_acc)
     hipLaunchKernelGGL((blind_rotate_fft_pair_kernel<CTS, true, false>), grid, block, 0, s, lwe_in, n, B, luts,
-                       lut_index, n_lut, bk, t, out_big, out_acc);
+                       lut_index, n_lut, bk, t, out_big, out_acc, n_cus);
   else
     hipLaunchKernelGGL((blind_rotate_fft_pair_kernel<CTS, false, true>), grid, block, 0, s, lwe_in, n, B, luts,
-                       lut_index, n_lut, bk, t, out_big, out_acc);
+                       lut_index, n_lut, bk, t, out_big, out_acc, n_cus);
   return hipGetLastError();
 }
 

@@ -34,9 +34,11 @@ void make_fft_tables(double* tw);
 bool fft_slot_constants_ok();  // the N = 1024 kernels' compile-time twist constants == the host tables
 hipError_t launch_bsk_to_fourier(const u64* bsk_std, double* bsk_f, size_t polys, const double* tw, hipStream_t s);
 // batches of at most latency_max_batch ciphertexts use the latency kernel (one ciphertext per workgroup)
+// n_cus: the device's compute-unit count (the batch kernel's priority split and start stagger follow the dispatch
+// half-rounds, pbs_fft.hip dispatch_half); <= 0 = 256 (MI355X)
 hipError_t launch_blind_rotate_fft(const u64* lwe_in, size_t B, int n, const u64* luts, const u32* lut_index,
                                    int n_lut, const double* bsk_f, const double* tw, u64* out_big, u64* out_acc,
-                                   hipStream_t s, size_t latency_max_batch = 0);
+                                   hipStream_t s, size_t latency_max_batch = 0, int n_cus = 0);
 hipError_t launch_sample_extract_torus(const u64* acc, size_t B, u64* out, hipStream_t s);
 hipError_t launch_fft_fwd(const u64* in, size_t count, double* out, const double* tw, hipStream_t s);
 hipError_t launch_fft_inv(const double* in, size_t count, double* out, const double* tw, hipStream_t s);
