@@ -208,6 +208,22 @@ int tfhe_hip_pbs(tfhe_ctx* ctx, const uint64_t* lwe_in, size_t B, const uint64_t
 #define TFHE_HIP_NULL_STREAM ((void*)(intptr_t)-1)
 int tfhe_hip_pbs_async(tfhe_ctx* ctx, const uint64_t* d_lwe_in, size_t B, const uint64_t* d_luts, size_t n_lut,
                        const uint32_t* d_lut_index, uint64_t* d_lwe_out, void* stream);
+/* Many-LUT PBS: n_fn functions of each input from ONE blind rotation.  Replaces tfhe-rs
+ * ServerKey::apply_many_lookup_table.  A many-LUT lays n_fn tables side by side in one accumulator and
+ * output f is the sample extracted at degree f * stride; the caller guarantees that every input uses only
+ * the first 1/n_fn of the message x carry space.  No builder of its own is needed (tfhe-rs
+ * generate_many_lookup_table): the many-LUT over n_fn tables of msg_modulus / n_fn entries is
+ * tfhe_hip_lut_from_table applied to their concatenation, with stride = N / n_fn; the half-box rotation is
+ * unchanged.  lwe_out: B x n_fn x (io_dim + 1), ciphertext-major (row b * n_fn + f).  Requires n_fn >= 1,
+ * stride >= 1, (n_fn - 1) * stride < N and B * n_fn <= 0x7FFFFFFF (EINVAL otherwise, before any device work).
+ * Host buffers, synchronous, sharded like tfhe_hip_pbs. */
+int tfhe_hip_pbs_many(tfhe_ctx* ctx, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,
+                      const uint32_t* lut_index, uint32_t n_fn, uint32_t stride, uint64_t* lwe_out);
+/* The same on device buffers (tfhe-rs apply_many_lookup_table on resident ciphertexts); stream and workspace
+ * rules of tfhe_hip_pbs_async. */
+int tfhe_hip_pbs_many_async(tfhe_ctx* ctx, const uint64_t* d_lwe_in, size_t B, const uint64_t* d_luts, size_t n_lut,
+                            const uint32_t* d_lut_index, uint32_t n_fn, uint32_t stride, uint64_t* d_lwe_out,
+                            void* stream);
 
 /* Stage-level entry points (host buffers) used by the parity tests. */
 /* acc_out: B x (k+1) x N values in the GLWE ring (Z_p for NTT, torus for FFT64) after the CMUX loop. */
@@ -215,6 +231,11 @@ int tfhe_hip_blind_rotate(tfhe_ctx* ctx, const uint64_t* lwe_in, size_t B, const
                           const uint32_t* lut_index, uint64_t* acc_out);
 /* acc (Z_p, B x (k+1)N) -> LWE under the GLWE key, converted to 2^64: B x (kN + 1). */
 int tfhe_hip_sample_extract(tfhe_ctx* ctx, const uint64_t* acc, size_t B, uint64_t* lwe_big_out);
+/* The extraction stage of tfhe-rs apply_many_lookup_table (extract_lwe_sample_from_glwe_ciphertext at
+ * MonomialDegree(f * stride)): acc as above -> B x n_fn x (kN + 1), row b * n_fn + f = the sample at degree
+ * f * stride, converted to 2^64 like tfhe_hip_sample_extract. */
+int tfhe_hip_sample_extract_many(tfhe_ctx* ctx, const uint64_t* acc, size_t B, uint32_t n_fn, uint32_t stride,
+                                 uint64_t* lwe_big_out);
 /* B x (kN+1) -> B x (n+1). */
 int tfhe_hip_keyswitch(tfhe_ctx* ctx, const uint64_t* lwe_big, size_t B, uint64_t* lwe_small_out);
 /* Negacyclic NTT over Z_p of count polynomials of size N, in place, natural order:

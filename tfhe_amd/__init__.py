@@ -113,7 +113,8 @@ ABI_SYMBOLS = (
     "tfhe_hip_server_keygen_k", "tfhe_hip_ms_zeros_keygen_k", "tfhe_hip_lwe_encrypt_k", "tfhe_hip_ndev",
     "tfhe_hip_device_at", "tfhe_hip_key_bcast_mode", "tfhe_hip_br_kernel", "tfhe_hip_aes128_block",
     "tfhe_hip_csprng_words", "tfhe_hip_seeded_server_keygen_k", "tfhe_hip_seeded_lwe_list_k", "tfhe_hip_decompress_bsk",
-    "tfhe_hip_decompress_ksk", "tfhe_hip_decompress_lwe_list",
+    "tfhe_hip_decompress_ksk", "tfhe_hip_decompress_lwe_list", "tfhe_hip_pbs_many", "tfhe_hip_pbs_many_async",
+    "tfhe_hip_sample_extract_many",
 )
 
 # P-FHEVM modulus-switch noise reduction key (include/tfhe_hip.h TFHE_HIP_MS_FHEVM_*)
@@ -193,6 +194,13 @@ def lib():
         L.tfhe_hip_blind_rotate.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, _U64P, ctypes.c_size_t, _U32P,
                                             _U64P]
         L.tfhe_hip_sample_extract.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, _U64P]
+        L.tfhe_hip_pbs_many.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, _U64P, ctypes.c_size_t, _U32P,
+                                        ctypes.c_uint32, ctypes.c_uint32, _U64P]
+        L.tfhe_hip_pbs_many_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                              ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.c_void_p, ctypes.c_void_p]
+        L.tfhe_hip_sample_extract_many.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, ctypes.c_uint32,
+                                                   ctypes.c_uint32, _U64P]
         L.tfhe_hip_keyswitch.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, _U64P]
         L.tfhe_hip_ntt_fwd.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t]
         L.tfhe_hip_ntt_inv.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t]
@@ -394,6 +402,22 @@ def lut_from_table(N: int, msg_modulus: int, table: Sequence[int], delta_out: in
     return out
 
 
+def lut_many(N: int, msg_modulus: int, tables: Sequence[Sequence[int]], delta_out: int):
+    """tfhe-rs ``generate_many_lookup_table``: n_fn tables of ``msg_modulus // n_fn`` entries side by side in
+    one accumulator -> (lut, stride).  After one blind rotation of an input that uses only the first
+    ``1/n_fn`` of the message space, function f is the sample at degree ``f * stride``
+    (``Engine.pbs_many``).  The LUT is ``lut_from_table`` of the concatenated tables."""
+    n_fn = len(tables)
+    if n_fn < 1 or n_fn & (n_fn - 1) or msg_modulus % n_fn or N % n_fn:
+        raise ValueError(f"lut_many: n_fn = {n_fn} must be a power of two dividing msg_modulus = {msg_modulus}")
+    per = msg_modulus // n_fn
+    for f, t in enumerate(tables):
+        if len(t) != per:
+            raise ValueError(f"lut_many: table {f} has {len(t)} entries, expected msg_modulus / n_fn = {per}")
+    flat = [v for t in tables for v in t]
+    return lut_from_table(N, msg_modulus, flat, delta_out), N // n_fn
+
+
 # ------------------------------------------------------------------------------------- engine
 class Engine:
     """A device engine over one or more GPUs (``device``: an ordinal or a sequence of ordinals, one
@@ -536,6 +560,53 @@ class Engine:
         if d_in.shape[0]:
             self.pbs_async(d_in.contiguous(), d_luts, d_out, d_lut_index)
         return d_out
+
+    def pbs_many(self, cts: np.ndarray, luts: np.ndarray, n_fn: int, stride: int, lut_index=None) -> np.ndarray:
+        """tfhe-rs ``apply_many_lookup_table``, batched over host arrays: one blind rotation per input and
+        ``n_fn`` outputs, function f extracted at degree ``f * stride`` (``lut_many`` builds the LUTs):
+        (B, dim+1) -> (B, n_fn, dim+1)."""
+        dim = self.params.io_dim
+        cts = _c_u64(cts).reshape(-1, dim + 1)
+        luts = _c_u64(luts).reshape(-1, self.params.N)
+        n_fn, stride = int(n_fn), int(stride)
+        if not (0 <= n_fn < 1 << 32 and 0 <= stride < 1 << 32):
+            raise ValueError("n_fn and stride must fit 32 bits")
+        out = np.zeros((cts.shape[0], max(n_fn, 0), dim + 1), dtype=np.uint64)
+        li = None
+        if lut_index is not None:
+            li = np.ascontiguousarray(np.asarray(lut_index, dtype=np.uint32))
+            if li.shape[0] != cts.shape[0]:
+                raise ValueError("lut_index must have one entry per ciphertext")
+        _check(lib().tfhe_hip_pbs_many(self._h, _u64(cts), cts.shape[0], _u64(luts), luts.shape[0],
+                                       li.ctypes.data_as(_U32P) if li is not None else None, n_fn, stride, _u64(out)))
+        return out
+
+    def pbs_many_async(self, d_in, d_luts, d_out, n_fn: int, stride: int, d_lut_index=None, stream=None) -> None:
+        """Device-resident ``pbs_many`` (torch tensors on this device; d_out: (B, n_fn, dim+1)), enqueued on
+        ``stream`` like ``pbs_async``."""
+        B = d_in.shape[0]
+        stream = _stream_handle(stream, self.device)
+        n_lut = d_luts.numel() // self.params.N
+        _check(lib().tfhe_hip_pbs_many_async(
+            self._h, ctypes.c_void_p(d_in.data_ptr()), B, ctypes.c_void_p(d_luts.data_ptr()), n_lut,
+            ctypes.c_void_p(d_lut_index.data_ptr()) if d_lut_index is not None else None, int(n_fn), int(stride),
+            ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(stream)))
+
+    def pbs_many_device(self, d_in, d_luts, n_fn: int, stride: int, d_lut_index=None):
+        """pbs_many_async into a fresh tensor: (B, dim+1) on this device -> (B, n_fn, dim+1), queued on torch's
+        current stream (no host synchronisation)."""
+        d_out = d_in.new_empty((d_in.shape[0], int(n_fn), d_in.shape[1]))
+        if d_in.shape[0]:
+            self.pbs_many_async(d_in.contiguous(), d_luts, d_out, n_fn, stride, d_lut_index)
+        return d_out
+
+    def sample_extract_many(self, acc: np.ndarray, n_fn: int, stride: int) -> np.ndarray:
+        """Samples of each accumulator at degrees ``f * stride``, f < n_fn: (B, (k+1)N) -> (B, n_fn, kN+1)."""
+        p = self.params
+        acc = _c_u64(acc).reshape(-1, (p.k + 1) * p.N)
+        out = np.zeros((acc.shape[0], max(int(n_fn), 0), p.k * p.N + 1), dtype=np.uint64)
+        _check(lib().tfhe_hip_sample_extract_many(self._h, _u64(acc), acc.shape[0], int(n_fn), int(stride), _u64(out)))
+        return out
 
     def blind_rotate(self, cts: np.ndarray, luts: np.ndarray, lut_index=None) -> np.ndarray:
         p = self.params

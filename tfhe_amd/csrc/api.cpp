@@ -151,6 +151,8 @@ struct tfhe_shard {
   // workspaces: every user waits for `ws_free` (the previous user's completion) on its own stream
   u64* d_big = nullptr;
   size_t big_cap = 0;  // bytes
+  u64* d_acc = nullptr;  // blind-rotation accumulators of a many-LUT PBS
+  size_t acc_cap = 0;    // bytes
   void* d_stage = nullptr;
   size_t stage_cap = 0;  // bytes
   void* d_ks_dig = nullptr;
@@ -306,6 +308,52 @@ int pbs_device(tfhe_ctx* c, shard& s, const u64* d_in, size_t B, const u64* d_lu
     HIP_TRY(launch_br(c, s, s.d_big, B, d_luts, d_idx, n_lut, d_out, nullptr, st));
     timed_end(c, s, 0, st);
   }
+  return 0;
+}
+
+// Many-LUT PBS on device buffers (same contract as pbs_device): one blind rotation per input into the shard's
+// accumulator workspace, then the samples at degrees f * stride, f < n_fn (sample_extract_many.hip), timed with
+// the rotation in slot 0.  Order 1 writes them to d_out directly; order 0 keyswitches the n_fn * B rows.
+// d_out: B x n_fn x (io_dim + 1), ciphertext-major.
+int pbs_many_device(tfhe_ctx* c, shard& s, const u64* d_in, size_t B, const u64* d_luts, size_t n_lut, const u32* d_idx,
+                    int n_fn, int stride, u64* d_out, hipStream_t st) {
+  const size_t big = (size_t)c->p.k * c->p.N + 1, small = (size_t)c->p.n + 1;
+  const size_t acc_len = (size_t)(c->p.k + 1) * c->p.N, rows = B * (size_t)n_fn;
+  RC_TRY(grow(s, (void**)&s.d_big, &s.big_cap, (c->p.order == 0 ? rows * big : B * small) * sizeof(u64)));
+  RC_TRY(grow(s, (void**)&s.d_acc, &s.acc_cap, B * acc_len * sizeof(u64)));
+  const bool zp = !is_fft(c->p);
+  if (c->p.order == 0) {
+    timed_begin(c, s, 0, st);
+    HIP_TRY(launch_br(c, s, d_in, B, d_luts, d_idx, n_lut, nullptr, s.d_acc, st));
+    HIP_TRY(tfhe::launch_sample_extract_many(s.d_acc, B, (int)c->p.k, (int)c->p.N, zp, n_fn, stride, s.d_big, st));
+    timed_end(c, s, 0, st);
+    timed_begin(c, s, 1, st);
+    RC_TRY(launch_ks(c, s, s.d_big, rows, d_out, st));
+    timed_end(c, s, 1, st);
+  } else {
+    timed_begin(c, s, 1, st);
+    RC_TRY(launch_ks(c, s, d_in, B, s.d_big, st));
+    timed_end(c, s, 1, st);
+    if (c->ms_count) {
+      timed_begin(c, s, 2, st);
+      HIP_TRY(launch_ms(c, s, s.d_big, B, nullptr, st));
+      timed_end(c, s, 2, st);
+    }
+    timed_begin(c, s, 0, st);
+    HIP_TRY(launch_br(c, s, s.d_big, B, d_luts, d_idx, n_lut, nullptr, s.d_acc, st));
+    HIP_TRY(tfhe::launch_sample_extract_many(s.d_acc, B, (int)c->p.k, (int)c->p.N, zp, n_fn, stride, d_out, st));
+    timed_end(c, s, 0, st);
+  }
+  return 0;
+}
+
+// n_fn functions at degrees f * stride of an N-coefficient accumulator, B inputs
+int check_many(const tfhe_ctx* c, const char* what, size_t B, uint32_t n_fn, uint32_t stride) {
+  if (n_fn < 1 || stride < 1) return fail(TFHE_HIP_EINVAL, "%s: n_fn = %u, stride = %u (both must be >= 1)", what, n_fn, stride);
+  if ((uint64_t)(n_fn - 1) * stride >= c->p.N)
+    return fail(TFHE_HIP_EINVAL, "%s: degree (n_fn - 1) * stride = %llu >= N = %u", what,
+                (unsigned long long)(n_fn - 1) * stride, c->p.N);
+  if (B > 0x7FFFFFFF || B * (uint64_t)n_fn > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "%s: B * n_fn too large", what);
   return 0;
 }
 
@@ -536,6 +584,7 @@ void shard_free(shard& s) {
   (void)hipFree(s.d_tw);
   (void)hipFree(s.d_ms_zeros);
   (void)hipFree(s.d_big);
+  (void)hipFree(s.d_acc);
   (void)hipFree(s.d_stage);
   if (s.ws_free) (void)hipEventDestroy(s.ws_free);
   if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -1002,6 +1051,61 @@ int tfhe_hip_pbs(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const uint64_t* 
   });
 }
 
+int tfhe_hip_pbs_many_async(tfhe_ctx* c, const uint64_t* d_in, size_t B, const uint64_t* d_luts, size_t n_lut,
+                            const uint32_t* d_idx, uint32_t n_fn, uint32_t stride, uint64_t* d_out, void* stream) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "pbs_many: null ctx");
+  if (!c->keys) return fail(TFHE_HIP_ENOKEYS, "pbs_many: keys not loaded");
+  RC_TRY(check_many(c, "pbs_many", B, n_fn, stride));
+  if (B == 0) return 0;
+  if (!d_in || !d_luts || !n_lut || !d_out) return fail(TFHE_HIP_EINVAL, "pbs_many: null buffer or n_lut == 0");
+  std::lock_guard<std::mutex> lk(c->mu);
+  size_t si = 0;
+  if (c->sh.size() > 1) {  // the shard whose device holds the input
+    hipPointerAttribute_t a;
+    HIP_TRY(hipPointerGetAttributes(&a, d_in));
+    si = c->sh.size();
+    for (size_t i = 0; i < c->sh.size() && si == c->sh.size(); i++)
+      if (c->sh[i].device == a.device) si = i;
+    if (si == c->sh.size()) return fail(TFHE_HIP_EINVAL, "pbs_many_async: input on device %d, no shard there", a.device);
+  }
+  shard& s = c->sh[si];
+  DeviceGuard g(s.device);
+  hipStream_t st = stream == TFHE_HIP_NULL_STREAM ? (hipStream_t)0 : stream ? (hipStream_t)stream : s.stream;
+  RC_TRY(ws_begin(s, st));
+  RC_TRY(pbs_many_device(c, s, d_in, B, d_luts, n_lut, d_idx, (int)n_fn, (int)stride, d_out, st));
+  return ws_end(s, st);
+}
+
+int tfhe_hip_pbs_many(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,
+                      const uint32_t* lut_index, uint32_t n_fn, uint32_t stride, uint64_t* lwe_out) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "pbs_many: null ctx");
+  if (!c->keys) return fail(TFHE_HIP_ENOKEYS, "pbs_many: keys not loaded");
+  RC_TRY(check_many(c, "pbs_many", B, n_fn, stride));
+  if (B == 0) return 0;
+  if (!lwe_in || !luts || !n_lut || !lwe_out) return fail(TFHE_HIP_EINVAL, "pbs_many: null buffer or n_lut == 0");
+  if (lut_index)
+    for (size_t q = 0; q < B; q++)
+      if (lut_index[q] >= n_lut)
+        return fail(TFHE_HIP_EINVAL, "pbs_many: lut_index[%zu] = %u >= n_lut %zu", q, lut_index[q], n_lut);
+  std::lock_guard<std::mutex> lk(c->mu);
+  const size_t dim = io_dim(c->p) + 1;
+  return for_each_slice(c, B, [&](size_t i, size_t lo, size_t hi) -> int {
+    shard& s = c->sh[i];
+    const size_t b = hi - lo, out_words = b * n_fn * dim;
+    RC_TRY(ws_begin(s, s.stream));
+    std::vector<void*> d;
+    RC_TRY(stage(s, {{lwe_in + lo * dim, b * dim * 8}, {luts, n_lut * c->p.N * 8},
+                     {lut_index ? lut_index + lo : nullptr, lut_index ? b * 4 : 0}},
+                 d, out_words * 8));
+    RC_TRY(pbs_many_device(c, s, (const u64*)d[0], b, (const u64*)d[1], n_lut, (const u32*)d[2], (int)n_fn, (int)stride,
+                           (u64*)d[3], s.stream));
+    HIP_TRY(hipMemcpyAsync(lwe_out + lo * n_fn * dim, d[3], out_words * 8, hipMemcpyDeviceToHost, s.stream));
+    RC_TRY(ws_end(s, s.stream));
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    return 0;
+  });
+}
+
 int tfhe_hip_blind_rotate(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,
                           const uint32_t* lut_index, uint64_t* acc_out) {
   if (!c) return fail(TFHE_HIP_EINVAL, "blind_rotate: null ctx");
@@ -1042,6 +1146,26 @@ int tfhe_hip_sample_extract(tfhe_ctx* c, const uint64_t* acc, size_t B, uint64_t
   else if (c->p.N == 2048) HIP_TRY(tfhe::launch_sample_extract_2048((const u64*)d[0], B, (u64*)d[1], s.stream));
   else HIP_TRY(tfhe::launch_sample_extract((const u64*)d[0], B, (u64*)d[1], s.stream));
   HIP_TRY(hipMemcpyAsync(out, d[1], B * big * 8, hipMemcpyDeviceToHost, s.stream));
+  RC_TRY(ws_end(s, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  return 0;
+}
+
+int tfhe_hip_sample_extract_many(tfhe_ctx* c, const uint64_t* acc, size_t B, uint32_t n_fn, uint32_t stride,
+                                 uint64_t* out) {
+  if (!c || (B && (!acc || !out))) return fail(TFHE_HIP_EINVAL, "sample_extract_many: bad arguments");
+  RC_TRY(check_many(c, "sample_extract_many", B, n_fn, stride));
+  if (B == 0) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  shard& s = c->sh[0];
+  DeviceGuard g(s.device);
+  const size_t acc_len = (size_t)(c->p.k + 1) * c->p.N, big = (size_t)c->p.k * c->p.N + 1;
+  RC_TRY(ws_begin(s, s.stream));
+  std::vector<void*> d;
+  RC_TRY(stage(s, {{acc, B * acc_len * 8}}, d, B * n_fn * big * 8));
+  HIP_TRY(tfhe::launch_sample_extract_many((const u64*)d[0], B, (int)c->p.k, (int)c->p.N, !is_fft(c->p), (int)n_fn,
+                                           (int)stride, (u64*)d[1], s.stream));
+  HIP_TRY(hipMemcpyAsync(out, d[1], B * n_fn * big * 8, hipMemcpyDeviceToHost, s.stream));
   RC_TRY(ws_end(s, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
   return 0;

@@ -95,5 +95,9 @@ hipError_t launch_pks_pack_mfma(const u64* lwes, size_t count, int in_dim, int b
 inline size_t ms_zeros_pitch(size_t count) { return (count + 63) / 64 * 64; }
 hipError_t launch_ms_reduce(u64* lwe, size_t B, int n, const u64* zeros, int count, int log2_2N, double bound,
                             double r_sigma, double var128, int* picks, hipStream_t s);
+// many-LUT sample extraction (sample_extract_many.hip): row b * n_fn + f of `out` is the sample of accumulator b
+// at degree f * stride, for either ring (zp: Z_p accumulators, converted to 2^64) and N <= 2048; acc 16-byte aligned
+hipError_t launch_sample_extract_many(const u64* acc, size_t B, int k, int N, bool zp, int n_fn, int stride, u64* out,
+                                      hipStream_t s);
 hipError_t launch_ntt2048_inv(u64* polys, size_t count, const u64* tw, u64 ninv, hipStream_t s);
 }  // namespace tfhe

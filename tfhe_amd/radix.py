@@ -44,10 +44,17 @@ MAX_LAUNCH = 1 << 18  # ciphertexts per engine call (P-FHEVM: 2 x 2049 x 8 B x 2
 
 class RadixCircuit:
     """Lockstep executor: each level is a list of (lin array (..., dim+1), table) pairs; every
-    distinct table becomes one LUT of the launch and each ciphertext indexes its own."""
+    distinct table becomes one LUT of the launch and each ciphertext indexes its own.
 
-    def __init__(self, engine):
+    A level entry whose second member is a tuple of n_fn tables of SPACE / n_fn entries is a many-LUT
+    request (tfhe-rs ``apply_many_lookup_table``): one blind rotation per ciphertext, n_fn results, and the
+    caller guarantees every value of ``lin`` is < SPACE / n_fn.  ``many_lut=True`` lets the circuits that
+    know such a bound (``g_propagate``) use it; the default keeps every circuit on one table per rotation.
+    ``pbs_count`` counts blind rotations, ``launches`` levels."""
+
+    def __init__(self, engine, many_lut: bool = False):
         self.engine = engine
+        self.many_lut = bool(many_lut)
         p = engine.params
         self.dim = p.k * p.N + 1 if p.order == 1 else p.n + 1
         self.N = p.N
@@ -69,10 +76,65 @@ class RadixCircuit:
             out[..., -1] = (v % np.uint64(SPACE)) * np.uint64(DELTA)
         return out
 
-    def bootstrap(self, reqs: Sequence[Tuple[np.ndarray, Tuple[int, ...]]]) -> List[np.ndarray]:
-        shapes = [a.shape[:-1] for a, _ in reqs]
+    def bootstrap(self, reqs: Sequence[Tuple[np.ndarray, Tuple[int, ...]]]) -> list:
         if not reqs:
             return []
+        many = [i for i, (_, t) in enumerate(reqs) if isinstance(t[0], tuple)]
+        if not many:
+            res = self._bootstrap_single(reqs)
+        else:
+            res = [None] * len(reqs)
+            single = [i for i in range(len(reqs)) if i not in set(many)]
+            if single:
+                for i, r in zip(single, self._bootstrap_single([reqs[i] for i in single])):
+                    res[i] = r
+            for n_fn in sorted({len(reqs[i][1]) for i in many}):
+                grp = [i for i in many if len(reqs[i][1]) == n_fn]
+                for i, r in zip(grp, self._bootstrap_many([reqs[i] for i in grp], n_fn)):
+                    res[i] = r
+        self.launches += 1
+        return res
+
+    def _bootstrap_many(self, reqs, n_fn: int) -> List[Tuple[np.ndarray, ...]]:
+        """The many-LUT entries of one level with n_fn tables each: one `_pbs_many` call (in chunks of
+        MAX_LAUNCH outputs); a tuple of n_fn arrays per entry."""
+        groups, index, idx_parts, flat_parts = [], {}, [], []
+        for a, ts in reqs:
+            if any(len(t) * n_fn != SPACE for t in ts):
+                raise ValueError(f"a many-LUT entry of {n_fn} tables takes tables of {SPACE // n_fn} entries")
+            if ts not in index:
+                index[ts] = len(groups)
+                groups.append(ts)
+            cnt = int(np.prod(a.shape[:-1], dtype=np.int64))
+            flat_parts.append(a.reshape(cnt, self.dim))
+            idx_parts.append(np.full(cnt, index[ts], dtype=np.uint32))
+        flat = np.concatenate(flat_parts, axis=0)
+        idx = np.concatenate(idx_parts)
+        step = max(1, MAX_LAUNCH // n_fn)
+        outs = [self._pbs_many(flat[o:o + step], groups, idx[o:o + step], n_fn) for o in range(0, flat.shape[0], step)]
+        out = outs[0] if len(outs) == 1 else np.concatenate(outs, axis=0)
+        self.pbs_count += flat.shape[0]
+        res, off = [], 0
+        for a, _ in reqs:
+            s = a.shape[:-1]
+            cnt = int(np.prod(s, dtype=np.int64))
+            res.append(tuple(out[off:off + cnt, f].reshape(s + (self.dim,)) for f in range(n_fn)))
+            off += cnt
+        return res
+
+    def _pbs_many(self, flat, table_groups, idx, n_fn: int):
+        """(cnt, dim) -> (cnt, n_fn, dim): ciphertext q through the many-LUT of table_groups[idx[q]]."""
+        luts = np.stack([self.many_lut_of(g) for g in table_groups])
+        return self.engine.pbs_many(flat, luts, n_fn, self.N // n_fn, idx)
+
+    def many_lut_of(self, group: Tuple[Tuple[int, ...], ...]) -> np.ndarray:
+        if group not in self._luts:
+            from . import lut_many
+            self._luts[group] = lut_many(self.N, SPACE, [list(t) for t in group], DELTA)[0]
+        return self._luts[group]
+
+    def _bootstrap_single(self, reqs: Sequence[Tuple[np.ndarray, Tuple[int, ...]]]) -> List[np.ndarray]:
+        shapes = [a.shape[:-1] for a, _ in reqs]
         tables = []
         index = {}
         idx_parts = []
@@ -92,7 +154,6 @@ class RadixCircuit:
                 for o in range(0, flat.shape[0], MAX_LAUNCH)]
         out = outs[0] if len(outs) == 1 else np.concatenate(outs, axis=0)
         self.pbs_count += flat.shape[0]
-        self.launches += 1
         res, off = [], 0
         for s in shapes:
             cnt = int(np.prod(s, dtype=np.int64))
@@ -222,6 +283,8 @@ T_MSG = _table(lambda v: v % MSG)
 T_STATE = _table(lambda v: 2 if v >= MSG else (1 if v == MSG - 1 else 0))   # of a block sum <= 7
 T_MERGE = _biv(lambda hi, lo: lo if hi == 1 else hi)                       # prefix op on states
 T_APPLY = _biv(lambda st, m: (m + (1 if st == 2 else 0)) % MSG)            # carry-in from the prefix
+# both tables of a block sum <= 7 from one blind rotation (a 2-function many-LUT: the sum leaves the top bit free)
+T_MSG_STATE = (T_MSG[:SPACE // 2], T_STATE[:SPACE // 2])
 
 
 def g_propagate(c: RadixCircuit, s: np.ndarray, carry_in: bool):
@@ -230,7 +293,17 @@ def g_propagate(c: RadixCircuit, s: np.ndarray, carry_in: bool):
     if carry_in:
         s = s.copy()
         s[:, 0] = _add(s[:, 0], _const(c, (B,), 1))
-    msg, st = yield [(s, T_MSG), (s, T_STATE)]
+    if not c.many_lut:
+        msg, st = yield [(s, T_MSG), (s, T_STATE)]
+    elif not carry_in:
+        ((msg, st),) = yield [(s, T_MSG_STATE)]
+    elif nb == 1:
+        msg, st = yield [(s, T_MSG), (s, T_STATE)]
+    else:
+        # block 0 holds up to 8 with the carry-in: all 16 values, so it stays on one table per rotation
+        (msg_hi, st_hi), msg0, st0 = yield [(s[:, 1:], T_MSG_STATE), (s[:, :1], T_MSG), (s[:, :1], T_STATE)]
+        msg = np.concatenate([msg0, msg_hi], axis=1)
+        st = np.concatenate([st0, st_hi], axis=1)
     # Kogge-Stone over block states: prefix[j] = state of blocks 0..j
     d = 1
     while d < nb:
