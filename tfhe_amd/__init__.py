@@ -524,19 +524,30 @@ class Engine:
         return lut_constant(self.params.N, MU)
 
     # -- hot path ---------------------------------------------------------------------------
-    def pbs(self, cts: np.ndarray, luts: np.ndarray, lut_index=None) -> np.ndarray:
-        """Batched keyswitch_programmable_bootstrap over host arrays: (B, dim+1) -> (B, dim+1)."""
-        dim = self.params.io_dim
-        cts = _c_u64(cts).reshape(-1, dim + 1)
+    def _pbs_host_args(self, cts, luts, lut_index):
+        """Host arrays of pbs / pbs_many -> (the (B, dim+1) ciphertexts, the C arguments up to ``lut_index``)."""
+        cts = _c_u64(cts).reshape(-1, self.params.io_dim + 1)
         luts = _c_u64(luts).reshape(-1, self.params.N)
-        out = np.zeros_like(cts)
         li = None
         if lut_index is not None:
             li = np.ascontiguousarray(np.asarray(lut_index, dtype=np.uint32))
             if li.shape[0] != cts.shape[0]:
                 raise ValueError("lut_index must have one entry per ciphertext")
-        _check(lib().tfhe_hip_pbs(self._h, _u64(cts), cts.shape[0], _u64(luts), luts.shape[0],
-                                  li.ctypes.data_as(_U32P) if li is not None else None, _u64(out)))
+        return cts, (self._h, _u64(cts), cts.shape[0], _u64(luts), luts.shape[0],
+                     li.ctypes.data_as(_U32P) if li is not None else None)
+
+    def _pbs_async_args(self, d_in, d_luts, d_lut_index, d_out, stream):
+        """Device tensors of pbs_async / pbs_many_async -> the C arguments (up to ``d_idx``, from ``d_out`` on)."""
+        head = (self._h, ctypes.c_void_p(d_in.data_ptr()), d_in.shape[0], ctypes.c_void_p(d_luts.data_ptr()),
+                d_luts.numel() // self.params.N,
+                ctypes.c_void_p(d_lut_index.data_ptr()) if d_lut_index is not None else None)
+        return head, (ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(_stream_handle(stream, self.device)))
+
+    def pbs(self, cts: np.ndarray, luts: np.ndarray, lut_index=None) -> np.ndarray:
+        """Batched keyswitch_programmable_bootstrap over host arrays: (B, dim+1) -> (B, dim+1)."""
+        cts, head = self._pbs_host_args(cts, luts, lut_index)
+        out = np.zeros_like(cts)
+        _check(lib().tfhe_hip_pbs(*head, _u64(out)))
         return out
 
     def keyswitch_programmable_bootstrap(self, ct: np.ndarray, acc: np.ndarray) -> np.ndarray:
@@ -545,13 +556,8 @@ class Engine:
     def pbs_async(self, d_in, d_luts, d_out, d_lut_index=None, stream=None) -> None:
         """Device-resident batch (torch tensors on this device), enqueued on ``stream``
         (a torch.cuda.Stream or raw handle; default torch's current stream if torch is loaded)."""
-        B = d_in.shape[0]
-        stream = _stream_handle(stream, self.device)
-        n_lut = d_luts.numel() // self.params.N
-        _check(lib().tfhe_hip_pbs_async(self._h, ctypes.c_void_p(d_in.data_ptr()), B,
-                                        ctypes.c_void_p(d_luts.data_ptr()), n_lut,
-                                        ctypes.c_void_p(d_lut_index.data_ptr()) if d_lut_index is not None else None,
-                                        ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(stream)))
+        head, tail = self._pbs_async_args(d_in, d_luts, d_lut_index, d_out, stream)
+        _check(lib().tfhe_hip_pbs_async(*head, *tail))
 
     def pbs_device(self, d_in, d_luts, d_lut_index=None):
         """pbs_async into a fresh tensor: (B, dim+1) int64 on this device -> the same shape, queued on torch's
@@ -565,32 +571,19 @@ class Engine:
         """tfhe-rs ``apply_many_lookup_table``, batched over host arrays: one blind rotation per input and
         ``n_fn`` outputs, function f extracted at degree ``f * stride`` (``lut_many`` builds the LUTs):
         (B, dim+1) -> (B, n_fn, dim+1)."""
-        dim = self.params.io_dim
-        cts = _c_u64(cts).reshape(-1, dim + 1)
-        luts = _c_u64(luts).reshape(-1, self.params.N)
+        cts, head = self._pbs_host_args(cts, luts, lut_index)
         n_fn, stride = int(n_fn), int(stride)
         if not (0 <= n_fn < 1 << 32 and 0 <= stride < 1 << 32):
             raise ValueError("n_fn and stride must fit 32 bits")
-        out = np.zeros((cts.shape[0], max(n_fn, 0), dim + 1), dtype=np.uint64)
-        li = None
-        if lut_index is not None:
-            li = np.ascontiguousarray(np.asarray(lut_index, dtype=np.uint32))
-            if li.shape[0] != cts.shape[0]:
-                raise ValueError("lut_index must have one entry per ciphertext")
-        _check(lib().tfhe_hip_pbs_many(self._h, _u64(cts), cts.shape[0], _u64(luts), luts.shape[0],
-                                       li.ctypes.data_as(_U32P) if li is not None else None, n_fn, stride, _u64(out)))
+        out = np.zeros((cts.shape[0], n_fn, cts.shape[1]), dtype=np.uint64)
+        _check(lib().tfhe_hip_pbs_many(*head, n_fn, stride, _u64(out)))
         return out
 
     def pbs_many_async(self, d_in, d_luts, d_out, n_fn: int, stride: int, d_lut_index=None, stream=None) -> None:
         """Device-resident ``pbs_many`` (torch tensors on this device; d_out: (B, n_fn, dim+1)), enqueued on
         ``stream`` like ``pbs_async``."""
-        B = d_in.shape[0]
-        stream = _stream_handle(stream, self.device)
-        n_lut = d_luts.numel() // self.params.N
-        _check(lib().tfhe_hip_pbs_many_async(
-            self._h, ctypes.c_void_p(d_in.data_ptr()), B, ctypes.c_void_p(d_luts.data_ptr()), n_lut,
-            ctypes.c_void_p(d_lut_index.data_ptr()) if d_lut_index is not None else None, int(n_fn), int(stride),
-            ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(stream)))
+        head, tail = self._pbs_async_args(d_in, d_luts, d_lut_index, d_out, stream)
+        _check(lib().tfhe_hip_pbs_many_async(*head, int(n_fn), int(stride), *tail))
 
     def pbs_many_device(self, d_in, d_luts, n_fn: int, stride: int, d_lut_index=None):
         """pbs_many_async into a fresh tensor: (B, dim+1) on this device -> (B, n_fn, dim+1), queued on torch's

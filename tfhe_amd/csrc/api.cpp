@@ -8,8 +8,6 @@
 #include <dlfcn.h>
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -23,6 +21,7 @@
 #include "../../include/tfhe_hip.h"
 #include "client.h"
 #include "gl64.h"
+#include "host_common.h"
 #include "pbs_kernels.h"
 
 using tfhe::u32;
@@ -30,31 +29,7 @@ using tfhe::u64;
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess)                                                                      \
-      return fail(_e == hipErrorOutOfMemory ? TFHE_HIP_ENOMEM : TFHE_HIP_EDEVICE, "%s: %s (%s:%d)", #expr, \
-                  hipGetErrorString(_e), __FILE__, __LINE__);                                  \
-  } while (0)
-
-#define RC_TRY(expr)      \
-  do {                    \
-    int _rc = (expr);     \
-    if (_rc) return _rc;  \
-  } while (0)
+thread_local std::string g_err;  // tfhe_hip_last_error; written through tfhe_hip_set_error (fail())
 
 bool params_valid(const tfhe_params* p) {
   return p && p->n > 0 && p->k > 0 && p->N >= 32 && (p->N & (p->N - 1)) == 0 && p->pbs_level > 0 &&
@@ -124,18 +99,6 @@ Rccl& rccl() {
   return r;
 }
 
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
 }  // namespace
 
 // One device's slice of an engine.
@@ -187,12 +150,7 @@ using shard = tfhe_shard;
 int grow(shard& s, void** ptr, size_t* cap, size_t bytes) {
   if (*cap >= bytes) return 0;
   if (s.ws_used) HIP_TRY(hipEventSynchronize(s.ws_free));  // no launch may still read the old buffer
-  if (*ptr) (void)hipFree(*ptr);
-  *ptr = nullptr;
-  *cap = 0;
-  HIP_TRY(hipMalloc(ptr, bytes));
-  *cap = bytes;
-  return 0;
+  return grow_device_buffer(ptr, cap, bytes);
 }
 
 // Workspace ordering across streams (tfhe_hip_pbs_async may be called on any stream): the stream that
@@ -281,52 +239,37 @@ int launch_ks(tfhe_ctx* c, shard& s, const u64* in_big, size_t B, u64* out, hipS
   return 0;
 }
 
+struct many_args {  // the many-LUT arguments of tfhe_hip_pbs_many*; a null pointer = plain PBS
+  uint32_t n_fn, stride;
+};
+
 // PBS on device buffers (caller holds c->mu and has set the shard's device; workspaces ordered by the
 // caller's ws_begin / ws_end).  Order 0 (P-GATE): BR + SE -> KS; order 1 (P-FHEVM): KS -> [MS noise
 // reduction] -> BR + SE.
+// Plain PBS (m null): the blind rotation extracts its one sample itself, d_out: B x (io_dim + 1).
+// Many-LUT PBS (m, checked by check_many): the rotation writes the shard's accumulator workspace and
+// sample_extract_many.hip takes the samples at degrees f * stride, f < n_fn, timed with the rotation in slot 0;
+// order 0 then keyswitches the n_fn * B rows.  d_out: B x n_fn x (io_dim + 1), ciphertext-major.
 int pbs_device(tfhe_ctx* c, shard& s, const u64* d_in, size_t B, const u64* d_luts, size_t n_lut, const u32* d_idx,
-               u64* d_out, hipStream_t st) {
+               const many_args* m, u64* d_out, hipStream_t st) {
   const size_t big = (size_t)c->p.k * c->p.N + 1, small = (size_t)c->p.n + 1;
-  RC_TRY(grow(s, (void**)&s.d_big, &s.big_cap, B * (c->p.order == 0 ? big : small) * sizeof(u64)));
-  if (c->p.order == 0) {
-    timed_begin(c, s, 0, st);
-    HIP_TRY(launch_br(c, s, d_in, B, d_luts, d_idx, n_lut, s.d_big, nullptr, st));
-    timed_end(c, s, 0, st);
-    timed_begin(c, s, 1, st);
-    RC_TRY(launch_ks(c, s, s.d_big, B, d_out, st));
-    timed_end(c, s, 1, st);
-  } else {
-    timed_begin(c, s, 1, st);
-    RC_TRY(launch_ks(c, s, d_in, B, s.d_big, st));
-    timed_end(c, s, 1, st);
-    if (c->ms_count) {
-      timed_begin(c, s, 2, st);
-      HIP_TRY(launch_ms(c, s, s.d_big, B, nullptr, st));
-      timed_end(c, s, 2, st);
-    }
-    timed_begin(c, s, 0, st);
-    HIP_TRY(launch_br(c, s, s.d_big, B, d_luts, d_idx, n_lut, d_out, nullptr, st));
-    timed_end(c, s, 0, st);
-  }
-  return 0;
-}
-
-// Many-LUT PBS on device buffers (same contract as pbs_device): one blind rotation per input into the shard's
-// accumulator workspace, then the samples at degrees f * stride, f < n_fn (sample_extract_many.hip), timed with
-// the rotation in slot 0.  Order 1 writes them to d_out directly; order 0 keyswitches the n_fn * B rows.
-// d_out: B x n_fn x (io_dim + 1), ciphertext-major.
-int pbs_many_device(tfhe_ctx* c, shard& s, const u64* d_in, size_t B, const u64* d_luts, size_t n_lut, const u32* d_idx,
-                    int n_fn, int stride, u64* d_out, hipStream_t st) {
-  const size_t big = (size_t)c->p.k * c->p.N + 1, small = (size_t)c->p.n + 1;
-  const size_t acc_len = (size_t)(c->p.k + 1) * c->p.N, rows = B * (size_t)n_fn;
+  const size_t rows = B * (m ? m->n_fn : 1);
   RC_TRY(grow(s, (void**)&s.d_big, &s.big_cap, (c->p.order == 0 ? rows * big : B * small) * sizeof(u64)));
-  RC_TRY(grow(s, (void**)&s.d_acc, &s.acc_cap, B * acc_len * sizeof(u64)));
-  const bool zp = !is_fft(c->p);
-  if (c->p.order == 0) {
+  if (m) RC_TRY(grow(s, (void**)&s.d_acc, &s.acc_cap, B * (size_t)(c->p.k + 1) * c->p.N * sizeof(u64)));
+  auto rotate = [&](const u64* in, u64* out) -> int {  // blind rotation + sample extraction, slot 0
     timed_begin(c, s, 0, st);
-    HIP_TRY(launch_br(c, s, d_in, B, d_luts, d_idx, n_lut, nullptr, s.d_acc, st));
-    HIP_TRY(tfhe::launch_sample_extract_many(s.d_acc, B, (int)c->p.k, (int)c->p.N, zp, n_fn, stride, s.d_big, st));
+    if (m) {
+      HIP_TRY(launch_br(c, s, in, B, d_luts, d_idx, n_lut, nullptr, s.d_acc, st));
+      HIP_TRY(tfhe::launch_sample_extract_many(s.d_acc, B, (int)c->p.k, (int)c->p.N, !is_fft(c->p), (int)m->n_fn,
+                                               (int)m->stride, out, st));
+    } else {
+      HIP_TRY(launch_br(c, s, in, B, d_luts, d_idx, n_lut, out, nullptr, st));
+    }
     timed_end(c, s, 0, st);
+    return 0;
+  };
+  if (c->p.order == 0) {
+    RC_TRY(rotate(d_in, s.d_big));
     timed_begin(c, s, 1, st);
     RC_TRY(launch_ks(c, s, s.d_big, rows, d_out, st));
     timed_end(c, s, 1, st);
@@ -339,10 +282,7 @@ int pbs_many_device(tfhe_ctx* c, shard& s, const u64* d_in, size_t B, const u64*
       HIP_TRY(launch_ms(c, s, s.d_big, B, nullptr, st));
       timed_end(c, s, 2, st);
     }
-    timed_begin(c, s, 0, st);
-    HIP_TRY(launch_br(c, s, s.d_big, B, d_luts, d_idx, n_lut, nullptr, s.d_acc, st));
-    HIP_TRY(tfhe::launch_sample_extract_many(s.d_acc, B, (int)c->p.k, (int)c->p.N, zp, n_fn, stride, d_out, st));
-    timed_end(c, s, 0, st);
+    RC_TRY(rotate(s.d_big, d_out));
   }
   return 0;
 }
@@ -357,10 +297,11 @@ int check_many(const tfhe_ctx* c, const char* what, size_t B, uint32_t n_fn, uin
   return 0;
 }
 
+using staged_in = std::initializer_list<std::pair<const void*, size_t>>;  // (host pointer or null, bytes)
+
 // Stage host buffers into the shard's staging allocation (on the shard stream).  Returns device pointers
 // in order, plus one for `extra_out_bytes` of output.
-int stage(shard& s, std::initializer_list<std::pair<const void*, size_t>> in, std::vector<void*>& dptr,
-          size_t extra_out_bytes) {
+int stage(shard& s, staged_in in, std::vector<void*>& dptr, size_t extra_out_bytes) {
   size_t total = 0;
   std::vector<size_t> off;
   for (auto& x : in) {
@@ -379,6 +320,36 @@ int stage(shard& s, std::initializer_list<std::pair<const void*, size_t>> in, st
   }
   dptr.push_back((char*)s.d_stage + out_off);
   return 0;
+}
+
+struct copy_back {  // after the launch: host dst (skipped when null) <- staged pointer d[src], bytes
+  void* dst;
+  size_t src, bytes;
+};
+
+// One host-buffer call on a shard's own stream (caller holds c->mu and has set the shard's device): order the
+// workspaces after their previous user, stage `in` plus out_bytes of output, launch(s, d) on the staged pointers,
+// copy `back` to the host, mark the workspaces used and wait.
+template <class F>
+int staged_run(shard& s, staged_in in, size_t out_bytes, std::initializer_list<copy_back> back, F&& launch) {
+  RC_TRY(ws_begin(s, s.stream));
+  std::vector<void*> d;
+  RC_TRY(stage(s, in, d, out_bytes));
+  RC_TRY(launch(s, d));
+  for (auto& b : back)
+    if (b.dst) HIP_TRY(hipMemcpyAsync(b.dst, d[b.src], b.bytes, hipMemcpyDeviceToHost, s.stream));
+  RC_TRY(ws_end(s, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  return 0;
+}
+
+// The single-shard host entry points: staged_run on shard 0 under the engine lock.
+template <class F>
+int staged_call(tfhe_ctx* c, staged_in in, size_t out_bytes, std::initializer_list<copy_back> back, F&& launch) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  shard& s = c->sh[0];
+  DeviceGuard g(s.device);
+  return staged_run(s, in, out_bytes, back, launch);
 }
 
 // Host -> device copy through a pinned staging ring (2 x 16 MB): the CPU fills one slot while the DMA
@@ -415,21 +386,22 @@ int upload_pinned(shard& s, void* dst, const void* src, size_t bytes) {
   return rc;
 }
 
-bool devices_distinct(const tfhe_ctx* c) {
-  for (size_t i = 0; i < c->sh.size(); i++)
-    for (size_t j = i + 1; j < c->sh.size(); j++)
-      if (c->sh[i].device == c->sh[j].device) return false;
+bool ordinals_distinct(const int* devices, int ndev) {
+  for (int i = 0; i < ndev; i++)
+    for (int j = i + 1; j < ndev; j++)
+      if (devices[i] == devices[j]) return false;
   return true;
 }
 
-// Broadcast planner (tfhe_hip_bcast_plan): which replication the key load takes and the per-rank call list.
+// Broadcast planner (tfhe_hip_bcast_plan): which replication the key load takes and the per-rank call list
+// (`distinct`: ordinals_distinct of the ndev device ordinals).
 //   policy "rccl": RCCL even for one device (the plumbing test); "copy": device / peer copies; NULL or "" = auto:
 //   RCCL when the ordinals are distinct and librccl loads, device / peer copies otherwise (a repeated ordinal, or
 //   no RCCL: hipMemcpyPeerAsync reaches every xGMI peer without it).
 //   mode 2: calls[i] = rank i's ncclBroadcast inside ONE ncclGroupStart / ncclGroupEnd, root 0 (sends in place)
 //   first, every rank on its own communicator member and stream; mode 1: calls[i - 1] = destination shard i of
 //   copy i from shard 0; mode 0: nothing to do.  Returns the call count or a negative error.
-int bcast_plan(const int* devices, int ndev, const char* policy, bool rccl_ok, int* mode, int* calls, int max_calls,
+int bcast_plan(int ndev, bool distinct, const char* policy, bool rccl_ok, int* mode, int* calls, int max_calls,
                std::string* why) {
   const bool forced = policy && strcmp(policy, "rccl") == 0;
   const bool copy = policy && strcmp(policy, "copy") == 0;
@@ -437,10 +409,6 @@ int bcast_plan(const int* devices, int ndev, const char* policy, bool rccl_ok, i
     if (why) *why = std::string("unknown broadcast policy '") + policy + "' (rccl | copy)";
     return TFHE_HIP_EINVAL;
   }
-  bool distinct = true;
-  for (int i = 0; i < ndev; i++)
-    for (int j = i + 1; j < ndev; j++)
-      if (devices[i] == devices[j]) distinct = false;
   *mode = 0;
   if (ndev < 2 && !forced) return 0;
   if (forced) {
@@ -470,15 +438,13 @@ int broadcast(tfhe_ctx* c, const u64* src, const std::vector<u64*>& dst, size_t 
   const char* env = getenv("TFHE_HIP_BCAST");
   std::vector<int> devs(nd), calls(nd);
   for (int i = 0; i < nd; i++) devs[i] = c->sh[i].device;
-  bool distinct = true;
-  for (int i = 0; i < nd; i++)
-    for (int j = i + 1; j < nd; j++) distinct = distinct && devs[i] != devs[j];
+  const bool distinct = ordinals_distinct(devs.data(), nd);
   // librccl is only probed when the plan could use it
   const bool want = (env && strcmp(env, "rccl") == 0) || (nd > 1 && distinct && !(env && strcmp(env, "copy") == 0));
   Rccl* R = want ? &rccl() : nullptr;
   int mode = 0;
   std::string why;
-  const int ncalls = bcast_plan(devs.data(), nd, env, R && R->ok, &mode, calls.data(), nd, &why);
+  const int ncalls = bcast_plan(nd, distinct, env, R && R->ok, &mode, calls.data(), nd, &why);
   if (ncalls < 0)
     return fail(ncalls, "key broadcast: %s%s%s", why.c_str(), R && !R->ok ? ": " : "", R && !R->ok ? R->why.c_str() : "");
   if (mode == 2) {
@@ -620,6 +586,65 @@ int for_each_slice(tfhe_ctx* c, size_t B, F&& fn) {
   return 0;
 }
 
+// argument checks shared by the four PBS entry points (`what`: the message prefix); B == 0 passes
+int pbs_check(const tfhe_ctx* c, const char* what, const void* in, size_t B, const void* luts, size_t n_lut,
+              const many_args* m, const void* out) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "%s: null ctx", what);
+  if (!c->keys) return fail(TFHE_HIP_ENOKEYS, "%s: keys not loaded", what);
+  if (m) RC_TRY(check_many(c, what, B, m->n_fn, m->stride));
+  if (B == 0) return 0;
+  if (!in || !luts || !n_lut || !out) return fail(TFHE_HIP_EINVAL, "%s: null buffer or n_lut == 0", what);
+  if (B > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "%s: batch too large", what);
+  return 0;
+}
+
+// tfhe_hip_pbs_async / tfhe_hip_pbs_many_async: device buffers, on the shard whose device holds the input
+int pbs_async_call(tfhe_ctx* c, const char* what, const u64* d_in, size_t B, const u64* d_luts, size_t n_lut,
+                   const u32* d_idx, const many_args* m, u64* d_out, void* stream) {
+  RC_TRY(pbs_check(c, what, d_in, B, d_luts, n_lut, m, d_out));
+  if (B == 0) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  size_t si = 0;
+  if (c->sh.size() > 1) {
+    hipPointerAttribute_t a;
+    HIP_TRY(hipPointerGetAttributes(&a, d_in));
+    si = c->sh.size();
+    for (size_t i = 0; i < c->sh.size() && si == c->sh.size(); i++)
+      if (c->sh[i].device == a.device) si = i;
+    if (si == c->sh.size()) return fail(TFHE_HIP_EINVAL, "%s_async: input on device %d, no shard there", what, a.device);
+  }
+  shard& s = c->sh[si];
+  DeviceGuard g(s.device);
+  hipStream_t st = resolve_stream(stream, s.stream);
+  RC_TRY(ws_begin(s, st));
+  RC_TRY(pbs_device(c, s, d_in, B, d_luts, n_lut, d_idx, m, d_out, st));
+  return ws_end(s, st);
+}
+
+// tfhe_hip_pbs / tfhe_hip_pbs_many: host buffers, sliced over the shards
+int pbs_host_call(tfhe_ctx* c, const char* what, const u64* lwe_in, size_t B, const u64* luts, size_t n_lut,
+                  const u32* lut_index, const many_args* m, u64* lwe_out) {
+  RC_TRY(pbs_check(c, what, lwe_in, B, luts, n_lut, m, lwe_out));
+  if (B == 0) return 0;
+  if (lut_index)
+    for (size_t q = 0; q < B; q++)
+      if (lut_index[q] >= n_lut)
+        return fail(TFHE_HIP_EINVAL, "%s: lut_index[%zu] = %u >= n_lut %zu", what, q, lut_index[q], n_lut);
+  std::lock_guard<std::mutex> lk(c->mu);
+  const size_t dim = io_dim(c->p) + 1, out_dim = (m ? m->n_fn : 1) * dim;
+  return for_each_slice(c, B, [&](size_t i, size_t lo, size_t hi) -> int {
+    const size_t b = hi - lo;
+    return staged_run(c->sh[i],
+                      {{lwe_in + lo * dim, b * dim * 8}, {luts, n_lut * c->p.N * 8},
+                       {lut_index ? lut_index + lo : nullptr, lut_index ? b * 4 : 0}},
+                      b * out_dim * 8, {{lwe_out + lo * out_dim, 3, b * out_dim * 8}},
+                      [&](shard& s, std::vector<void*>& d) {
+                        return pbs_device(c, s, (const u64*)d[0], b, (const u64*)d[1], n_lut, (const u32*)d[2], m,
+                                          (u64*)d[3], s.stream);
+                      });
+  });
+}
+
 }  // namespace
 
 
@@ -668,12 +693,6 @@ int tfhe_hip_rng_key_entropy(tfhe_rng_key* out) {
 int tfhe_hip_rng_key_from_seed(uint64_t seed, tfhe_rng_key* out) {
   if (!out) return fail(TFHE_HIP_EINVAL, "rng_key_from_seed: null out");
   *out = tfhe::client::rng_key_from_seed(seed);
-  return 0;
-}
-
-static int check_binary(const uint64_t* key, size_t len, const char* what) {
-  for (size_t i = 0; i < len; i++)
-    if (key[i] > 1) return fail(TFHE_HIP_EINVAL, "%s[%zu] is not binary", what, i);
   return 0;
 }
 
@@ -874,8 +893,8 @@ int tfhe_hip_bcast_plan(const int* devices, int ndev, const char* policy, int rc
                         int max_calls) {
   if (!devices || ndev < 1 || !mode || (max_calls > 0 && !calls)) return fail(TFHE_HIP_EINVAL, "bcast_plan: bad arguments");
   std::string why;
-  const int n = bcast_plan(devices, ndev, policy, rccl_available != 0, mode, max_calls > 0 ? calls : nullptr, max_calls,
-                           &why);
+  const int n = bcast_plan(ndev, ordinals_distinct(devices, ndev), policy, rccl_available != 0, mode,
+                           max_calls > 0 ? calls : nullptr, max_calls, &why);
   return n < 0 ? fail(n, "bcast_plan: %s", why.c_str()) : n;
 }
 
@@ -983,127 +1002,34 @@ int tfhe_hip_ms_reduce(tfhe_ctx* c, const uint64_t* in, size_t B, uint64_t* out,
   if (c->p.order != 1) return fail(TFHE_HIP_EUNSUPPORTED, "ms_reduce: KS -> PBS parameter sets only");
   if (B == 0) return 0;
   if (B > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "ms_reduce: batch too large");
-  std::lock_guard<std::mutex> lk(c->mu);
-  shard& s = c->sh[0];
-  DeviceGuard g(s.device);
-  const size_t small = (size_t)c->p.n + 1;
-  RC_TRY(ws_begin(s, s.stream));
-  std::vector<void*> d;
-  RC_TRY(stage(s, {{in, B * small * 8}}, d, B * 4));
-  HIP_TRY(launch_ms(c, s, (u64*)d[0], B, (int*)d[1], s.stream));
-  HIP_TRY(hipMemcpyAsync(out, d[0], B * small * 8, hipMemcpyDeviceToHost, s.stream));
-  if (picks) HIP_TRY(hipMemcpyAsync(picks, d[1], B * 4, hipMemcpyDeviceToHost, s.stream));
-  RC_TRY(ws_end(s, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  return 0;
+  const size_t bytes = B * ((size_t)c->p.n + 1) * 8;
+  return staged_call(c, {{in, bytes}}, B * 4, {{out, 0, bytes}, {picks, 1, B * 4}},
+                     [&](shard& s, std::vector<void*>& d) -> int {
+                       HIP_TRY(launch_ms(c, s, (u64*)d[0], B, (int*)d[1], s.stream));
+                       return 0;
+                     });
 }
 
 int tfhe_hip_pbs_async(tfhe_ctx* c, const uint64_t* d_in, size_t B, const uint64_t* d_luts, size_t n_lut,
                        const uint32_t* d_idx, uint64_t* d_out, void* stream) {
-  if (!c) return fail(TFHE_HIP_EINVAL, "pbs: null ctx");
-  if (!c->keys) return fail(TFHE_HIP_ENOKEYS, "pbs: keys not loaded");
-  if (B == 0) return 0;
-  if (!d_in || !d_luts || !n_lut || !d_out) return fail(TFHE_HIP_EINVAL, "pbs: null buffer or n_lut == 0");
-  if (B > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "pbs: batch too large");
-  std::lock_guard<std::mutex> lk(c->mu);
-  size_t si = 0;
-  if (c->sh.size() > 1) {  // the shard whose device holds the input
-    hipPointerAttribute_t a;
-    HIP_TRY(hipPointerGetAttributes(&a, d_in));
-    si = c->sh.size();
-    for (size_t i = 0; i < c->sh.size() && si == c->sh.size(); i++)
-      if (c->sh[i].device == a.device) si = i;
-    if (si == c->sh.size()) return fail(TFHE_HIP_EINVAL, "pbs_async: input on device %d, no shard there", a.device);
-  }
-  shard& s = c->sh[si];
-  DeviceGuard g(s.device);
-  hipStream_t st = stream == TFHE_HIP_NULL_STREAM ? (hipStream_t)0 : stream ? (hipStream_t)stream : s.stream;
-  RC_TRY(ws_begin(s, st));
-  RC_TRY(pbs_device(c, s, d_in, B, d_luts, n_lut, d_idx, d_out, st));
-  return ws_end(s, st);
+  return pbs_async_call(c, "pbs", d_in, B, d_luts, n_lut, d_idx, nullptr, d_out, stream);
 }
 
 int tfhe_hip_pbs(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,
                  const uint32_t* lut_index, uint64_t* lwe_out) {
-  if (!c) return fail(TFHE_HIP_EINVAL, "pbs: null ctx");
-  if (!c->keys) return fail(TFHE_HIP_ENOKEYS, "pbs: keys not loaded");
-  if (B == 0) return 0;
-  if (!lwe_in || !luts || !n_lut || !lwe_out) return fail(TFHE_HIP_EINVAL, "pbs: null buffer or n_lut == 0");
-  if (B > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "pbs: batch too large");
-  if (lut_index)
-    for (size_t q = 0; q < B; q++)
-      if (lut_index[q] >= n_lut) return fail(TFHE_HIP_EINVAL, "pbs: lut_index[%zu] = %u >= n_lut %zu", q, lut_index[q], n_lut);
-  std::lock_guard<std::mutex> lk(c->mu);
-  const size_t dim = io_dim(c->p) + 1;
-  return for_each_slice(c, B, [&](size_t i, size_t lo, size_t hi) -> int {
-    shard& s = c->sh[i];
-    const size_t b = hi - lo;
-    RC_TRY(ws_begin(s, s.stream));
-    std::vector<void*> d;
-    RC_TRY(stage(s, {{lwe_in + lo * dim, b * dim * 8}, {luts, n_lut * c->p.N * 8},
-                     {lut_index ? lut_index + lo : nullptr, lut_index ? b * 4 : 0}},
-                 d, b * dim * 8));
-    RC_TRY(pbs_device(c, s, (const u64*)d[0], b, (const u64*)d[1], n_lut, (const u32*)d[2], (u64*)d[3], s.stream));
-    HIP_TRY(hipMemcpyAsync(lwe_out + lo * dim, d[3], b * dim * 8, hipMemcpyDeviceToHost, s.stream));
-    RC_TRY(ws_end(s, s.stream));
-    HIP_TRY(hipStreamSynchronize(s.stream));
-    return 0;
-  });
+  return pbs_host_call(c, "pbs", lwe_in, B, luts, n_lut, lut_index, nullptr, lwe_out);
 }
 
 int tfhe_hip_pbs_many_async(tfhe_ctx* c, const uint64_t* d_in, size_t B, const uint64_t* d_luts, size_t n_lut,
                             const uint32_t* d_idx, uint32_t n_fn, uint32_t stride, uint64_t* d_out, void* stream) {
-  if (!c) return fail(TFHE_HIP_EINVAL, "pbs_many: null ctx");
-  if (!c->keys) return fail(TFHE_HIP_ENOKEYS, "pbs_many: keys not loaded");
-  RC_TRY(check_many(c, "pbs_many", B, n_fn, stride));
-  if (B == 0) return 0;
-  if (!d_in || !d_luts || !n_lut || !d_out) return fail(TFHE_HIP_EINVAL, "pbs_many: null buffer or n_lut == 0");
-  std::lock_guard<std::mutex> lk(c->mu);
-  size_t si = 0;
-  if (c->sh.size() > 1) {  // the shard whose device holds the input
-    hipPointerAttribute_t a;
-    HIP_TRY(hipPointerGetAttributes(&a, d_in));
-    si = c->sh.size();
-    for (size_t i = 0; i < c->sh.size() && si == c->sh.size(); i++)
-      if (c->sh[i].device == a.device) si = i;
-    if (si == c->sh.size()) return fail(TFHE_HIP_EINVAL, "pbs_many_async: input on device %d, no shard there", a.device);
-  }
-  shard& s = c->sh[si];
-  DeviceGuard g(s.device);
-  hipStream_t st = stream == TFHE_HIP_NULL_STREAM ? (hipStream_t)0 : stream ? (hipStream_t)stream : s.stream;
-  RC_TRY(ws_begin(s, st));
-  RC_TRY(pbs_many_device(c, s, d_in, B, d_luts, n_lut, d_idx, (int)n_fn, (int)stride, d_out, st));
-  return ws_end(s, st);
+  const many_args m{n_fn, stride};
+  return pbs_async_call(c, "pbs_many", d_in, B, d_luts, n_lut, d_idx, &m, d_out, stream);
 }
 
 int tfhe_hip_pbs_many(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,
                       const uint32_t* lut_index, uint32_t n_fn, uint32_t stride, uint64_t* lwe_out) {
-  if (!c) return fail(TFHE_HIP_EINVAL, "pbs_many: null ctx");
-  if (!c->keys) return fail(TFHE_HIP_ENOKEYS, "pbs_many: keys not loaded");
-  RC_TRY(check_many(c, "pbs_many", B, n_fn, stride));
-  if (B == 0) return 0;
-  if (!lwe_in || !luts || !n_lut || !lwe_out) return fail(TFHE_HIP_EINVAL, "pbs_many: null buffer or n_lut == 0");
-  if (lut_index)
-    for (size_t q = 0; q < B; q++)
-      if (lut_index[q] >= n_lut)
-        return fail(TFHE_HIP_EINVAL, "pbs_many: lut_index[%zu] = %u >= n_lut %zu", q, lut_index[q], n_lut);
-  std::lock_guard<std::mutex> lk(c->mu);
-  const size_t dim = io_dim(c->p) + 1;
-  return for_each_slice(c, B, [&](size_t i, size_t lo, size_t hi) -> int {
-    shard& s = c->sh[i];
-    const size_t b = hi - lo, out_words = b * n_fn * dim;
-    RC_TRY(ws_begin(s, s.stream));
-    std::vector<void*> d;
-    RC_TRY(stage(s, {{lwe_in + lo * dim, b * dim * 8}, {luts, n_lut * c->p.N * 8},
-                     {lut_index ? lut_index + lo : nullptr, lut_index ? b * 4 : 0}},
-                 d, out_words * 8));
-    RC_TRY(pbs_many_device(c, s, (const u64*)d[0], b, (const u64*)d[1], n_lut, (const u32*)d[2], (int)n_fn, (int)stride,
-                           (u64*)d[3], s.stream));
-    HIP_TRY(hipMemcpyAsync(lwe_out + lo * n_fn * dim, d[3], out_words * 8, hipMemcpyDeviceToHost, s.stream));
-    RC_TRY(ws_end(s, s.stream));
-    HIP_TRY(hipStreamSynchronize(s.stream));
-    return 0;
-  });
+  const many_args m{n_fn, stride};
+  return pbs_host_call(c, "pbs_many", lwe_in, B, luts, n_lut, lut_index, &m, lwe_out);
 }
 
 int tfhe_hip_blind_rotate(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,
@@ -1115,40 +1041,29 @@ int tfhe_hip_blind_rotate(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const u
   if (lut_index)
     for (size_t q = 0; q < B; q++)
       if (lut_index[q] >= n_lut) return fail(TFHE_HIP_EINVAL, "blind_rotate: lut_index[%zu] >= n_lut", q);
-  std::lock_guard<std::mutex> lk(c->mu);
-  shard& s = c->sh[0];
-  DeviceGuard g(s.device);
-  const size_t din = (size_t)c->p.n + 1, acc_len = (size_t)(c->p.k + 1) * c->p.N;
-  RC_TRY(ws_begin(s, s.stream));
-  std::vector<void*> d;
-  RC_TRY(stage(s, {{lwe_in, B * din * 8}, {luts, n_lut * c->p.N * 8}, {lut_index, lut_index ? B * 4 : 0}}, d,
-               B * acc_len * 8));
-  HIP_TRY(launch_br(c, s, (const u64*)d[0], B, (const u64*)d[1], (const u32*)d[2], n_lut, nullptr, (u64*)d[3], s.stream));
-  HIP_TRY(hipMemcpyAsync(acc_out, d[3], B * acc_len * 8, hipMemcpyDeviceToHost, s.stream));
-  RC_TRY(ws_end(s, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  return 0;
+  const size_t din = (size_t)c->p.n + 1, acc_bytes = B * (size_t)(c->p.k + 1) * c->p.N * 8;
+  return staged_call(c, {{lwe_in, B * din * 8}, {luts, n_lut * c->p.N * 8}, {lut_index, lut_index ? B * 4 : 0}},
+                     acc_bytes, {{acc_out, 3, acc_bytes}}, [&](shard& s, std::vector<void*>& d) -> int {
+                       HIP_TRY(launch_br(c, s, (const u64*)d[0], B, (const u64*)d[1], (const u32*)d[2], n_lut, nullptr,
+                                         (u64*)d[3], s.stream));
+                       return 0;
+                     });
 }
 
 int tfhe_hip_sample_extract(tfhe_ctx* c, const uint64_t* acc, size_t B, uint64_t* out) {
   if (!c || (B && (!acc || !out))) return fail(TFHE_HIP_EINVAL, "sample_extract: bad arguments");
   if (B == 0) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  shard& s = c->sh[0];
-  DeviceGuard g(s.device);
   const size_t acc_len = (size_t)(c->p.k + 1) * c->p.N, big = (size_t)c->p.k * c->p.N + 1;
-  RC_TRY(ws_begin(s, s.stream));
-  std::vector<void*> d;
-  RC_TRY(stage(s, {{acc, B * acc_len * 8}}, d, B * big * 8));
-  if (is_fft(c->p) && c->p.N == 2048)
-    HIP_TRY(tfhe::launch_sample_extract_torus2k((const u64*)d[0], B, (u64*)d[1], s.stream));
-  else if (is_fft(c->p)) HIP_TRY(tfhe::launch_sample_extract_torus((const u64*)d[0], B, (u64*)d[1], s.stream));
-  else if (c->p.N == 2048) HIP_TRY(tfhe::launch_sample_extract_2048((const u64*)d[0], B, (u64*)d[1], s.stream));
-  else HIP_TRY(tfhe::launch_sample_extract((const u64*)d[0], B, (u64*)d[1], s.stream));
-  HIP_TRY(hipMemcpyAsync(out, d[1], B * big * 8, hipMemcpyDeviceToHost, s.stream));
-  RC_TRY(ws_end(s, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  return 0;
+  return staged_call(c, {{acc, B * acc_len * 8}}, B * big * 8, {{out, 1, B * big * 8}},
+                     [&](shard& s, std::vector<void*>& d) -> int {
+                       const u64* in = (const u64*)d[0];
+                       if (is_fft(c->p) && c->p.N == 2048)
+                         HIP_TRY(tfhe::launch_sample_extract_torus2k(in, B, (u64*)d[1], s.stream));
+                       else if (is_fft(c->p)) HIP_TRY(tfhe::launch_sample_extract_torus(in, B, (u64*)d[1], s.stream));
+                       else if (c->p.N == 2048) HIP_TRY(tfhe::launch_sample_extract_2048(in, B, (u64*)d[1], s.stream));
+                       else HIP_TRY(tfhe::launch_sample_extract(in, B, (u64*)d[1], s.stream));
+                       return 0;
+                     });
 }
 
 int tfhe_hip_sample_extract_many(tfhe_ctx* c, const uint64_t* acc, size_t B, uint32_t n_fn, uint32_t stride,
@@ -1156,37 +1071,25 @@ int tfhe_hip_sample_extract_many(tfhe_ctx* c, const uint64_t* acc, size_t B, uin
   if (!c || (B && (!acc || !out))) return fail(TFHE_HIP_EINVAL, "sample_extract_many: bad arguments");
   RC_TRY(check_many(c, "sample_extract_many", B, n_fn, stride));
   if (B == 0) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  shard& s = c->sh[0];
-  DeviceGuard g(s.device);
-  const size_t acc_len = (size_t)(c->p.k + 1) * c->p.N, big = (size_t)c->p.k * c->p.N + 1;
-  RC_TRY(ws_begin(s, s.stream));
-  std::vector<void*> d;
-  RC_TRY(stage(s, {{acc, B * acc_len * 8}}, d, B * n_fn * big * 8));
-  HIP_TRY(tfhe::launch_sample_extract_many((const u64*)d[0], B, (int)c->p.k, (int)c->p.N, !is_fft(c->p), (int)n_fn,
-                                           (int)stride, (u64*)d[1], s.stream));
-  HIP_TRY(hipMemcpyAsync(out, d[1], B * n_fn * big * 8, hipMemcpyDeviceToHost, s.stream));
-  RC_TRY(ws_end(s, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  return 0;
+  const size_t acc_len = (size_t)(c->p.k + 1) * c->p.N, out_bytes = B * n_fn * ((size_t)c->p.k * c->p.N + 1) * 8;
+  return staged_call(c, {{acc, B * acc_len * 8}}, out_bytes, {{out, 1, out_bytes}},
+                     [&](shard& s, std::vector<void*>& d) -> int {
+                       HIP_TRY(tfhe::launch_sample_extract_many((const u64*)d[0], B, (int)c->p.k, (int)c->p.N,
+                                                                !is_fft(c->p), (int)n_fn, (int)stride, (u64*)d[1],
+                                                                s.stream));
+                       return 0;
+                     });
 }
 
 int tfhe_hip_keyswitch(tfhe_ctx* c, const uint64_t* in, size_t B, uint64_t* out) {
   if (!c || (B && (!in || !out))) return fail(TFHE_HIP_EINVAL, "keyswitch: bad arguments");
   if (!c->keys) return fail(TFHE_HIP_ENOKEYS, "keyswitch: keys not loaded");
   if (B == 0) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  shard& s = c->sh[0];
-  DeviceGuard g(s.device);
   const size_t big = (size_t)c->p.k * c->p.N + 1, small = (size_t)c->p.n + 1;
-  RC_TRY(ws_begin(s, s.stream));
-  std::vector<void*> d;
-  RC_TRY(stage(s, {{in, B * big * 8}}, d, B * small * 8));
-  RC_TRY(launch_ks(c, s, (const u64*)d[0], B, (u64*)d[1], s.stream));
-  HIP_TRY(hipMemcpyAsync(out, d[1], B * small * 8, hipMemcpyDeviceToHost, s.stream));
-  RC_TRY(ws_end(s, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  return 0;
+  return staged_call(c, {{in, B * big * 8}}, B * small * 8, {{out, 1, B * small * 8}},
+                     [&](shard& s, std::vector<void*>& d) {
+                       return launch_ks(c, s, (const u64*)d[0], B, (u64*)d[1], s.stream);
+                     });
 }
 
 static int ntt_impl(tfhe_ctx* c, uint64_t* polys, size_t count, bool inverse) {
@@ -1195,24 +1098,17 @@ static int ntt_impl(tfhe_ctx* c, uint64_t* polys, size_t count, bool inverse) {
   if (count == 0) return 0;
   for (size_t i = 0; i < count * c->p.N; i++)
     if (polys[i] >= tfhe::GL_P) return fail(TFHE_HIP_EINVAL, "ntt: value at %zu not reduced mod p", i);
-  std::lock_guard<std::mutex> lk(c->mu);
-  shard& s = c->sh[0];
-  DeviceGuard g(s.device);
   const size_t bytes = count * c->p.N * 8;
-  RC_TRY(ws_begin(s, s.stream));
-  std::vector<void*> d;
-  RC_TRY(stage(s, {{polys, bytes}}, d, 0));
-  if (c->p.N == 2048) {
-    if (inverse) HIP_TRY(tfhe::launch_ntt2048_inv((u64*)d[0], count, s.d_tw, c->ninv, s.stream));
-    else HIP_TRY(tfhe::launch_ntt2048_fwd((u64*)d[0], count, s.d_tw, s.stream));
-  } else {
-    if (inverse) HIP_TRY(tfhe::launch_ntt_inv((u64*)d[0], count, s.d_tw, c->ninv, s.stream));
-    else HIP_TRY(tfhe::launch_ntt_fwd((u64*)d[0], count, s.d_tw, s.stream));
-  }
-  HIP_TRY(hipMemcpyAsync(polys, d[0], bytes, hipMemcpyDeviceToHost, s.stream));
-  RC_TRY(ws_end(s, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  return 0;
+  return staged_call(c, {{polys, bytes}}, 0, {{polys, 0, bytes}}, [&](shard& s, std::vector<void*>& d) -> int {
+    if (c->p.N == 2048) {
+      if (inverse) HIP_TRY(tfhe::launch_ntt2048_inv((u64*)d[0], count, s.d_tw, c->ninv, s.stream));
+      else HIP_TRY(tfhe::launch_ntt2048_fwd((u64*)d[0], count, s.d_tw, s.stream));
+    } else {
+      if (inverse) HIP_TRY(tfhe::launch_ntt_inv((u64*)d[0], count, s.d_tw, c->ninv, s.stream));
+      else HIP_TRY(tfhe::launch_ntt_fwd((u64*)d[0], count, s.d_tw, s.stream));
+    }
+    return 0;
+  });
 }
 
 int tfhe_hip_ntt_fwd(tfhe_ctx* c, uint64_t* polys, size_t count) { return ntt_impl(c, polys, count, false); }
@@ -1222,25 +1118,18 @@ static int fft_impl(tfhe_ctx* c, const void* in, size_t count, double* out, bool
   if (!c || (count && (!in || !out))) return fail(TFHE_HIP_EINVAL, "fft: bad arguments");
   if (!is_fft(c->p)) return fail(TFHE_HIP_EUNSUPPORTED, "fft: ctx transform is not FFT64");
   if (count == 0) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  shard& s = c->sh[0];
-  DeviceGuard g(s.device);
   const size_t bytes = count * c->p.N * 8;
-  RC_TRY(ws_begin(s, s.stream));
-  std::vector<void*> d;
-  RC_TRY(stage(s, {{in, bytes}}, d, bytes));
-  const double* tw = (const double*)s.d_tw;
-  if (!inverse) {
-    if (c->p.N == 2048) HIP_TRY(tfhe::launch_fft2k_fwd((const u64*)d[0], count, (double*)d[1], tw, s.stream));
-    else HIP_TRY(tfhe::launch_fft_fwd((const u64*)d[0], count, (double*)d[1], tw, s.stream));
-  } else {
-    if (c->p.N == 2048) HIP_TRY(tfhe::launch_fft2k_inv((const double*)d[0], count, (double*)d[1], tw, s.stream));
-    else HIP_TRY(tfhe::launch_fft_inv((const double*)d[0], count, (double*)d[1], tw, s.stream));
-  }
-  HIP_TRY(hipMemcpyAsync(out, d[1], bytes, hipMemcpyDeviceToHost, s.stream));
-  RC_TRY(ws_end(s, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  return 0;
+  return staged_call(c, {{in, bytes}}, bytes, {{out, 1, bytes}}, [&](shard& s, std::vector<void*>& d) -> int {
+    const double* tw = (const double*)s.d_tw;
+    if (!inverse) {
+      if (c->p.N == 2048) HIP_TRY(tfhe::launch_fft2k_fwd((const u64*)d[0], count, (double*)d[1], tw, s.stream));
+      else HIP_TRY(tfhe::launch_fft_fwd((const u64*)d[0], count, (double*)d[1], tw, s.stream));
+    } else {
+      if (c->p.N == 2048) HIP_TRY(tfhe::launch_fft2k_inv((const double*)d[0], count, (double*)d[1], tw, s.stream));
+      else HIP_TRY(tfhe::launch_fft_inv((const double*)d[0], count, (double*)d[1], tw, s.stream));
+    }
+    return 0;
+  });
 }
 
 int tfhe_hip_fft_fwd(tfhe_ctx* c, const uint64_t* polys, size_t count, double* out) {

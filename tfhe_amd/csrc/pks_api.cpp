@@ -1,9 +1,7 @@
 // pks_api.cpp — C ABI of the packing keyswitch / compression (include/tfhe_hip.h, tfhe_hip_pks_*):
 // key residency, workspace, chunked launches.  Kernels: pks.hip; host key material: client.cpp.
 #include <hip/hip_runtime_api.h>
-#include <stdarg.h>
 #include <stdlib.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -12,32 +10,13 @@
 
 #include "../../include/tfhe_hip.h"
 #include "client.h"
+#include "host_common.h"
 #include "pbs_kernels.h"
 
 using tfhe::u32;
 using tfhe::u64;
 
-// shared error slot of the library (api.cpp)
-int tfhe_hip_set_error(int code, const char* msg);
-
 namespace {
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return tfhe_hip_set_error(code, buf);
-}
-
-#define PKS_TRY(expr)                                                                                    \
-  do {                                                                                                   \
-    hipError_t _e = (expr);                                                                              \
-    if (_e != hipSuccess)                                                                                \
-      return fail(_e == hipErrorOutOfMemory ? TFHE_HIP_ENOMEM : TFHE_HIP_EDEVICE, "%s: %s (%s:%d)", #expr, \
-                  hipGetErrorString(_e), __FILE__, __LINE__);                                            \
-  } while (0)
 
 bool pks_valid(const tfhe_pks_params* pp) {
   return pp && pp->in_dim > 0 && pp->in_dim % 16 == 0 && pp->out_k > 0 && pp->out_N >= 32 &&
@@ -46,18 +25,6 @@ bool pks_valid(const tfhe_pks_params* pp) {
          pp->lwe_per_glwe <= pp->out_N && pp->storage_log > 0 && pp->storage_log < 64 && pp->noise_log2 < 0 &&
          pp->noise_log2 > -64;
 }
-
-struct DevGuard {
-  int prev = -1;
-  explicit DevGuard(int d) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != d) (void)hipSetDevice(d);
-  }
-  ~DevGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
 
 constexpr size_t PKS_T_BUDGET = 512ull << 20;  // T workspace per chunk of groups
 
@@ -95,13 +62,13 @@ int ensure_rows(tfhe_pks_ctx* c, size_t rows) {
   c->rows_cap = 0;
   const size_t K = (size_t)c->pp.in_dim * c->pp.level, Nc = (size_t)(c->pp.out_k + 1) * c->pp.out_N;
   if (c->valu) {
-    PKS_TRY(hipMalloc(&c->d_A, rows * K * sizeof(u32)));
+    HIP_TRY(hipMalloc(&c->d_A, rows * K * sizeof(u32)));
   } else {
     const size_t r = tfhe::pks_mfma_rows(rows);
-    PKS_TRY(hipMalloc(&c->d_A0, r * K));
-    PKS_TRY(hipMalloc(&c->d_A1, r * K));
+    HIP_TRY(hipMalloc(&c->d_A0, r * K));
+    HIP_TRY(hipMalloc(&c->d_A1, r * K));
   }
-  PKS_TRY(hipMalloc(&c->d_T, rows * Nc * sizeof(u64)));
+  HIP_TRY(hipMalloc(&c->d_T, rows * Nc * sizeof(u64)));
   c->rows_cap = rows;
   return 0;
 }
@@ -111,16 +78,15 @@ int pack_device(tfhe_pks_ctx* c, const u64* d_lwes, size_t count, u64* d_out, hi
   const size_t Nc = (size_t)(p.out_k + 1) * p.out_N, lpg = p.lwe_per_glwe;
   const size_t groups_per_chunk = std::max<size_t>(1, PKS_T_BUDGET / (lpg * Nc * 8));
   const size_t rows = std::min(count, groups_per_chunk * lpg);
-  int rc = ensure_rows(c, rows);
-  if (rc) return rc;
+  RC_TRY(ensure_rows(c, rows));
   for (size_t first = 0; first < count; first += rows) {
     const size_t n = std::min(rows, count - first);
     if (c->valu)
-      PKS_TRY(tfhe::launch_pks_pack(d_lwes + first * (p.in_dim + 1), n, (int)p.in_dim, (int)p.base_log, (int)p.level,
+      HIP_TRY(tfhe::launch_pks_pack(d_lwes + first * (p.in_dim + 1), n, (int)p.in_dim, (int)p.base_log, (int)p.level,
                                     (int)p.out_k, (int)p.out_N, (int)lpg, c->d_pksk, c->d_corr, c->d_A, c->d_T,
                                     d_out + (first / lpg) * Nc, s));
     else
-      PKS_TRY(tfhe::launch_pks_pack_mfma(d_lwes + first * (p.in_dim + 1), n, (int)p.in_dim, (int)p.base_log,
+      HIP_TRY(tfhe::launch_pks_pack_mfma(d_lwes + first * (p.in_dim + 1), n, (int)p.in_dim, (int)p.base_log,
                                          (int)p.level, (int)p.out_k, (int)p.out_N, (int)lpg, c->d_planes, c->d_A0,
                                          c->d_A1, c->d_T, d_out + (first / lpg) * Nc, s));
   }
@@ -143,8 +109,7 @@ size_t tfhe_hip_pksk_len(const tfhe_pks_params* pp) { return pp ? tfhe::client::
 int tfhe_hip_pks_keygen_k(const tfhe_pks_params* pp, const tfhe_rng_key* rk, const uint64_t* in_key,
                           uint64_t* out_key, uint64_t* pksk) {
   if (!pks_valid(pp) || !rk || !in_key || !out_key) return fail(TFHE_HIP_EINVAL, "pks_keygen: bad arguments");
-  for (uint32_t j = 0; j < pp->in_dim; j++)
-    if (in_key[j] > 1) return fail(TFHE_HIP_EINVAL, "pks_keygen: in_key[%u] is not binary", j);
+  RC_TRY(check_binary(in_key, pp->in_dim, "pks_keygen: in_key"));
   tfhe::client::pks_keygen(*pp, *rk, in_key, out_key, pksk);
   return 0;
 }
@@ -160,9 +125,9 @@ int tfhe_hip_pks_create(const tfhe_pks_params* pp, int device, tfhe_pks_ctx** ou
   *out = nullptr;
   if (!pks_valid(pp)) return fail(TFHE_HIP_EINVAL, "pks_create: invalid parameters");
   int ndev = 0;
-  PKS_TRY(hipGetDeviceCount(&ndev));
+  HIP_TRY(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(TFHE_HIP_EINVAL, "pks_create: device %d of %d", device, ndev);
-  DevGuard g(device);
+  DeviceGuard g(device);
   tfhe_pks_ctx* c = new tfhe_pks_ctx();
   c->pp = *pp;
   c->device = device;
@@ -182,7 +147,7 @@ int tfhe_hip_pks_create(const tfhe_pks_params* pp, int device, tfhe_pks_ctx** ou
 void tfhe_hip_pks_destroy(tfhe_pks_ctx* c) {
   if (!c) return;
   {
-    DevGuard g(c->device);
+    DeviceGuard g(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)hipFree(c->d_pksk);
     (void)hipFree(c->d_corr);
@@ -202,20 +167,20 @@ int tfhe_hip_pks_load_key(tfhe_pks_ctx* c, const uint64_t* pksk, size_t len) {
   if (len != tfhe::client::pksk_len(c->pp))
     return fail(TFHE_HIP_EINVAL, "pks_load_key: length %zu, expected %zu", len, tfhe::client::pksk_len(c->pp));
   std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard g(c->device);
+  DeviceGuard g(c->device);
   c->key = false;
   const size_t Nc = (size_t)(c->pp.out_k + 1) * c->pp.out_N;
-  if (!c->d_pksk) PKS_TRY(hipMalloc(&c->d_pksk, len * 8));
-  if (!c->d_corr) PKS_TRY(hipMalloc(&c->d_corr, Nc * 8));
-  PKS_TRY(hipMemcpyAsync(c->d_pksk, pksk, len * 8, hipMemcpyHostToDevice, c->stream));
-  PKS_TRY(tfhe::launch_pks_corr(c->d_pksk, (int)(c->pp.in_dim * c->pp.level), (int)Nc, (int)c->pp.base_log, c->d_corr,
+  if (!c->d_pksk) HIP_TRY(hipMalloc(&c->d_pksk, len * 8));
+  if (!c->d_corr) HIP_TRY(hipMalloc(&c->d_corr, Nc * 8));
+  HIP_TRY(hipMemcpyAsync(c->d_pksk, pksk, len * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(tfhe::launch_pks_corr(c->d_pksk, (int)(c->pp.in_dim * c->pp.level), (int)Nc, (int)c->pp.base_log, c->d_corr,
                                 c->stream));
   if (!c->valu) {  // balanced byte planes of the key (ks_mfma.hip's recoding, Nc columns)
     if (!c->d_planes)
-      PKS_TRY(hipMalloc(&c->d_planes, tfhe::ks_planes_bytes((int)c->pp.in_dim, (int)c->pp.level, (int)Nc - 1)));
-    PKS_TRY(tfhe::launch_ksk_planes(c->d_pksk, (int)c->pp.in_dim, (int)c->pp.level, (int)Nc - 1, c->d_planes, c->stream));
+      HIP_TRY(hipMalloc(&c->d_planes, tfhe::ks_planes_bytes((int)c->pp.in_dim, (int)c->pp.level, (int)Nc - 1)));
+    HIP_TRY(tfhe::launch_ksk_planes(c->d_pksk, (int)c->pp.in_dim, (int)c->pp.level, (int)Nc - 1, c->d_planes, c->stream));
   }
-  PKS_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   c->key = true;
   return 0;
 }
@@ -226,8 +191,8 @@ int tfhe_hip_pks_pack_async(tfhe_pks_ctx* c, const uint64_t* d_lwes, size_t coun
   if (count == 0) return 0;
   if (!d_lwes || !d_glwes) return fail(TFHE_HIP_EINVAL, "pks_pack: null buffer");
   std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard g(c->device);
-  return pack_device(c, d_lwes, count, d_glwes, stream == TFHE_HIP_NULL_STREAM ? (hipStream_t)0 : stream ? (hipStream_t)stream : c->stream);
+  DeviceGuard g(c->device);
+  return pack_device(c, d_lwes, count, d_glwes, resolve_stream(stream, c->stream));
 }
 
 int tfhe_hip_pks_pack(tfhe_pks_ctx* c, const uint64_t* lwes, size_t count, uint64_t* glwes) {
@@ -237,24 +202,17 @@ int tfhe_hip_pks_pack(tfhe_pks_ctx* c, const uint64_t* lwes, size_t count, uint6
   if (!lwes || !glwes) return fail(TFHE_HIP_EINVAL, "pks_pack: null buffer");
   if (count > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "pks_pack: too many ciphertexts");
   std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard g(c->device);
+  DeviceGuard g(c->device);
   const tfhe_pks_params& p = c->pp;
   const size_t in_bytes = count * (p.in_dim + 1) * 8, groups = (count + p.lwe_per_glwe - 1) / p.lwe_per_glwe;
   const size_t out_bytes = groups * (p.out_k + 1) * p.out_N * 8, in_off = (out_bytes + 255) & ~(size_t)255;
-  if (c->io_cap < in_off + in_bytes) {
-    (void)hipFree(c->d_io);
-    c->d_io = nullptr;
-    c->io_cap = 0;
-    PKS_TRY(hipMalloc(&c->d_io, in_off + in_bytes));
-    c->io_cap = in_off + in_bytes;
-  }
+  RC_TRY(grow_device_buffer((void**)&c->d_io, &c->io_cap, in_off + in_bytes));
   u64* d_out = c->d_io;
   u64* d_in = (u64*)((char*)c->d_io + in_off);
-  PKS_TRY(hipMemcpyAsync(d_in, lwes, in_bytes, hipMemcpyHostToDevice, c->stream));
-  int rc = pack_device(c, d_in, count, d_out, c->stream);
-  if (rc) return rc;
-  PKS_TRY(hipMemcpyAsync(glwes, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  PKS_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpyAsync(d_in, lwes, in_bytes, hipMemcpyHostToDevice, c->stream));
+  RC_TRY(pack_device(c, d_in, count, d_out, c->stream));
+  HIP_TRY(hipMemcpyAsync(glwes, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
 

@@ -1,8 +1,6 @@
 // sns_api.cpp — C ABI of noise squashing (include/tfhe_hip.h, tfhe_hip_sns_*): key residency,
 // workspaces, chunked launches.  Kernels: sns.hip; host key material: client.cpp.
 #include <hip/hip_runtime_api.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -12,48 +10,18 @@
 
 #include "../../include/tfhe_hip.h"
 #include "client.h"
+#include "host_common.h"
 #include "pbs_kernels.h"
 
 using tfhe::u64;
 
-int tfhe_hip_set_error(int code, const char* msg);
-
 namespace {
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return tfhe_hip_set_error(code, buf);
-}
-
-#define SNS_TRY(expr)                                                                                    \
-  do {                                                                                                   \
-    hipError_t _e = (expr);                                                                              \
-    if (_e != hipSuccess)                                                                                \
-      return fail(_e == hipErrorOutOfMemory ? TFHE_HIP_ENOMEM : TFHE_HIP_EDEVICE, "%s: %s (%s:%d)", #expr, \
-                  hipGetErrorString(_e), __FILE__, __LINE__);                                            \
-  } while (0)
 
 // the device kernels of this build: k = 2, N = 2048, 2^24 x 3 (any n), words over Z_2^128
 bool sns_valid(const tfhe_sns_params* sp) {
   return sp && sp->n > 0 && sp->k == 2 && sp->N == 2048 && sp->base_log == 24 && sp->level == 3 &&
          sp->noise_log2 < 0 && sp->noise_log2 > -64;
 }
-
-struct DevGuard {
-  int prev = -1;
-  explicit DevGuard(int d) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != d) (void)hipSetDevice(d);
-  }
-  ~DevGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
 
 // ciphertexts per pass (acc 96 KB + digit spectra 147 KB + MAC products 246 KB each); TFHE_HIP_SNS_CHUNK overrides.
 // 512 since round 6: a 1024 batch as two 512 chunks measured 4,819 vs 4,556 squashes/s (256: 4,455) on one box
@@ -99,9 +67,9 @@ int ensure_ws(tfhe_sns_ctx* c, size_t B) {
   c->d_D = c->d_O = nullptr;
   c->ws_cap = 0;
   const size_t poly = 2 * (size_t)c->sp.N;
-  SNS_TRY(hipMalloc(&c->d_acc, B * (c->sp.k + 1) * poly * 8));
-  SNS_TRY(hipMalloc(&c->d_D, tfhe::sns_digit_len(B) * 16));
-  SNS_TRY(hipMalloc(&c->d_O, tfhe::sns_fft_prod_len(B) * 16));
+  HIP_TRY(hipMalloc(&c->d_acc, B * (c->sp.k + 1) * poly * 8));
+  HIP_TRY(hipMalloc(&c->d_D, tfhe::sns_digit_len(B) * 16));
+  HIP_TRY(hipMalloc(&c->d_O, tfhe::sns_fft_prod_len(B) * 16));
   c->ws_cap = B;
   return 0;
 }
@@ -110,8 +78,8 @@ int ensure_lut(tfhe_sns_ctx* c, uint32_t mm) {
   if (c->d_lut && c->lut_mm == mm) return 0;
   std::vector<u64> lut(2 * (size_t)c->sp.N);
   tfhe::client::sns_lut_identity(c->sp, mm, lut.data());
-  if (!c->d_lut) SNS_TRY(hipMalloc(&c->d_lut, lut.size() * 8));
-  SNS_TRY(hipMemcpy(c->d_lut, lut.data(), lut.size() * 8, hipMemcpyHostToDevice));
+  if (!c->d_lut) HIP_TRY(hipMalloc(&c->d_lut, lut.size() * 8));
+  HIP_TRY(hipMemcpy(c->d_lut, lut.data(), lut.size() * 8, hipMemcpyHostToDevice));
   c->lut_mm = mm;
   return 0;
 }
@@ -119,17 +87,16 @@ int ensure_lut(tfhe_sns_ctx* c, uint32_t mm) {
 // squash (out != null) or blind rotate only (acc_out != null) of B device ciphertexts
 int run_device(tfhe_sns_ctx* c, const u64* d_in, size_t B, u64* d_out, u64* d_acc_out, hipStream_t s) {
   const size_t chunk = std::min(B, sns_chunk());
-  int rc = ensure_ws(c, chunk);
-  if (rc) return rc;
+  RC_TRY(ensure_ws(c, chunk));
   const size_t in_dim = c->sp.n + 1, out_dim = 2 * ((size_t)c->sp.k * c->sp.N + 1);
   const size_t acc_len = (size_t)(c->sp.k + 1) * 2 * c->sp.N;
   for (size_t f = 0; f < B; f += chunk) {
     const size_t nb = std::min(chunk, B - f);
-    SNS_TRY(tfhe::launch_sns_blind_rotate(d_in + f * in_dim, nb, (int)c->sp.n, c->d_lut, c->d_bskf, c->d_acc, c->d_D,
+    HIP_TRY(tfhe::launch_sns_blind_rotate(d_in + f * in_dim, nb, (int)c->sp.n, c->d_lut, c->d_bskf, c->d_acc, c->d_D,
                                           c->d_O, c->d_fconst, s));
-    if (d_out) SNS_TRY(tfhe::launch_sns_extract(c->d_acc, nb, d_out + f * out_dim, s));
+    if (d_out) HIP_TRY(tfhe::launch_sns_extract(c->d_acc, nb, d_out + f * out_dim, s));
     if (d_acc_out)
-      SNS_TRY(hipMemcpyAsync(d_acc_out + f * acc_len, c->d_acc, nb * acc_len * 8, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(hipMemcpyAsync(d_acc_out + f * acc_len, c->d_acc, nb * acc_len * 8, hipMemcpyDeviceToDevice, s));
   }
   return 0;
 }
@@ -140,26 +107,18 @@ int host_call(tfhe_sns_ctx* c, const u64* in, size_t B, uint32_t mm, u64* out, b
   if (B == 0) return 0;
   if (!in || !out || !mm || mm > c->sp.N || (c->sp.N % mm)) return fail(TFHE_HIP_EINVAL, "sns: bad arguments");
   std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard g(c->device);
-  int rc = ensure_lut(c, mm);
-  if (rc) return rc;
+  DeviceGuard g(c->device);
+  RC_TRY(ensure_lut(c, mm));
   const size_t in_bytes = B * (c->sp.n + 1) * 8;
   const size_t out_bytes = acc_only ? B * (c->sp.k + 1) * 2 * c->sp.N * 8 : B * 2 * ((size_t)c->sp.k * c->sp.N + 1) * 8;
   const size_t off = (out_bytes + 255) & ~(size_t)255;
-  if (c->io_cap < off + in_bytes) {
-    (void)hipFree(c->d_io);
-    c->d_io = nullptr;
-    c->io_cap = 0;
-    SNS_TRY(hipMalloc(&c->d_io, off + in_bytes));
-    c->io_cap = off + in_bytes;
-  }
+  RC_TRY(grow_device_buffer((void**)&c->d_io, &c->io_cap, off + in_bytes));
   u64* d_out = c->d_io;
   u64* d_in = (u64*)((char*)c->d_io + off);
-  SNS_TRY(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream));
-  rc = run_device(c, d_in, B, acc_only ? nullptr : d_out, acc_only ? d_out : nullptr, c->stream);
-  if (rc) return rc;
-  SNS_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  SNS_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream));
+  RC_TRY(run_device(c, d_in, B, acc_only ? nullptr : d_out, acc_only ? d_out : nullptr, c->stream));
+  HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
 
@@ -179,8 +138,7 @@ size_t tfhe_hip_sns_bsk_len(const tfhe_sns_params* sp) { return sp ? tfhe::clien
 int tfhe_hip_sns_keygen_k(const tfhe_sns_params* sp, const tfhe_rng_key* rk, const uint64_t* lwe_key,
                           uint64_t* glwe_key, uint64_t* bsk) {
   if (!sns_valid(sp) || !rk || !lwe_key || !glwe_key) return fail(TFHE_HIP_EINVAL, "sns_keygen: bad arguments");
-  for (uint32_t i = 0; i < sp->n; i++)
-    if (lwe_key[i] > 1) return fail(TFHE_HIP_EINVAL, "sns_keygen: lwe_key[%u] is not binary", i);
+  RC_TRY(check_binary(lwe_key, sp->n, "sns_keygen: lwe_key"));
   tfhe::client::sns_keygen(*sp, *rk, lwe_key, glwe_key, bsk);
   return 0;
 }
@@ -197,9 +155,9 @@ int tfhe_hip_sns_create(const tfhe_sns_params* sp, int device, tfhe_sns_ctx** ou
   if (!sns_valid(sp))
     return fail(TFHE_HIP_EUNSUPPORTED, "sns_create: the device kernels cover k = 2, N = 2048, 2^24 x 3");
   int ndev = 0;
-  SNS_TRY(hipGetDeviceCount(&ndev));
+  HIP_TRY(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(TFHE_HIP_EINVAL, "sns_create: device %d of %d", device, ndev);
-  DevGuard g(device);
+  DeviceGuard g(device);
   tfhe_sns_ctx* c = new tfhe_sns_ctx();
   c->sp = *sp;
   c->device = device;
@@ -218,7 +176,7 @@ int tfhe_hip_sns_create(const tfhe_sns_params* sp, int device, tfhe_sns_ctx** ou
 void tfhe_hip_sns_destroy(tfhe_sns_ctx* c) {
   if (!c) return;
   {
-    DevGuard g(c->device);
+    DeviceGuard g(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (void* p : {c->d_fconst, c->d_bskf, (void*)c->d_acc, c->d_D, c->d_O, (void*)c->d_lut, (void*)c->d_io})
       (void)hipFree(p);
@@ -232,27 +190,21 @@ int tfhe_hip_sns_load_key(tfhe_sns_ctx* c, const uint64_t* bsk, size_t len) {
   if (len != tfhe::client::sns_bsk_len(c->sp))
     return fail(TFHE_HIP_EINVAL, "sns_load_key: length %zu, expected %zu", len, tfhe::client::sns_bsk_len(c->sp));
   std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard g(c->device);
+  DeviceGuard g(c->device);
   c->key = false;
-  if (!c->d_bskf) SNS_TRY(hipMalloc(&c->d_bskf, tfhe::sns_fft_key_len(c->sp.n) * 16));
+  if (!c->d_bskf) HIP_TRY(hipMalloc(&c->d_bskf, tfhe::sns_fft_key_len(c->sp.n) * 16));
   // stage the key words in chunks of polynomials (lo, hi planes) through the io buffer, convert to limb spectra
   const size_t poly_words = 2 * (size_t)c->sp.N, polys = len / poly_words, per = 2048;
   const size_t bytes = per * poly_words * 8;
-  if (c->io_cap < bytes) {
-    (void)hipFree(c->d_io);
-    c->d_io = nullptr;
-    c->io_cap = 0;
-    SNS_TRY(hipMalloc(&c->d_io, bytes));
-    c->io_cap = bytes;
-  }
+  RC_TRY(grow_device_buffer((void**)&c->d_io, &c->io_cap, bytes));
   for (size_t f = 0; f < polys; f += per) {
     const size_t np = std::min(per, polys - f);
-    SNS_TRY(hipMemcpyAsync(c->d_io, bsk + f * poly_words, np * poly_words * 8, hipMemcpyHostToDevice, c->stream));
-    SNS_TRY(tfhe::launch_sns_bsk_to_fft(c->d_io, (char*)c->d_bskf + f * tfhe::SNS_FFT_POLY_BYTES, np, c->d_fconst,
+    HIP_TRY(hipMemcpyAsync(c->d_io, bsk + f * poly_words, np * poly_words * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(tfhe::launch_sns_bsk_to_fft(c->d_io, (char*)c->d_bskf + f * tfhe::SNS_FFT_POLY_BYTES, np, c->d_fconst,
                                         c->stream));
     // the io buffer is reused by the next chunk's copy: same stream, ordered
   }
-  SNS_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   c->key = true;
   return 0;
 }
@@ -272,11 +224,9 @@ int tfhe_hip_sns_squash_async(tfhe_sns_ctx* c, const uint64_t* d_in, size_t B, u
   if (B == 0) return 0;
   if (!d_in || !d_out || !mm || mm > c->sp.N || (c->sp.N % mm)) return fail(TFHE_HIP_EINVAL, "sns: bad arguments");
   std::lock_guard<std::mutex> lk(c->mu);
-  DevGuard g(c->device);
-  int rc = ensure_lut(c, mm);
-  if (rc) return rc;
-  hipStream_t s = stream == TFHE_HIP_NULL_STREAM ? (hipStream_t)0 : stream ? (hipStream_t)stream : c->stream;
-  return run_device(c, d_in, B, d_out, nullptr, s);
+  DeviceGuard g(c->device);
+  RC_TRY(ensure_lut(c, mm));
+  return run_device(c, d_in, B, d_out, nullptr, resolve_stream(stream, c->stream));
 }
 
 int tfhe_hip_sns_phase(const tfhe_sns_params* sp, const uint64_t* glwe_key, const uint64_t* cts, size_t count,
