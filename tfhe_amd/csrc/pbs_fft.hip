@@ -87,8 +87,21 @@ __device__ __forceinline__ int decomp_step(u32& st, u32 bmask) {
 #endif
   return d;
 }
-// the top level (b = 0, no next state): 3 VALU per digit
-__device__ __forceinline__ int decomp_top(u32 st) { return (int)(st - ((st + 63u) & ~127u)); }
+// decomp_state of the complement: for S = ~x the high word is h = ~hi(x), and ~h + 1024 = 1023 - h (mod 2^32)
+__device__ __forceinline__ u32 decomp_state_not(u64 S) { return (1023u - (u32)(S >> 32)) >> 11; }
+// the top level (b = 0, no next state), as a double: 2 integer VALU per digit.  A top state is 0 <= st <= 128, and there
+// st - ((st + 63) & ~127) = -sext7(-st) (every st checked in tests/test_pair_int_forms.py): v_sub_u32, v_bfe_i32, the
+// conversion, and a negation that rides in the source modifiers of the f64 consumers.  (In inline asm: hipcc's known-bits
+// have mis-folded an sbfe builtin in rotate_states below.)  The one difference from (double)(int) is a zero digit, -0.0
+// here: it can change only the sign of exact zeros downstream (mac_first's argument: a sum or an fma with a non-zero
+// term does not see the sign of a zero term, products and sums of zeros stay zeros), and the accumulator update
+// (torus_acc_add_y) takes floor(y), y - floor(y) and the words of both plus non-zero magic numbers, which are the same
+// for y = -0.0 and +0.0
+__device__ __forceinline__ double decomp_top(u32 st) {
+  int t;
+  asm("v_bfe_i32 %0, %1, 0, 7" : "=v"(t) : "v"(0u - st));
+  return -(double)t;
+}
 
 // o = D (.) K as the first term of an fma chain: a multiply where the chain would add to +0 (the oracle's
 // first term; the two differ only in the sign of an exact zero, which no later step can turn into a non-zero)
@@ -299,7 +312,8 @@ typedef __attribute__((address_space(3))) u64 lds_u64;
 // of the lanes L + r >= 64 wraps, negated, to the image start); the reads take (X^(64 A) W)[L + 64 e] = W[L + 64 (e -
 // A)] for e >= A and -W[L + 64 (e - A + 16)] for e < A, so slot e's base (two per-lane bases 8 KB apart) and sign
 // (xor s) depend only on the SGPR comparison e < A.  Per slot 8 VALU instead of 10 (no compare, no negate-and-select:
-// y = (x ^ M) - (v + M), M = 0 or all ones); the values are the same, so no operation order changes.
+// y = (x ^ M) - (v + M), M = 0 or all ones); the values are the same, so no operation order changes.  Since round 8 the
+// difference is taken as the complement of a sum, 7 VALU per slot (below).
 #ifndef FFT_ROT_UNIFORM
 #define FFT_ROT_UNIFORM 1
 #endif
@@ -327,16 +341,21 @@ __device__ __forceinline__ void rotate_states(const u64 (&v)[16], int a, int lan
   // bit e of wmask: slot e reads the wrapped part (e < A); bit e of mbits: slot e negated.  Bit-field extracts of
   // these SGPR words keep every per-slot decision scalar (a compare would be rebuilt as a per-lane select)
   const u32 wmask = (1u << A) - 1u;
-  const u32 mbits = __builtin_amdgcn_readfirstlane(wmask ^ (sgn ? ~0u : 0u));
+  const u64 mbits = (u32)__builtin_amdgcn_readfirstlane(wmask ^ (sgn ? ~0u : 0u));
 #pragma unroll
   for (int e = 0; e < 16; e++) {
-    // s_bfe_i32 (0 or -1) in inline asm: hipcc's known-bits treat the width-1 sbfe builtin as non-negative and drop
-    // the sign extension (a probe kernel stores hi = 0 for it)
-    int m32;
-    asm("s_bfe_i32 %0, %1, %2" : "=s"(m32) : "s"(mbits), "i"(e | (1 << 16)));
-    const u64 M = (u64)(long long)m32;
+    // s_bfe_i64 (0 or all ones, both words in ONE scalar instruction) in inline asm: hipcc's known-bits treat the
+    // width-1 sbfe builtin as non-negative and drop the sign extension (a probe kernel stores hi = 0 for it).  The
+    // scalar instructions of this loop are not free: the form with a separate ~M (an s_bfe_i32 and an s_ashr_i32 for
+    // each mask, 32 more scalar instructions per CMUX) ran 0.16 ms per 4096 SLOWER than the subtracting code it
+    // replaced, this one 0.19 ms faster
+    u64 M;
+    asm("s_bfe_i64 %0, %1, %2" : "=s"(M) : "s"(mbits), "i"(e | (1 << 16)));
     const u64 x = ((const lds_u64*)(uintptr_t)(rb + (__builtin_amdgcn_ubfe(wmask, e, 1) << 13)))[64 * e];
-    st[e] = decomp_state((x ^ M) - (v[e] + M));
+    // (x ^ M) - (v + M) = ~((x ^ ~M) + (v + M)), exact in all 64 bits (-(x ^ ~M) = (x ^ M) + 1): two 64-bit adds (one
+    // v_lshl_add_u64 each) instead of an add and a two-instruction subtract; the complement folds into the state.
+    // x ^ ~M = ~(x ^ M) is one v_xnor_b32 per word
+    st[e] = decomp_state_not(~(x ^ M) + (v[e] + M));
   }
   lds_order();
 #else
@@ -618,8 +637,8 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
 #pragma unroll
       for (int e = 0; e < 8; e++) {
         if constexpr (q == 2) {
-          xr[e] = (double)decomp_top(st[e]);
-          xi[e] = (double)decomp_top(st[e + 8]);
+          xr[e] = decomp_top(st[e]);
+          xi[e] = decomp_top(st[e + 8]);
         } else {
           xr[e] = (double)decomp_step(st[e], 1u);
           xi[e] = (double)decomp_step(st[e + 8], 1u);
@@ -856,8 +875,8 @@ __global__ __launch_bounds__(64 * G3_NW, 1) void blind_rotate_fft_g3_kernel(
 #pragma unroll
         for (int e = 0; e < 8; e++) {
           if constexpr (q == 2) {
-            xr[e] = (double)decomp_top(st[e]);
-            xi[e] = (double)decomp_top(st[e + 8]);
+            xr[e] = decomp_top(st[e]);
+            xi[e] = decomp_top(st[e + 8]);
           } else {
             xr[e] = (double)decomp_step(st[e], 1u);
             xi[e] = (double)decomp_step(st[e + 8], 1u);

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Static ISA stats of the CMUX loop of the P-GATE pair kernel (blind_rotate_fft_pair_kernel<2, false, true>, the
-# instantiation bench.py runs): resources of the kernel, then the f64, LDS and wait counts of the loop body (both
+# instantiation bench.py runs): resources of the kernel, then the f64, non-f64 VALU, scalar, LDS and wait counts of the loop body (both
 # branches of the partial-sum exchange counted).  Compiles with the Makefile's flags for pbs_fft.o; needs no GPU.
 # usage: tools/isa_pair_stats.sh [-k out.s] [extra hipcc flags, e.g. -DFFT_MAC_PIPE=0 ...]
 #   -k out.s: keep the loop body (its line numbers are those of the kernel's listing) for reading
@@ -30,6 +30,7 @@ SPILL=$(grep -A40 "\.name: *$SYM" "$D/k.s" | sed -n 's/.*\.vgpr_spill_count: *\(
 echo "kernel: VGPRs $(num NumVgprs), spilled ${SPILL:-?}, scratch $(num ScratchSize) B, LDS $(num LDSByteSize) B, occupancy $(num Occupancy)"
 echo "CMUX loop: lines $LO-$HI of the kernel's listing"
 echo "  v_add_f64 $(cnt v_add_f64)  v_mul_f64 $(cnt v_mul_f64)  v_fma_f64+v_fmac_f64 $(cnt 'v_fma_f64|v_fmac_f64')  v_floor_f64 $(cnt v_floor_f64)"
+echo "  non-f64 VALU $(grep -E '^\s+v_' "$D/loop.s" | grep -cvE '^\s+v_(add|mul|fma|fmac|floor)_f64(_e32|_e64)?(\s|$)' || true)  (every v_* but the four above)  scalar $(grep -cE '^\s+s_' "$D/loop.s" || true)  (every s_*, waits and s_nop included)"
 echo "  ds_read_b128 $(cnt ds_read_b128)  ds_write_b128 $(cnt ds_write_b128)  ds_read_b64 $(cnt ds_read_b64)  ds_write_b64 $(cnt ds_write_b64)"
 echo "  s_waitcnt $(cnt s_waitcnt)  of which lgkmcnt(0) $(grep -cE '^\s+s_waitcnt.*lgkmcnt\(0\)' "$D/loop.s" || true)  s_barrier $(cnt s_barrier)"
 if [ -n "$KEEP" ]; then cp "$D/loop.s" "$KEEP"; echo "loop body kept in $KEEP"; fi
