@@ -252,16 +252,28 @@ def keyswitch(prm: Params, keys: Keys, lwe_big: np.ndarray) -> np.ndarray:
     return out
 
 
-def ms_measure(prm: Params, keys: Keys, ct: np.ndarray, zero_index=None) -> float:
-    ms = keys.ms_key()
+def ms_key(zeros: np.ndarray, bound: float = MS_FHEVM["bound"], r_sigma: float = MS_FHEVM["r_sigma"],
+           input_variance: float = MS_FHEVM["input_variance"]) -> MsKey:
+    """An explicit noise-reduction key: any rows [count][n+1] as the zeros, any bound."""
+    z = np.ascontiguousarray(zeros, dtype=np.uint64)
+    assert z.ndim == 2 and z.shape[0] > 0
+    k = MsKey(z.ctypes.data, z.shape[0], bound, r_sigma, input_variance)
+    k._keep = z
+    return k
+
+
+def ms_measure(prm: Params, keys: Keys, ct: np.ndarray, zero_index=None, ms: MsKey = None) -> float:
+    """Measure of ct (+ row zero_index of the key's zeros); ms: an explicit key (ms_key) instead of keys.ms_key()."""
+    ms = ms if ms is not None else keys.ms_key()
     ct = np.ascontiguousarray(ct, dtype=np.uint64)
-    z = None if zero_index is None else _p(np.ascontiguousarray(keys.ms_zeros[zero_index]))
+    zeros = ms._keep.reshape(-1, prm.n + 1)
+    z = None if zero_index is None else _p(np.ascontiguousarray(zeros[zero_index]))
     return lib().or_ms_measure(ctypes.byref(prm), ctypes.byref(ms), _p(ct), z)
 
 
-def ms_reduce(prm: Params, keys: Keys, small: np.ndarray):
-    """-> (reduced ciphertexts, chosen zero index per ciphertext or -1)"""
-    ms = keys.ms_key()
+def ms_reduce(prm: Params, keys: Keys, small: np.ndarray, ms: MsKey = None):
+    """-> (reduced ciphertexts, chosen zero index per ciphertext or -1); ms: an explicit key (ms_key)"""
+    ms = ms if ms is not None else keys.ms_key()
     out = np.ascontiguousarray(small, dtype=np.uint64).reshape(-1, prm.n + 1).copy()
     picks = np.array([lib().or_ms_reduce(ctypes.byref(prm), ctypes.byref(ms), _p(out[i])) for i in range(out.shape[0])],
                      dtype=np.int64)

@@ -74,3 +74,47 @@ def test_oracle_pack_decrypts_and_extracts(pks, oracle_mod):
     ph2 = C.glwe_phase(1, 2048, ck.post_packing_key, comp.extract())
     assert np.abs((ph2[:6] - msgs).view(np.int64)).max() < 2 ** 45
     assert comp.nbytes == 8 * -(-(2048 + 6) * 26 // 64)
+
+
+# ---- away from the preset (the device side is tests/test_gpu_pks_params.py) -------------------------------
+def test_glwe_size_off_the_column_tile_is_refused():
+    """(k+1)N = 96 is no multiple of the GEMMs' 64-column tile: keygen and context creation refuse it with
+    EINVAL (the argument check comes before any device call), so no kernel can run past a tile."""
+    import tfhe_amd
+    import test_gpu_pks_params as T
+    pp, _ = T.make_params(*T.REFUSED_FIELDS)
+    assert pp.glwe_len == 96
+    for make in (lambda: C.Packer(pp, 0), lambda: C.CompressionKey(pp, SEED, np.zeros(pp.in_dim, np.uint64))):
+        with pytest.raises(tfhe_amd.TfheError) as e:
+            make()
+        assert e.value.code == -1
+
+
+@pytest.mark.parametrize("fields", [(64, 3, 32, 16, 3, 32), (48, 1, 32, 5, 1, 32)])
+def test_keygen_matches_oracle_small_params(oracle_mod, fields):
+    pp = C.PksParams(*fields, 26, -48)
+    opp = oracle_mod.PksParams(*fields, 26, -48)
+    in_key = np.random.default_rng(6).integers(0, 2, pp.in_dim).astype(np.uint64)
+    ck, ok = C.CompressionKey(pp, SEED, in_key), oracle_mod.PksKeys(opp, SEED, in_key)
+    assert ck.pksk.size == pp.in_dim * pp.level * pp.glwe_len
+    assert np.array_equal(ck.post_packing_key, ok.out_key)
+    assert np.array_equal(ck.pksk, ok.pksk)
+
+
+def test_gpu_sweep_inputs_hold_the_edge_digits():
+    """The inputs of the device parameter sweep contain the digits it is about (+-B/2; at base 2^16 a digit
+    whose high byte would be +128), checked with or_decompose, and each case names the GEMM that the selection
+    rule gives it."""
+    import test_gpu_pks_params as T
+    for name, (_, path) in T.SWEEP.items():
+        pp, _, key, lwes = T.sweep_inputs(name)
+        assert T.expected_path(pp) == path, name
+        T.check_digit_coverage(pp, lwes)
+        assert key.pksk.size == pp.in_dim * pp.level * pp.glwe_len
+
+
+def test_gpu_chunk_case_spans_two_chunks():
+    """The device chunk-loop test packs lwe_per_glwe + 3 LWEs at parameters whose T workspace budget (read from
+    pks_api.cpp) holds one group: two launches."""
+    import test_gpu_pks_params as T
+    T.check_chunk_plan()

@@ -33,7 +33,8 @@ def test_pack_vs_oracle(setup, oracle_mod, count):
 
 
 def test_pack_many_groups_decrypt(setup, oracle_mod):
-    """2 full groups + a partial one in one call (chunked GEMM workspaces); last group bit-exact
+    """2 full groups + a partial one in one call (one chunk: the T budget holds 8 groups at the preset; the
+    chunk loop itself is tests/test_gpu_pks_params.py::test_chunk_loop); last group bit-exact
     with the oracle, every coefficient of every group decrypts to its message."""
     pp, opp, ck, ok, packer = setup
     count = 2 * 2048 + 9

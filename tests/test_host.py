@@ -163,6 +163,18 @@ def test_ms_noise_reduction_rule_oracle(oracle_mod):
     assert np.abs(d).max() < 2 ** 50
 
 
+def test_ms_scan_cases_oracle_picks():
+    """The constructed keys and bounds of tests/test_gpu_ms_scan.py: the oracle alone (or_ms_reduce with an
+    explicit key) yields the pick each case is built for, before anything runs on a device."""
+    import test_gpu_ms_scan as T
+    _, cases = T.check_oracle_picks()
+    names = " ".join(c["name"] for c in cases)
+    for kind in T._kinds():
+        assert kind in names
+    assert {c["zeros"].shape[0] for c in cases} >= set(T.COUNTS)
+    assert {c["cts"].shape[0] for c in cases} == {1, 5, 9}
+
+
 def test_entropy_keygen_and_encryption_are_fresh():
     """no public default seed.  gen_keys / server_keygen / encrypt without a seed draw
     192 bits of OS entropy: two key sets, two server keys for one client key and two encryptions of

@@ -140,8 +140,10 @@ __global__ __launch_bounds__(64 * KM_WAVES) void ks_gemm_kernel(const v4i* __res
 
 // ---------------------------------------------------------------------------------------------
 // Packing keyswitch GEMM on the matrix cores (pks.hip's T = D x PKSK mod 2^64).
-// The digits are tfhe-rs SignedDecomposer digits at base 2^B (B <= 16): two signed bytes each,
-// d = d0 + 2^8 d1 (d0 in [-128, 127], |d1| <= 2^(B-9)), so
+// The digits are tfhe-rs SignedDecomposer digits at base 2^B, -2^(B-1) <= d <= +2^(B-1), as two signed bytes
+// each: d = d0 + 2^8 d1 with d0 in [-128, 127] and |d1| <= 2^(B-9).  d1 must fit a signed byte, +2^(B-9)
+// included, so B <= 15: at B = 16 every digit in 32640..32768 has d1 = +128 (pks_create sends B >= 16 to the
+// VALU GEMM).  Then
 //   sum_k d[k] PKSK[k][n] = sum_t 2^(8t) (D0 x S_t + D1 x S_(t-1))[n]      (mod 2^64, S_-1 = 0)
 // with S_t the key's balanced byte planes (ksk_planes_kernel, the same recoding as the keyswitch).
 // Fifteen int8 GEMMs per (row, column) tile, all exact in int32: |acc| <= K * 2 * 128 * 128 = 2^27 at
@@ -261,7 +263,7 @@ hipError_t launch_pks_gemm_mfma(const u64* lwes, size_t count, int in_dim, int b
                                 const void* planes, void* A0, void* A1, u64* T, hipStream_t s) {
   if (count == 0) return hipSuccess;
   const int K = in_dim * LV;
-  if (K % 64 || Nc % (16 * PM_NT) || base_log < 2 || base_log > 16 || base_log * LV >= 64 ||
+  if (K % 64 || Nc % (16 * PM_NT) || base_log < 2 || base_log > 15 || LV > 8 || base_log * LV >= 64 ||
       (long long)K * 2 * 128 * 128 >= (1ll << 31))
     return hipErrorInvalidValue;
   const size_t rows = pks_mfma_rows(count), el = rows * (size_t)in_dim;

@@ -133,8 +133,9 @@ int tfhe_hip_pks_create(const tfhe_pks_params* pp, int device, tfhe_pks_ctx** ou
   c->device = device;
   {
     const char* e = getenv("TFHE_HIP_PKS_VALU");
-    // the matrix-core GEMM needs int8 digit bytes (base <= 16) and 64-deep k steps
-    c->valu = (e && e[0] == '1') || pp->base_log > 16 || (pp->in_dim * pp->level) % 64 != 0;
+    // the matrix-core GEMM needs two int8 bytes per digit (base <= 2^15: a balanced digit reaches +2^(B-1), and
+    // +2^15 would need a high byte of +128), the key planes' level limit (<= 8) and 64-deep k steps
+    c->valu = (e && e[0] == '1') || pp->base_log > 15 || pp->level > 8 || (pp->in_dim * pp->level) % 64 != 0;
   }
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
     delete c;
