@@ -183,6 +183,14 @@ int tfhe_hip_load_keys(tfhe_ctx* ctx, const uint64_t* bsk, size_t bsk_len, const
 /* Same, from DEVICE buffers on shard 0's device (e.g. after a torch.distributed broadcast of the keys). */
 int tfhe_hip_load_keys_device(tfhe_ctx* ctx, const uint64_t* d_bsk, size_t bsk_len, const uint64_t* d_ksk,
                               size_t ksk_len);
+/* The bootstrapping key alone: upload, broadcast to every shard and convert it as tfhe_hip_load_keys does, with no
+ * keyswitching key (a tfhe-rs DecompressionKey holds none; a dummy KSK at n = 2048, N = 2048 would be 134 MB).
+ * Replaces the key residency behind tfhe-rs DecompressionKey / programmable_bootstrap_lwe_ciphertext.  The ctx
+ * is then "rotation-only": tfhe_hip_blind_rotate, tfhe_hip_bootstrap*, tfhe_hip_decompress* and tfhe_hip_br_kernel
+ * work; every call that keyswitches (tfhe_hip_pbs*, tfhe_hip_nand, tfhe_hip_keyswitch) keeps returning
+ * TFHE_HIP_ENOKEYS until a tfhe_hip_load_keys makes the ctx complete.  _device: d_bsk on shard 0's device. */
+int tfhe_hip_load_bsk(tfhe_ctx* ctx, const uint64_t* bsk, size_t bsk_len);
+int tfhe_hip_load_bsk_device(tfhe_ctx* ctx, const uint64_t* d_bsk, size_t bsk_len);
 
 /* Enable the modulus-switch noise reduction between keyswitch and blind rotation (order 1 only;
  * count = 0 disables).  Before each blind rotation the ciphertext gets the one zero whose
@@ -224,6 +232,16 @@ int tfhe_hip_pbs_many(tfhe_ctx* ctx, const uint64_t* lwe_in, size_t B, const uin
 int tfhe_hip_pbs_many_async(tfhe_ctx* ctx, const uint64_t* d_lwe_in, size_t B, const uint64_t* d_luts, size_t n_lut,
                             const uint32_t* d_lut_index, uint32_t n_fn, uint32_t stride, uint64_t* d_lwe_out,
                             void* stream);
+
+/* Programmable bootstrap WITHOUT a keyswitch: blind rotation + sample extraction of B ciphertexts under the small
+ * (dimension n) key, B x (n+1) in -> B x (kN+1) out under the GLWE key, for either `order`; no modulus-switch noise
+ * reduction.  Replaces tfhe-rs programmable_bootstrap_lwe_ciphertext.  Needs the BSK only (tfhe_hip_load_bsk or
+ * tfhe_hip_load_keys).  Host buffers, synchronous, sharded like tfhe_hip_pbs; timed in slot 0. */
+int tfhe_hip_bootstrap(tfhe_ctx* ctx, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,
+                       const uint32_t* lut_index, uint64_t* lwe_big_out);
+/* The same on device buffers; stream and workspace rules of tfhe_hip_pbs_async. */
+int tfhe_hip_bootstrap_async(tfhe_ctx* ctx, const uint64_t* d_lwe_in, size_t B, const uint64_t* d_luts, size_t n_lut,
+                             const uint32_t* d_lut_index, uint64_t* d_lwe_big_out, void* stream);
 
 /* Stage-level entry points (host buffers) used by the parity tests. */
 /* acc_out: B x (k+1) x N values in the GLWE ring (Z_p for NTT, torus for FFT64) after the CMUX loop. */
@@ -272,7 +290,7 @@ int tfhe_hip_sync(tfhe_ctx* ctx);
 /* Per-kernel device timing (HIP events recorded on the launch stream around every blind-rotate /
  * keyswitch launch).  reset clears the record; stats waits for the recorded events and returns the
  * summed milliseconds and the launch count.  which: 0 = blind rotate (+sample extract), 1 = keyswitch,
- * 2 = modulus-switch noise reduction.
+ * 2 = modulus-switch noise reduction, 3 = unpack / extract of tfhe_hip_decompress.
  * Used by bench.py for the roofline figure. */
 int tfhe_hip_timing_enable(tfhe_ctx* ctx, int enable);
 int tfhe_hip_timing_reset(tfhe_ctx* ctx);
@@ -316,6 +334,36 @@ int tfhe_hip_pks_compress(const tfhe_pks_params* pp, const uint64_t* glwe, uint3
 int tfhe_hip_pks_extract(const tfhe_pks_params* pp, const uint64_t* packed, uint32_t bodies, uint64_t* glwe);
 /* client-side decryption of a native GLWE: body - sum_c mask_c * S_c (N values) */
 int tfhe_hip_glwe_phase(uint32_t k, uint32_t N, const uint64_t* key, const uint64_t* glwe, uint64_t* out);
+
+/* ---- decompression: compressed GLWEs back into compute-ready LWEs -----------------------------
+ * Replaces tfhe-rs CompressedCiphertextList::get / DecompressionKey::unpack (the return half of the reference's
+ * compression surface, ml/extensions/rust/src/compression.rs:134-291): unpack the stored bits, sample-extract
+ * coefficient i, blind-rotate under a key from the post-packing key to the compute GLWE key, sample-extract.
+ * A list of `count` ciphertexts is the concatenation of G = ceil(count / lwe_per_glwe) compressed GLWEs exactly as
+ * tfhe_hip_pks_compress writes them: group g holds lwe_per_glwe bodies (the last one the remainder) and is
+ * tfhe_hip_pks_packed_words(pp, bodies_g) words long; spare high bits of a group's last word are ignored.
+ *
+ * Stage-level (tfhe-rs: unpack + extract_lwe_sample_from_glwe_ciphertext; needs no key): row q = g * lwe_per_glwe
+ * + i of lwes_out (count x (out_k*out_N + 1)) is the LWE of coefficient i of group g under the post-packing key,
+ * stored values moved to the top of the word (<< (64 - storage_log)).  EINVAL if packed_words is not the sum
+ * above; EUNSUPPORTED for out_N > 4096; count == 0 returns OK.  _async: device pointers and a stream, rules of
+ * tfhe_hip_pks_pack_async. */
+int tfhe_hip_pks_unpack_extract(tfhe_pks_ctx* ctx, const uint64_t* packed, size_t packed_words, size_t count,
+                                uint64_t* lwes_out);
+int tfhe_hip_pks_unpack_extract_async(tfhe_pks_ctx* ctx, const uint64_t* d_packed, size_t packed_words, size_t count,
+                                      uint64_t* d_lwes_out, void* stream);
+/* The whole decompression on a ctx whose n = pp->out_k * pp->out_N and whose BSK (tfhe_hip_load_bsk) goes from the
+ * post-packing key to the ctx GLWE key: unpack / extract into a shard workspace (timed in slot 3), then
+ * tfhe_hip_bootstrap (slot 0).  lwe_big_out: count x (kN + 1); lut_index: count entries or null.  EINVAL unless pp
+ * is valid, packed_words fits and pp->out_k * pp->out_N == n; ENOKEYS without a BSK; count <= 0x7FFFFFFF; all checks
+ * run before any device work.  The host form runs on shard 0; a multi-shard caller hands whole groups to the
+ * async form (device buffers on the shard's device; stream and workspace rules of tfhe_hip_pbs_async). */
+int tfhe_hip_decompress(tfhe_ctx* ctx, const tfhe_pks_params* pp, const uint64_t* packed, size_t packed_words,
+                        size_t count, const uint64_t* luts, size_t n_lut, const uint32_t* lut_index,
+                        uint64_t* lwe_big_out);
+int tfhe_hip_decompress_async(tfhe_ctx* ctx, const tfhe_pks_params* pp, const uint64_t* d_packed, size_t packed_words,
+                              size_t count, const uint64_t* d_luts, size_t n_lut, const uint32_t* d_lut_index,
+                              uint64_t* d_lwe_big_out, void* stream);
 
 /* ---- switch-and-squash: noise squashing to a 128-bit LWE ----------------------
  * fhEVM's sns-worker (coprocessor-docker-compose.yml:124-140) turns each 64-bit P-FHEVM ciphertext into

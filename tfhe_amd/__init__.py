@@ -114,7 +114,9 @@ ABI_SYMBOLS = (
     "tfhe_hip_device_at", "tfhe_hip_key_bcast_mode", "tfhe_hip_br_kernel", "tfhe_hip_aes128_block",
     "tfhe_hip_csprng_words", "tfhe_hip_seeded_server_keygen_k", "tfhe_hip_seeded_lwe_list_k", "tfhe_hip_decompress_bsk",
     "tfhe_hip_decompress_ksk", "tfhe_hip_decompress_lwe_list", "tfhe_hip_pbs_many", "tfhe_hip_pbs_many_async",
-    "tfhe_hip_sample_extract_many",
+    "tfhe_hip_sample_extract_many", "tfhe_hip_load_bsk", "tfhe_hip_load_bsk_device", "tfhe_hip_bootstrap",
+    "tfhe_hip_bootstrap_async", "tfhe_hip_pks_unpack_extract", "tfhe_hip_pks_unpack_extract_async",
+    "tfhe_hip_decompress", "tfhe_hip_decompress_async",
 )
 
 # P-FHEVM modulus-switch noise reduction key (include/tfhe_hip.h TFHE_HIP_MS_FHEVM_*)
@@ -186,7 +188,12 @@ def lib():
         L.tfhe_hip_load_keys.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, _U64P, ctypes.c_size_t]
         L.tfhe_hip_load_keys_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                                 ctypes.c_size_t]
+        L.tfhe_hip_load_bsk.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t]
+        L.tfhe_hip_load_bsk_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
         L.tfhe_hip_pbs.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, _U64P, ctypes.c_size_t, _U32P, _U64P]
+        L.tfhe_hip_bootstrap.argtypes = L.tfhe_hip_pbs.argtypes
+        L.tfhe_hip_bootstrap_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                               ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         L.tfhe_hip_fft_fwd.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, ctypes.c_void_p]
         L.tfhe_hip_fft_inv.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         L.tfhe_hip_pbs_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
@@ -486,6 +493,14 @@ class Engine:
             self.load_ms_key(sk.ms_zeros)
         return self
 
+    def load_bsk(self, bsk: np.ndarray) -> "Engine":
+        """The bootstrapping key alone (a decompression key has no keyswitching key).  The engine is then
+        rotation-only: ``blind_rotate``, ``bootstrap*`` and decompression work; ``pbs`` / ``keyswitch`` / ``nand``
+        raise ENOKEYS until ``load_keys``."""
+        b = _c_u64(bsk)
+        _check(lib().tfhe_hip_load_bsk(self._h, _u64(b), b.size))
+        return self
+
     def load_ms_key(self, zeros: Optional[np.ndarray], bound: float = MS_FHEVM["bound"],
                     r_sigma: float = MS_FHEVM["r_sigma"], input_variance: float = MS_FHEVM["input_variance"]):
         """Modulus-switch noise reduction between keyswitch and blind rotation (None: disable)."""
@@ -565,6 +580,37 @@ class Engine:
         d_out = d_in.new_empty(d_in.shape)
         if d_in.shape[0]:
             self.pbs_async(d_in.contiguous(), d_luts, d_out, d_lut_index)
+        return d_out
+
+    def bootstrap(self, cts: np.ndarray, luts: np.ndarray, lut_index=None) -> np.ndarray:
+        """tfhe-rs ``programmable_bootstrap_lwe_ciphertext``, batched over host arrays: blind rotation and sample
+        extraction with no keyswitch, (B, n+1) under the small key -> (B, kN+1) under the GLWE key.  Needs the
+        bootstrapping key only (``load_bsk`` or ``load_keys``)."""
+        p = self.params
+        cts = _c_u64(cts).reshape(-1, p.n + 1)
+        luts = _c_u64(luts).reshape(-1, p.N)
+        li = None
+        if lut_index is not None:
+            li = np.ascontiguousarray(np.asarray(lut_index, dtype=np.uint32))
+            if li.shape[0] != cts.shape[0]:
+                raise ValueError("lut_index must have one entry per ciphertext")
+        out = np.zeros((cts.shape[0], p.k * p.N + 1), dtype=np.uint64)
+        _check(lib().tfhe_hip_bootstrap(self._h, _u64(cts), cts.shape[0], _u64(luts), luts.shape[0],
+                                        li.ctypes.data_as(_U32P) if li is not None else None, _u64(out)))
+        return out
+
+    def bootstrap_async(self, d_in, d_luts, d_out, d_lut_index=None, stream=None) -> None:
+        """Device-resident ``bootstrap`` (torch tensors on this device: d_in (B, n+1), d_out (B, kN+1)), enqueued
+        on ``stream`` like ``pbs_async``."""
+        head, tail = self._pbs_async_args(d_in, d_luts, d_lut_index, d_out, stream)
+        _check(lib().tfhe_hip_bootstrap_async(*head, *tail))
+
+    def bootstrap_device(self, d_in, d_luts, d_lut_index=None):
+        """bootstrap_async into a fresh tensor: (B, n+1) on this device -> (B, kN+1), queued on torch's current
+        stream (no host synchronisation)."""
+        d_out = d_in.new_empty((d_in.shape[0], self.params.k * self.params.N + 1))
+        if d_in.shape[0]:
+            self.bootstrap_async(d_in.contiguous(), d_luts, d_out, d_lut_index)
         return d_out
 
     def pbs_many(self, cts: np.ndarray, luts: np.ndarray, n_fn: int, stride: int, lut_index=None) -> np.ndarray:

@@ -8,6 +8,11 @@ Mirrors the reference's compression surface (ml/extensions/rust/src/compression.
 with the packing keyswitch on the GPU (one integer GEMM + negacyclic shift-sum per chunk of GLWEs)
 and the modulus switch / bit packing on the host.  Parameters: the reference's PARAMS_8B_2048_NEW
 (ml/extensions/rust/src/fhext_classes.rs:98-112).
+
+The return half (tfhe-rs CompressedCiphertextList::get / DecompressionKey::unpack) runs on the GPU:
+  DecompressionKey(compute_params, pks_params, post_packing_key, glwe_key, seed) -> a BSK, no KSK
+  Decompressor(dk).decompress([CompressedGlwe]) -> LWEs under the compute GLWE key
+(unpack + sample extraction: tfhe_amd/csrc/decompress.hip; then a PBS without keyswitch on a BSK-only engine).
 """
 from __future__ import annotations
 
@@ -16,7 +21,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import RngKey, _c_u64, _check, _stream_handle, _u64, lib, rng_key
+from . import Engine, Params, RngKey, _c_u64, _check, _stream_handle, _u64, lib, lut_from_table, rng_key
 
 PKS_PRESET_ML2048 = 0
 _U64P = ctypes.POINTER(ctypes.c_uint64)
@@ -62,6 +67,14 @@ def _lib():
         L.tfhe_hip_pks_compress.argtypes = [P, _U64P, ctypes.c_uint32, _U64P]
         L.tfhe_hip_pks_extract.argtypes = [P, _U64P, ctypes.c_uint32, _U64P]
         L.tfhe_hip_glwe_phase.argtypes = [ctypes.c_uint32, ctypes.c_uint32, _U64P, _U64P, _U64P]
+        L.tfhe_hip_pks_unpack_extract.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, ctypes.c_size_t, _U64P]
+        L.tfhe_hip_pks_unpack_extract_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                        ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+        L.tfhe_hip_decompress.argtypes = [ctypes.c_void_p, P, _U64P, ctypes.c_size_t, ctypes.c_size_t, _U64P,
+                                          ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32), _U64P]
+        L.tfhe_hip_decompress_async.argtypes = [ctypes.c_void_p, P, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p]
         _BOUND = True
     return L
 
@@ -164,6 +177,34 @@ class Packer:
             out.append(compress_glwe(p, glwes[g], bodies))
         return out
 
+    def unpack_extract(self, comp: List[CompressedGlwe]) -> np.ndarray:
+        """Steps 1 and 2 of the decompression on the device (decompress.hip): the list's ciphertexts as LWEs under
+        the post-packing key, (count, k*N + 1); row g * lwe_per_glwe + i is ``extract_lwe(comp[g].extract(), i)``."""
+        packed, count = concat_list(self.params, comp)
+        out = np.zeros((count, self.params.out_k * self.params.out_N + 1), dtype=np.uint64)
+        _check(_lib().tfhe_hip_pks_unpack_extract(self._h, _u64(packed), packed.size, count, _u64(out)))
+        return out
+
+    def unpack_extract_async(self, d_packed, count: int, d_lwes, stream=None) -> None:
+        """The same on torch device tensors (d_packed: the concatenated words, d_lwes: (count, k*N + 1)), enqueued
+        on ``stream`` like ``pack_async``."""
+        _check(_lib().tfhe_hip_pks_unpack_extract_async(self._h, ctypes.c_void_p(d_packed.data_ptr()),
+                                                        d_packed.numel(), count, ctypes.c_void_p(d_lwes.data_ptr()),
+                                                        ctypes.c_void_p(_stream_handle(stream, self.device))))
+
+
+def concat_list(params: PksParams, comp: List[CompressedGlwe]):
+    """The list layout of tfhe_hip_pks_unpack_extract / tfhe_hip_decompress: the groups' packed words back to back,
+    every group but the last full -> (words, count)."""
+    for c in comp[:-1]:
+        if c.bodies != params.lwe_per_glwe:
+            raise ValueError("every compressed GLWE of a list but the last holds lwe_per_glwe ciphertexts")
+    if comp and not 0 < comp[-1].bodies <= params.lwe_per_glwe:
+        raise ValueError("the last compressed GLWE of a list holds 1 .. lwe_per_glwe ciphertexts")
+    if not comp:
+        return np.zeros(0, dtype=np.uint64), 0
+    return np.concatenate([_c_u64(c.packed).reshape(-1) for c in comp]), sum(c.bodies for c in comp)
+
 
 def extract_lwe(params: PksParams, glwe: np.ndarray, index: int) -> np.ndarray:
     """LWE (dim k*N, native q) of coefficient `index` of a GLWE (tfhe-rs extract_lwe_sample_from_glwe_
@@ -181,3 +222,88 @@ def extract_lwe(params: PksParams, glwe: np.ndarray, index: int) -> np.ndarray:
             out[c * N:(c + 1) * N] = val
     out[-1] = g[k][index]
     return out
+
+
+# ---- decompression: compressed GLWEs back into compute-ready LWEs (tfhe-rs DecompressionKey) ------------------
+class DecompressionKey:
+    """Bootstrapping key from the post-packing GLWE key (read as an LWE key of dimension out_k * out_N) to the
+    compute GLWE key; no keyswitching key.  ``params``: the compute parameters with ``n`` replaced by
+    out_k * out_N -- the parameter set of the rotation-only engine.  seed None: OS entropy; an int: the
+    reproducible test stream."""
+
+    def __init__(self, compute_params: Params, pks_params: PksParams, post_packing_key: np.ndarray,
+                 glwe_key: np.ndarray, seed: Optional[int]):
+        self.pks_params, self.seed = pks_params, seed
+        self.params = Params.from_buffer_copy(compute_params)
+        self.params.n = pks_params.out_k * pks_params.out_N
+        lwe, glwe = _c_u64(post_packing_key), _c_u64(glwe_key)
+        if lwe.size != self.params.n or glwe.size != self.params.k * self.params.N:
+            raise ValueError("DecompressionKey: key sizes do not match the parameters")
+        L = lib()
+        self.bsk = np.zeros(L.tfhe_hip_bsk_len(ctypes.byref(self.params)), dtype=np.uint64)
+        rk = rng_key(seed)
+        _check(L.tfhe_hip_server_keygen_k(ctypes.byref(self.params), ctypes.byref(rk), _u64(lwe), _u64(glwe),
+                                          _u64(self.bsk), None))
+
+
+class Decompressor:
+    """tfhe-rs ``CompressedCiphertextList::get`` on one GPU: owns a rotation-only engine holding the decompression
+    key; every ciphertext of a list comes back as an LWE under the compute GLWE key after one PBS."""
+
+    def __init__(self, dk: DecompressionKey, device: int = 0):
+        self.key, self.device = dk, device
+        self.engine = Engine(dk.params, device)
+        try:
+            self.engine.load_bsk(dk.bsk)
+        except Exception:
+            self.engine.close()
+            raise
+
+    def close(self) -> None:
+        self.engine.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def identity_lut(self, msg_modulus: int = 16) -> np.ndarray:
+        """m -> m over msg_modulus values, one padding bit: delta = 2^64 / (2 * msg_modulus)."""
+        return lut_from_table(self.key.params.N, msg_modulus, list(range(msg_modulus)), (1 << 63) // msg_modulus)
+
+    def decompress(self, comp: List[CompressedGlwe], lut: Optional[np.ndarray] = None, msg_modulus: int = 16,
+                   lut_index=None) -> np.ndarray:
+        """A list of compressed GLWEs -> (count, k*N + 1) LWEs under the compute GLWE key.  lut: one table or
+        (n_lut, N) with ``lut_index`` (count entries); None: the identity over ``msg_modulus`` values."""
+        p, pp = self.key.params, self.key.pks_params
+        packed, count = concat_list(pp, comp)
+        luts = _c_u64(self.identity_lut(msg_modulus) if lut is None else lut).reshape(-1, p.N)
+        li = None
+        if lut_index is not None:
+            li = np.ascontiguousarray(np.asarray(lut_index, dtype=np.uint32))
+            if li.shape[0] != count:
+                raise ValueError("lut_index must have one entry per ciphertext")
+        out = np.zeros((count, p.k * p.N + 1), dtype=np.uint64)
+        _check(_lib().tfhe_hip_decompress(self.engine._h, ctypes.byref(pp), _u64(packed), packed.size, count,
+                                          _u64(luts), luts.shape[0],
+                                          li.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if li is not None else None,
+                                          _u64(out)))
+        return out
+
+    def decompress_async(self, d_packed, count: int, d_luts, d_out, d_lut_index=None, stream=None) -> None:
+        """Device tensors (d_packed: the concatenated words of whole groups, d_out: (count, k*N + 1)), enqueued on
+        ``stream`` (None: torch's current stream)."""
+        _check(_lib().tfhe_hip_decompress_async(
+            self.engine._h, ctypes.byref(self.key.pks_params), ctypes.c_void_p(d_packed.data_ptr()), d_packed.numel(),
+            count, ctypes.c_void_p(d_luts.data_ptr()), d_luts.numel() // self.key.params.N,
+            ctypes.c_void_p(d_lut_index.data_ptr()) if d_lut_index is not None else None,
+            ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(_stream_handle(stream, self.device))))
+
+    def decompress_device(self, d_packed, count: int, d_lut, d_lut_index=None):
+        """decompress_async into a fresh (count, k*N + 1) tensor on torch's current stream (no host sync)."""
+        p = self.key.params
+        d_out = d_packed.new_empty((count, p.k * p.N + 1))
+        if count:
+            self.decompress_async(d_packed.contiguous(), count, d_lut, d_out, d_lut_index)
+        return d_out

@@ -101,6 +101,8 @@ Rccl& rccl() {
 
 }  // namespace
 
+constexpr int TIMING_SLOTS = 4;
+
 // One device's slice of an engine.
 struct tfhe_shard {
   int device = 0;
@@ -123,15 +125,17 @@ struct tfhe_shard {
   hipEvent_t ws_free = nullptr;
   hipStream_t ws_last = nullptr;
   bool ws_used = false;
-  // timing: start/stop event pairs per slot (0 = blind rotate, 1 = keyswitch, 2 = MS noise reduction)
-  std::vector<hipEvent_t> ev[3];
+  // timing: start/stop event pairs per slot (0 = blind rotate, 1 = keyswitch, 2 = MS noise reduction,
+  // 3 = unpack / extract of a decompression)
+  std::vector<hipEvent_t> ev[TIMING_SLOTS];
   std::vector<hipEvent_t> ev_pool;
 };
 
 struct tfhe_ctx {
   tfhe_params p{};
   std::vector<tfhe_shard> sh;
-  bool keys = false;
+  bool bsk = false;   // a BSK is resident: the rotation-only calls work (tfhe_hip_load_bsk or tfhe_hip_load_keys)
+  bool keys = false;  // BSK and KSK of one key set: every call works (tfhe_hip_load_keys)
   bool ks_valu = false;  // TFHE_HIP_KS_VALU=1: the VALU keyswitch kernel instead (A/B runs)
   size_t lat_max = 1024; // batches up to this size (per shard) use the latency blind-rotate kernel
   u64 ninv = 0;
@@ -242,6 +246,22 @@ int launch_ks(tfhe_ctx* c, shard& s, const u64* in_big, size_t B, u64* out, hipS
 struct many_args {  // the many-LUT arguments of tfhe_hip_pbs_many*; a null pointer = plain PBS
   uint32_t n_fn, stride;
 };
+
+// what a PBS entry point runs: the parameter set's full PBS (keyswitch and rotation in its `order`, optionally
+// many-LUT), or the rotation alone (tfhe_hip_bootstrap: B x (n+1) -> B x (kN+1), BSK only)
+struct pbs_kind {
+  const many_args* m = nullptr;
+  bool rotation_only = false;
+};
+
+// Blind rotation + extraction of the degree-0 sample, B x (n+1) -> B x (kN+1), timed in slot 0.
+int bootstrap_device(tfhe_ctx* c, shard& s, const u64* d_in, size_t B, const u64* d_luts, size_t n_lut,
+                     const u32* d_idx, u64* d_out, hipStream_t st) {
+  timed_begin(c, s, 0, st);
+  HIP_TRY(launch_br(c, s, d_in, B, d_luts, d_idx, n_lut, d_out, nullptr, st));
+  timed_end(c, s, 0, st);
+  return 0;
+}
 
 // PBS on device buffers (caller holds c->mu and has set the shard's device; workspaces ordered by the
 // caller's ws_begin / ws_end).  Order 0 (P-GATE): BR + SE -> KS; order 1 (P-FHEVM): KS -> [MS noise
@@ -488,12 +508,12 @@ int broadcast(tfhe_ctx* c, const u64* src, const std::vector<u64*>& dst, size_t 
   return 0;
 }
 
-// Convert a standard-domain BSK at `std_bsk` (on the shard's device) to the transform domain and the KSK
-// at s.d_ksk to byte planes.
-int convert_keys(tfhe_ctx* c, shard& s, const u64* std_bsk, size_t bsk_len) {
+// Convert a standard-domain BSK at `std_bsk` (on the shard's device) to the transform domain and, with_ksk, the
+// KSK at s.d_ksk to byte planes.
+int convert_keys(tfhe_ctx* c, shard& s, const u64* std_bsk, size_t bsk_len, bool with_ksk) {
   const size_t polys = bsk_len / c->p.N;
   DeviceGuard g(s.device);
-  if (!c->ks_valu) {
+  if (with_ksk && !c->ks_valu) {
     const int big_dim = (int)(c->p.k * c->p.N);
     if (!s.d_ks_planes)
       HIP_TRY(hipMalloc(&s.d_ks_planes, tfhe::ks_planes_bytes(big_dim, (int)c->p.ks_level, (int)c->p.n)));
@@ -540,7 +560,7 @@ int shard_init(tfhe_ctx* c, shard& s) {
 void shard_free(shard& s) {
   DeviceGuard g(s.device);
   if (s.stream) (void)hipStreamSynchronize(s.stream);
-  for (int w = 0; w < 3; w++)
+  for (int w = 0; w < TIMING_SLOTS; w++)
     for (auto e : s.ev[w]) (void)hipEventDestroy(e);
   for (auto e : s.ev_pool) (void)hipEventDestroy(e);
   (void)hipFree(s.d_bsk);
@@ -586,11 +606,13 @@ int for_each_slice(tfhe_ctx* c, size_t B, F&& fn) {
   return 0;
 }
 
-// argument checks shared by the four PBS entry points (`what`: the message prefix); B == 0 passes
+// argument checks shared by the PBS entry points (`what`: the message prefix); B == 0 passes
 int pbs_check(const tfhe_ctx* c, const char* what, const void* in, size_t B, const void* luts, size_t n_lut,
-              const many_args* m, const void* out) {
+              const pbs_kind& kd, const void* out) {
+  const many_args* m = kd.m;
   if (!c) return fail(TFHE_HIP_EINVAL, "%s: null ctx", what);
-  if (!c->keys) return fail(TFHE_HIP_ENOKEYS, "%s: keys not loaded", what);
+  if (kd.rotation_only ? !c->bsk : !c->keys)
+    return fail(TFHE_HIP_ENOKEYS, "%s: %s not loaded", what, kd.rotation_only ? "bootstrapping key" : "keys");
   if (m) RC_TRY(check_many(c, what, B, m->n_fn, m->stride));
   if (B == 0) return 0;
   if (!in || !luts || !n_lut || !out) return fail(TFHE_HIP_EINVAL, "%s: null buffer or n_lut == 0", what);
@@ -598,40 +620,62 @@ int pbs_check(const tfhe_ctx* c, const char* what, const void* in, size_t B, con
   return 0;
 }
 
-// tfhe_hip_pbs_async / tfhe_hip_pbs_many_async: device buffers, on the shard whose device holds the input
-int pbs_async_call(tfhe_ctx* c, const char* what, const u64* d_in, size_t B, const u64* d_luts, size_t n_lut,
-                   const u32* d_idx, const many_args* m, u64* d_out, void* stream) {
-  RC_TRY(pbs_check(c, what, d_in, B, d_luts, n_lut, m, d_out));
-  if (B == 0) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  size_t si = 0;
-  if (c->sh.size() > 1) {
-    hipPointerAttribute_t a;
-    HIP_TRY(hipPointerGetAttributes(&a, d_in));
-    si = c->sh.size();
-    for (size_t i = 0; i < c->sh.size() && si == c->sh.size(); i++)
-      if (c->sh[i].device == a.device) si = i;
-    if (si == c->sh.size()) return fail(TFHE_HIP_EINVAL, "%s_async: input on device %d, no shard there", what, a.device);
-  }
-  shard& s = c->sh[si];
-  DeviceGuard g(s.device);
-  hipStream_t st = resolve_stream(stream, s.stream);
-  RC_TRY(ws_begin(s, st));
-  RC_TRY(pbs_device(c, s, d_in, B, d_luts, n_lut, d_idx, m, d_out, st));
-  return ws_end(s, st);
+// The shard that runs an *_async call: the first one whose device holds the input (caller holds c->mu).
+int shard_of_input(tfhe_ctx* c, const char* what, const void* d_in, size_t* si) {
+  *si = 0;
+  if (c->sh.size() < 2) return 0;
+  hipPointerAttribute_t a;
+  HIP_TRY(hipPointerGetAttributes(&a, d_in));
+  for (size_t i = 0; i < c->sh.size(); i++)
+    if (c->sh[i].device == a.device) {
+      *si = i;
+      return 0;
+    }
+  return fail(TFHE_HIP_EINVAL, "%s_async: input on device %d, no shard there", what, a.device);
 }
 
-// tfhe_hip_pbs / tfhe_hip_pbs_many: host buffers, sliced over the shards
-int pbs_host_call(tfhe_ctx* c, const char* what, const u64* lwe_in, size_t B, const u64* luts, size_t n_lut,
-                  const u32* lut_index, const many_args* m, u64* lwe_out) {
-  RC_TRY(pbs_check(c, what, lwe_in, B, luts, n_lut, m, lwe_out));
-  if (B == 0) return 0;
+int host_lut_index_check(const char* what, const u32* lut_index, size_t B, size_t n_lut) {
   if (lut_index)
     for (size_t q = 0; q < B; q++)
       if (lut_index[q] >= n_lut)
         return fail(TFHE_HIP_EINVAL, "%s: lut_index[%zu] = %u >= n_lut %zu", what, q, lut_index[q], n_lut);
+  return 0;
+}
+
+// a PBS entry point's work on one shard (pbs_device, or the rotation alone)
+int pbs_kind_device(tfhe_ctx* c, shard& s, const u64* d_in, size_t B, const u64* d_luts, size_t n_lut,
+                    const u32* d_idx, const pbs_kind& kd, u64* d_out, hipStream_t st) {
+  if (kd.rotation_only) return bootstrap_device(c, s, d_in, B, d_luts, n_lut, d_idx, d_out, st);
+  return pbs_device(c, s, d_in, B, d_luts, n_lut, d_idx, kd.m, d_out, st);
+}
+
+// tfhe_hip_pbs_async / tfhe_hip_pbs_many_async / tfhe_hip_bootstrap_async: device buffers, on the shard whose
+// device holds the input
+int pbs_async_call(tfhe_ctx* c, const char* what, const u64* d_in, size_t B, const u64* d_luts, size_t n_lut,
+                   const u32* d_idx, const pbs_kind& kd, u64* d_out, void* stream) {
+  RC_TRY(pbs_check(c, what, d_in, B, d_luts, n_lut, kd, d_out));
+  if (B == 0) return 0;
   std::lock_guard<std::mutex> lk(c->mu);
-  const size_t dim = io_dim(c->p) + 1, out_dim = (m ? m->n_fn : 1) * dim;
+  size_t si = 0;
+  RC_TRY(shard_of_input(c, what, d_in, &si));
+  shard& s = c->sh[si];
+  DeviceGuard g(s.device);
+  hipStream_t st = resolve_stream(stream, s.stream);
+  RC_TRY(ws_begin(s, st));
+  RC_TRY(pbs_kind_device(c, s, d_in, B, d_luts, n_lut, d_idx, kd, d_out, st));
+  return ws_end(s, st);
+}
+
+// tfhe_hip_pbs / tfhe_hip_pbs_many / tfhe_hip_bootstrap: host buffers, sliced over the shards
+int pbs_host_call(tfhe_ctx* c, const char* what, const u64* lwe_in, size_t B, const u64* luts, size_t n_lut,
+                  const u32* lut_index, const pbs_kind& kd, u64* lwe_out) {
+  RC_TRY(pbs_check(c, what, lwe_in, B, luts, n_lut, kd, lwe_out));
+  if (B == 0) return 0;
+  RC_TRY(host_lut_index_check(what, lut_index, B, n_lut));
+  std::lock_guard<std::mutex> lk(c->mu);
+  const size_t io = io_dim(c->p) + 1;
+  const size_t dim = kd.rotation_only ? (size_t)c->p.n + 1 : io;
+  const size_t out_dim = kd.rotation_only ? (size_t)c->p.k * c->p.N + 1 : (kd.m ? kd.m->n_fn : 1) * io;
   return for_each_slice(c, B, [&](size_t i, size_t lo, size_t hi) -> int {
     const size_t b = hi - lo;
     return staged_run(c->sh[i],
@@ -639,10 +683,36 @@ int pbs_host_call(tfhe_ctx* c, const char* what, const u64* lwe_in, size_t B, co
                        {lut_index ? lut_index + lo : nullptr, lut_index ? b * 4 : 0}},
                       b * out_dim * 8, {{lwe_out + lo * out_dim, 3, b * out_dim * 8}},
                       [&](shard& s, std::vector<void*>& d) {
-                        return pbs_device(c, s, (const u64*)d[0], b, (const u64*)d[1], n_lut, (const u32*)d[2], m,
-                                          (u64*)d[3], s.stream);
+                        return pbs_kind_device(c, s, (const u64*)d[0], b, (const u64*)d[1], n_lut, (const u32*)d[2],
+                                               kd, (u64*)d[3], s.stream);
                       });
   });
+}
+
+// tfhe_hip_decompress*: every check that precedes device work.  The list checks need no ctx, so they come first.
+int decompress_check(const tfhe_ctx* c, const tfhe_pks_params* pp, const void* packed, size_t packed_words,
+                     size_t count, const void* luts, size_t n_lut, const void* out) {
+  RC_TRY(tfhe_hip_pks_list_check(pp, packed_words, count, "decompress"));
+  if (!c) return fail(TFHE_HIP_EINVAL, "decompress: null ctx");
+  if ((uint64_t)pp->out_k * pp->out_N != c->p.n)
+    return fail(TFHE_HIP_EINVAL, "decompress: out_k * out_N = %llu, the ctx rotates ciphertexts of dimension n = %u",
+                (unsigned long long)pp->out_k * pp->out_N, c->p.n);
+  if (!c->bsk) return fail(TFHE_HIP_ENOKEYS, "decompress: bootstrapping key not loaded");
+  if (count == 0) return 0;
+  if (!packed || !luts || !n_lut || !out) return fail(TFHE_HIP_EINVAL, "decompress: null buffer or n_lut == 0");
+  return 0;
+}
+
+// Decompression on device buffers (caller as pbs_device): unpack / extract into the shard's d_big workspace
+// (slot 3), then the rotation (slot 0).
+int decompress_device(tfhe_ctx* c, shard& s, const tfhe_pks_params& pp, const u64* d_packed, size_t count,
+                      const u64* d_luts, size_t n_lut, const u32* d_idx, u64* d_out, hipStream_t st) {
+  RC_TRY(grow(s, (void**)&s.d_big, &s.big_cap, count * ((size_t)c->p.n + 1) * sizeof(u64)));
+  timed_begin(c, s, 3, st);
+  HIP_TRY(tfhe::launch_unpack_extract(d_packed, count, (int)pp.out_k, (int)pp.out_N, (int)pp.lwe_per_glwe,
+                                      (int)pp.storage_log, s.d_big, st));
+  timed_end(c, s, 3, st);
+  return bootstrap_device(c, s, s.d_big, count, d_luts, n_lut, d_idx, d_out, st);
 }
 
 }  // namespace
@@ -898,14 +968,16 @@ int tfhe_hip_bcast_plan(const int* devices, int ndev, const char* policy, int rc
   return n < 0 ? fail(n, "bcast_plan: %s", why.c_str()) : n;
 }
 
-static int load_keys_impl(tfhe_ctx* c, const uint64_t* bsk, size_t bsk_len, const uint64_t* ksk, size_t ksk_len,
-                          bool from_host) {
-  if (!c || !bsk || !ksk) return fail(TFHE_HIP_EINVAL, "load_keys: null argument");
+// tfhe_hip_load_keys* (with_ksk) and tfhe_hip_load_bsk* (the BSK half alone; ksk / ksk_len unused)
+static int load_keys_impl(tfhe_ctx* c, const char* what, const uint64_t* bsk, size_t bsk_len, const uint64_t* ksk,
+                          size_t ksk_len, bool with_ksk, bool from_host) {
+  if (!c || !bsk || (with_ksk && !ksk)) return fail(TFHE_HIP_EINVAL, "%s: null argument", what);
+  if (!with_ksk) ksk_len = tfhe::client::ksk_len(c->p);
   if (bsk_len != tfhe::client::bsk_len(c->p) || ksk_len != tfhe::client::ksk_len(c->p))
-    return fail(TFHE_HIP_EINVAL, "load_keys: sizes %zu/%zu, expected %zu/%zu", bsk_len, ksk_len,
+    return fail(TFHE_HIP_EINVAL, "%s: sizes %zu/%zu, expected %zu/%zu", what, bsk_len, ksk_len,
                 tfhe::client::bsk_len(c->p), tfhe::client::ksk_len(c->p));
   std::lock_guard<std::mutex> lk(c->mu);
-  c->keys = false;
+  c->keys = c->bsk = false;  // after a BSK-only load an earlier KSK belongs to another key set: rotation-only
   c->bcast_mode = 0;
   const size_t nd = c->sh.size();
   // every shard: key buffers + a standard-domain BSK staging area (its d_stage)
@@ -913,7 +985,7 @@ static int load_keys_impl(tfhe_ctx* c, const uint64_t* bsk, size_t bsk_len, cons
     DeviceGuard g(s.device);
     if (s.ws_used) HIP_TRY(hipEventSynchronize(s.ws_free));
     if (!s.d_bsk) HIP_TRY(hipMalloc(&s.d_bsk, bsk_len * 8));
-    if (!s.d_ksk) HIP_TRY(hipMalloc(&s.d_ksk, ksk_len * 8));
+    if (with_ksk && !s.d_ksk) HIP_TRY(hipMalloc(&s.d_ksk, ksk_len * 8));
     RC_TRY(grow(s, &s.d_stage, &s.stage_cap, bsk_len * 8));
   }
   shard& s0 = c->sh[0];
@@ -922,9 +994,9 @@ static int load_keys_impl(tfhe_ctx* c, const uint64_t* bsk, size_t bsk_len, cons
     DeviceGuard g(s0.device);
     if (from_host) {
       RC_TRY(upload_pinned(s0, s0.d_stage, bsk, bsk_len * 8));
-      RC_TRY(upload_pinned(s0, s0.d_ksk, ksk, ksk_len * 8));
+      if (with_ksk) RC_TRY(upload_pinned(s0, s0.d_ksk, ksk, ksk_len * 8));
       bsk0 = (const u64*)s0.d_stage;
-    } else {
+    } else if (with_ksk) {
       HIP_TRY(hipMemcpyAsync(s0.d_ksk, ksk, ksk_len * 8, hipMemcpyDeviceToDevice, s0.stream));
       HIP_TRY(hipStreamSynchronize(s0.stream));
     }
@@ -936,21 +1008,30 @@ static int load_keys_impl(tfhe_ctx* c, const uint64_t* bsk, size_t bsk_len, cons
       dst_k[i] = c->sh[i].d_ksk;
     }
     RC_TRY(broadcast(c, bsk0, dst_b, bsk_len));
-    RC_TRY(broadcast(c, s0.d_ksk, dst_k, ksk_len));
+    if (with_ksk) RC_TRY(broadcast(c, s0.d_ksk, dst_k, ksk_len));
   }
   for (size_t i = 0; i < nd; i++)
-    RC_TRY(convert_keys(c, c->sh[i], i == 0 ? bsk0 : (const u64*)c->sh[i].d_stage, bsk_len));
-  c->keys = true;
+    RC_TRY(convert_keys(c, c->sh[i], i == 0 ? bsk0 : (const u64*)c->sh[i].d_stage, bsk_len, with_ksk));
+  c->bsk = true;
+  c->keys = with_ksk;
   return 0;
 }
 
 int tfhe_hip_load_keys(tfhe_ctx* c, const uint64_t* bsk, size_t bsk_len, const uint64_t* ksk, size_t ksk_len) {
-  return load_keys_impl(c, bsk, bsk_len, ksk, ksk_len, true);
+  return load_keys_impl(c, "load_keys", bsk, bsk_len, ksk, ksk_len, true, true);
 }
 
 int tfhe_hip_load_keys_device(tfhe_ctx* c, const uint64_t* d_bsk, size_t bsk_len, const uint64_t* d_ksk,
                               size_t ksk_len) {
-  return load_keys_impl(c, d_bsk, bsk_len, d_ksk, ksk_len, false);
+  return load_keys_impl(c, "load_keys", d_bsk, bsk_len, d_ksk, ksk_len, true, false);
+}
+
+int tfhe_hip_load_bsk(tfhe_ctx* c, const uint64_t* bsk, size_t bsk_len) {
+  return load_keys_impl(c, "load_bsk", bsk, bsk_len, nullptr, 0, false, true);
+}
+
+int tfhe_hip_load_bsk_device(tfhe_ctx* c, const uint64_t* d_bsk, size_t bsk_len) {
+  return load_keys_impl(c, "load_bsk", d_bsk, bsk_len, nullptr, 0, false, false);
 }
 
 int tfhe_hip_load_ms_key(tfhe_ctx* c, const uint64_t* zeros, uint32_t count, double bound, double r_sigma,
@@ -1012,30 +1093,70 @@ int tfhe_hip_ms_reduce(tfhe_ctx* c, const uint64_t* in, size_t B, uint64_t* out,
 
 int tfhe_hip_pbs_async(tfhe_ctx* c, const uint64_t* d_in, size_t B, const uint64_t* d_luts, size_t n_lut,
                        const uint32_t* d_idx, uint64_t* d_out, void* stream) {
-  return pbs_async_call(c, "pbs", d_in, B, d_luts, n_lut, d_idx, nullptr, d_out, stream);
+  return pbs_async_call(c, "pbs", d_in, B, d_luts, n_lut, d_idx, pbs_kind{}, d_out, stream);
 }
 
 int tfhe_hip_pbs(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,
                  const uint32_t* lut_index, uint64_t* lwe_out) {
-  return pbs_host_call(c, "pbs", lwe_in, B, luts, n_lut, lut_index, nullptr, lwe_out);
+  return pbs_host_call(c, "pbs", lwe_in, B, luts, n_lut, lut_index, pbs_kind{}, lwe_out);
 }
 
 int tfhe_hip_pbs_many_async(tfhe_ctx* c, const uint64_t* d_in, size_t B, const uint64_t* d_luts, size_t n_lut,
                             const uint32_t* d_idx, uint32_t n_fn, uint32_t stride, uint64_t* d_out, void* stream) {
   const many_args m{n_fn, stride};
-  return pbs_async_call(c, "pbs_many", d_in, B, d_luts, n_lut, d_idx, &m, d_out, stream);
+  return pbs_async_call(c, "pbs_many", d_in, B, d_luts, n_lut, d_idx, pbs_kind{&m, false}, d_out, stream);
 }
 
 int tfhe_hip_pbs_many(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,
                       const uint32_t* lut_index, uint32_t n_fn, uint32_t stride, uint64_t* lwe_out) {
   const many_args m{n_fn, stride};
-  return pbs_host_call(c, "pbs_many", lwe_in, B, luts, n_lut, lut_index, &m, lwe_out);
+  return pbs_host_call(c, "pbs_many", lwe_in, B, luts, n_lut, lut_index, pbs_kind{&m, false}, lwe_out);
+}
+
+int tfhe_hip_bootstrap_async(tfhe_ctx* c, const uint64_t* d_in, size_t B, const uint64_t* d_luts, size_t n_lut,
+                             const uint32_t* d_idx, uint64_t* d_out, void* stream) {
+  return pbs_async_call(c, "bootstrap", d_in, B, d_luts, n_lut, d_idx, pbs_kind{nullptr, true}, d_out, stream);
+}
+
+int tfhe_hip_bootstrap(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,
+                       const uint32_t* lut_index, uint64_t* lwe_big_out) {
+  return pbs_host_call(c, "bootstrap", lwe_in, B, luts, n_lut, lut_index, pbs_kind{nullptr, true}, lwe_big_out);
+}
+
+int tfhe_hip_decompress_async(tfhe_ctx* c, const tfhe_pks_params* pp, const uint64_t* d_packed, size_t packed_words,
+                              size_t count, const uint64_t* d_luts, size_t n_lut, const uint32_t* d_idx,
+                              uint64_t* d_out, void* stream) {
+  RC_TRY(decompress_check(c, pp, d_packed, packed_words, count, d_luts, n_lut, d_out));
+  if (count == 0) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  size_t si = 0;
+  RC_TRY(shard_of_input(c, "decompress", d_packed, &si));
+  shard& s = c->sh[si];
+  DeviceGuard g(s.device);
+  hipStream_t st = resolve_stream(stream, s.stream);
+  RC_TRY(ws_begin(s, st));
+  RC_TRY(decompress_device(c, s, *pp, d_packed, count, d_luts, n_lut, d_idx, d_out, st));
+  return ws_end(s, st);
+}
+
+int tfhe_hip_decompress(tfhe_ctx* c, const tfhe_pks_params* pp, const uint64_t* packed, size_t packed_words,
+                        size_t count, const uint64_t* luts, size_t n_lut, const uint32_t* lut_index,
+                        uint64_t* lwe_big_out) {
+  RC_TRY(decompress_check(c, pp, packed, packed_words, count, luts, n_lut, lwe_big_out));
+  if (count == 0) return 0;
+  RC_TRY(host_lut_index_check("decompress", lut_index, count, n_lut));
+  const size_t out_bytes = count * ((size_t)c->p.k * c->p.N + 1) * 8;
+  return staged_call(c, {{packed, packed_words * 8}, {luts, n_lut * c->p.N * 8}, {lut_index, lut_index ? count * 4 : 0}},
+                     out_bytes, {{lwe_big_out, 3, out_bytes}}, [&](shard& s, std::vector<void*>& d) {
+                       return decompress_device(c, s, *pp, (const u64*)d[0], count, (const u64*)d[1], n_lut,
+                                                (const u32*)d[2], (u64*)d[3], s.stream);
+                     });
 }
 
 int tfhe_hip_blind_rotate(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,
                           const uint32_t* lut_index, uint64_t* acc_out) {
   if (!c) return fail(TFHE_HIP_EINVAL, "blind_rotate: null ctx");
-  if (!c->keys) return fail(TFHE_HIP_ENOKEYS, "blind_rotate: keys not loaded");
+  if (!c->bsk) return fail(TFHE_HIP_ENOKEYS, "blind_rotate: keys not loaded");
   if (B == 0) return 0;
   if (!lwe_in || !luts || !n_lut || !acc_out) return fail(TFHE_HIP_EINVAL, "blind_rotate: null buffer");
   if (lut_index)
@@ -1192,7 +1313,7 @@ int tfhe_hip_timing_reset(tfhe_ctx* c) {
   if (!c) return fail(TFHE_HIP_EINVAL, "timing: null ctx");
   std::lock_guard<std::mutex> lk(c->mu);
   for (auto& s : c->sh)
-    for (int w = 0; w < 3; w++) {
+    for (int w = 0; w < TIMING_SLOTS; w++) {
       for (auto e : s.ev[w]) s.ev_pool.push_back(e);
       s.ev[w].clear();
     }
@@ -1200,7 +1321,7 @@ int tfhe_hip_timing_reset(tfhe_ctx* c) {
 }
 
 int tfhe_hip_timing_stats(tfhe_ctx* c, int which, double* total_ms, int* launches) {
-  if (!c || which < 0 || which > 2 || !total_ms || !launches) return fail(TFHE_HIP_EINVAL, "timing: bad arguments");
+  if (!c || which < 0 || which >= TIMING_SLOTS || !total_ms || !launches) return fail(TFHE_HIP_EINVAL, "timing: bad arguments");
   std::lock_guard<std::mutex> lk(c->mu);
   double tot = 0;
   int cnt = 0;

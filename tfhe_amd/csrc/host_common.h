@@ -10,6 +10,10 @@
 
 // the library's thread-local error slot (owned by api.cpp)
 int tfhe_hip_set_error(int code, const char* msg);
+// Argument check of a list of compressed GLWEs (owned by pks_api.cpp; shared with tfhe_hip_decompress): EINVAL for
+// invalid parameters, count > 0x7FFFFFFF or packed_words != the words of ceil(count / lwe_per_glwe) groups,
+// EUNSUPPORTED for out_N above the unpack kernel's 4096.  `what` prefixes the message.
+int tfhe_hip_pks_list_check(const tfhe_pks_params* pp, size_t packed_words, size_t count, const char* what);
 
 namespace {
 

@@ -99,5 +99,10 @@ hipError_t launch_ms_reduce(u64* lwe, size_t B, int n, const u64* zeros, int cou
 // at degree f * stride, for either ring (zp: Z_p accumulators, converted to 2^64) and N <= 2048; acc 16-byte aligned
 hipError_t launch_sample_extract_many(const u64* acc, size_t B, int k, int N, bool zp, int n_fn, int stride, u64* out,
                                       hipStream_t s);
+// decompression, steps 1 and 2 (decompress.hip): `packed` = ceil(count / lpg) compressed GLWEs (k, N, storage w
+// bits) back to back as tfhe_hip_pks_compress writes them -> count x (kN + 1) LWEs, row g * lpg + i = the sample
+// at degree i of group g.  N <= 4096 (hipErrorInvalidValue above), count <= 0x7FFFFFFF
+hipError_t launch_unpack_extract(const u64* packed, size_t count, int k, int N, int lpg, int w, u64* lwes_out,
+                                 hipStream_t s);
 hipError_t launch_ntt2048_inv(u64* polys, size_t count, const u64* tw, u64 ninv, hipStream_t s);
 }  // namespace tfhe

@@ -27,8 +27,23 @@ bool pks_valid(const tfhe_pks_params* pp) {
 }
 
 constexpr size_t PKS_T_BUDGET = 512ull << 20;  // T workspace per chunk of groups
+constexpr uint32_t UNPACK_MAX_N = 4096;          // decompress.hip: one mask polynomial in 32 KB of LDS
 
 }  // namespace
+
+int tfhe_hip_pks_list_check(const tfhe_pks_params* pp, size_t packed_words, size_t count, const char* what) {
+  if (!pks_valid(pp)) return fail(TFHE_HIP_EINVAL, "%s: invalid packing parameters", what);
+  if (pp->out_N > UNPACK_MAX_N)
+    return fail(TFHE_HIP_EUNSUPPORTED, "%s: out_N = %u, the unpack kernel covers out_N <= %u", what, pp->out_N, UNPACK_MAX_N);
+  if (count > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "%s: too many ciphertexts", what);
+  const size_t lpg = pp->lwe_per_glwe, rest = count % lpg;
+  const size_t want = (count / lpg) * tfhe::client::pks_packed_words(*pp, (uint32_t)lpg) +
+                      (rest ? tfhe::client::pks_packed_words(*pp, (uint32_t)rest) : 0);
+  if (packed_words != want)
+    return fail(TFHE_HIP_EINVAL, "%s: packed_words = %zu, %zu ciphertexts in groups of %zu take %zu", what, packed_words,
+                count, lpg, want);
+  return 0;
+}
 
 struct tfhe_pks_ctx {
   tfhe_pks_params pp{};
@@ -230,6 +245,43 @@ int tfhe_hip_pks_compress(const tfhe_pks_params* pp, const uint64_t* glwe, uint3
 int tfhe_hip_pks_extract(const tfhe_pks_params* pp, const uint64_t* packed, uint32_t bodies, uint64_t* glwe) {
   if (!pks_valid(pp) || !glwe || !packed || bodies > pp->out_N) return fail(TFHE_HIP_EINVAL, "pks_extract: bad arguments");
   tfhe::client::pks_extract(*pp, packed, bodies, glwe);
+  return 0;
+}
+
+static hipError_t unpack_extract_device(const tfhe_pks_params& p, const u64* d_packed, size_t count, u64* d_out,
+                                        hipStream_t s) {
+  return tfhe::launch_unpack_extract(d_packed, count, (int)p.out_k, (int)p.out_N, (int)p.lwe_per_glwe,
+                                     (int)p.storage_log, d_out, s);
+}
+
+int tfhe_hip_pks_unpack_extract_async(tfhe_pks_ctx* c, const uint64_t* d_packed, size_t packed_words, size_t count,
+                                      uint64_t* d_lwes_out, void* stream) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "pks_unpack_extract: null ctx");
+  RC_TRY(tfhe_hip_pks_list_check(&c->pp, packed_words, count, "pks_unpack_extract"));
+  if (count == 0) return 0;
+  if (!d_packed || !d_lwes_out) return fail(TFHE_HIP_EINVAL, "pks_unpack_extract: null buffer");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  HIP_TRY(unpack_extract_device(c->pp, d_packed, count, d_lwes_out, resolve_stream(stream, c->stream)));
+  return 0;
+}
+
+int tfhe_hip_pks_unpack_extract(tfhe_pks_ctx* c, const uint64_t* packed, size_t packed_words, size_t count,
+                                uint64_t* lwes_out) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "pks_unpack_extract: null ctx");
+  RC_TRY(tfhe_hip_pks_list_check(&c->pp, packed_words, count, "pks_unpack_extract"));
+  if (count == 0) return 0;
+  if (!packed || !lwes_out) return fail(TFHE_HIP_EINVAL, "pks_unpack_extract: null buffer");
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const size_t out_bytes = count * ((size_t)c->pp.out_k * c->pp.out_N + 1) * 8;
+  const size_t in_off = (out_bytes + 255) & ~(size_t)255;
+  RC_TRY(grow_device_buffer((void**)&c->d_io, &c->io_cap, in_off + packed_words * 8));
+  u64* d_in = (u64*)((char*)c->d_io + in_off);
+  HIP_TRY(hipMemcpyAsync(d_in, packed, packed_words * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(unpack_extract_device(c->pp, d_in, count, c->d_io, c->stream));
+  HIP_TRY(hipMemcpyAsync(lwes_out, c->d_io, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
 
