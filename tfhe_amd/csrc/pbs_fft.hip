@@ -260,6 +260,24 @@ struct FpShared {
   double2 T[2 * CTS][T_C64];                       // after the tables: T - 8 KB is still inside the block
   double2 K[2][STEP_C64];
 };
+// FFT_CT_AHEAD, FFT_DMA_IMM (round 9; 0 = the parent's code each): how the LWE mask word and the level-step
+// chunk reach the wave.
+//   FFT_CT_AHEAD: the mask word of CMUX i + 1 is loaded during CMUX i (after the rotation, ahead of level step 0's
+//     chunk) and becomes the scalar ms2048 value behind the vmcnt(0) of level step 0's glds_barrier, so no CMUX opens
+//     with a global load and a full wait.  Only the word's high half is loaded (ms2048 reads bits 52..63).  Row n + 1
+//     words long: CMUX n - 1 prefetches the body word and ignores it.
+//   FFT_DMA_IMM: the eight 1 KB pieces a wave loads per level step are contiguous in the BSK row and in the chunk, so
+//     pieces 1..3 and 5..7 ride on the instruction's immediate offset (it advances the buffer address AND the LDS
+//     address): two M0 values and two soffsets per wave and level step instead of eight of each.
+// Measured and not shipped: the level-step buffer as a __shared__ object of its own and its pieces issued from asm
+// statements that hipcc's wait bookkeeping does not see (tools/ab_patches/r09_k_own_dma_asm.patch); the pieces of level
+// steps 0 and 2 issued one per iteration of the digit loop (tools/ab_patches/r09_dma_spread.patch).
+#ifndef FFT_CT_AHEAD
+#define FFT_CT_AHEAD 1
+#endif
+#ifndef FFT_DMA_IMM
+#define FFT_DMA_IMM 1
+#endif
 template <int CTS>
 struct FpShared<CTS, false> {
   double2 twI[M];                                  // TW_I only (passes A, B: registers, loaded from global)
@@ -465,6 +483,34 @@ __device__ __forceinline__ void load_step_buf(__amdgpu_buffer_rsrc_t bsr, int g,
                                              16, voff, soff, 0, 0);
   }
 }
+// FFT_DMA_IMM: the wave's 32 / NW blocks in groups of four consecutive ones (NW = 4: one component row, 8 KB in a row,
+// in the BSK and in the chunk), pieces 1..3 of a group on the immediate offset
+template <int NW>
+__device__ __forceinline__ void load_step_buf4(__amdgpu_buffer_rsrc_t bsr, int g, double2* dst, int wave_s, int voff) {
+  static_assert((32 / NW) % 4 == 0 && 16 % (32 / NW) == 0, "groups of four blocks inside one component row");
+  const int i = g / 3, q = g - 3 * (g / 3);
+#pragma unroll
+  for (int h = 0; h < 32 / NW; h += 4) {
+    const int blk = wave_s * (32 / NW) + h;
+    const int c = blk >> 4;
+    const int soff = ((i * 6 + c * 3 + q) * (2 * M)) * (int)sizeof(double2) + (blk & 15) * 1024;  // < 2^31: BSK < 2 GB
+    auto* ld = (__attribute__((address_space(3))) void*)((char*)dst + blk * 1024);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(bsr, ld, 16, voff, soff, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(bsr, ld, 16, voff, soff, 1024, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(bsr, ld, 16, voff, soff, 2048, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(bsr, ld, 16, voff, soff, 3072, 0);
+  }
+}
+
+#ifndef FFT_DMASTAMP
+#define FFT_DMASTAMP 0
+#endif
+#if FFT_DMASTAMP
+// diagnostic build only (tools/dma_stamps.py): shader-clock cycles (s_memtime) a wave spends issuing the eight pieces of
+// a level step, summed over the CMUX loop per site q = 0, 1, 2; [3] = the whole loop.  Workgroups 0..63 x wave.  The
+// stamps pin the pieces at the step's start (a sched_barrier on either side).
+__device__ unsigned long long g_dmast[64 * 4 * 4];
+#endif
 
 #ifndef FFT_WGTIME
 #define FFT_WGTIME 0
@@ -600,6 +646,16 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
   if (wg_staggered(blockIdx.x, (unsigned)n_cus))
     for (int k = 0; k < FFT_STAGGER; k++) __builtin_amdgcn_s_sleep(127);
 #endif
+#if FFT_DMASTAMP
+  unsigned long long dma_cyc[3] = {0, 0, 0};
+  const unsigned long long loop_t0 = __builtin_amdgcn_s_memtime();
+#endif
+#if FFT_CT_AHEAD
+  // ms2048 from a word's high half (bits 52..63 are all it reads); the high halves of the row
+  auto ms2048_hi = [](u32 hi) { return (int)((((hi >> 20) + 1u) >> 1) & 2047u); };
+  const u32* ct_hi = (const u32*)ct + 1;
+  int a_s = __builtin_amdgcn_readfirstlane(ms2048_hi(ct_hi[0]));
+#endif
   for (int i = 0; i < n; i++) {
 #if FFT_PRIO == 6
     prio_flag = ((unsigned)i >> FFT_PRIO_SH ^ prio_ph) & 1u;
@@ -611,7 +667,14 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
 #if FFT_ROTPRIO
     __builtin_amdgcn_s_setprio(FFT_ROTPRIO);  // A/B: the rotation phase at a raised priority
 #endif
+#if FFT_CT_AHEAD
+    rotate_states(acc, a_s, lane, T, st);
+    // the next CMUX's mask word (i = n - 1: the body word, ignored), issued ahead of level step 0's chunk and
+    // consumed behind that step's glds_barrier
+    u32 ct_next = ct_hi[2 * (size_t)(i + 1)];
+#else
     rotate_states(acc, ms2048(ct[i]), lane, T, st);
+#endif
     double o0r[8], o0i[8], o1r[8], o1i[8];
     // level steps q = 0, 1, 2 (least significant first), each specialised at compile time: q = 0 starts the two
     // fma chains with a multiply (no zeroed partial sums), q = 2 takes the top digit (no carry bit, no next state)
@@ -627,10 +690,20 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
       } else {
         // one buffer: every wave is done with step g - 1's chunk (the exchange's barriers order q = 0)
         if (q > 0) __syncthreads();
-#if FFT_BUF_LDS
+#if FFT_DMASTAMP
+        __builtin_amdgcn_sched_barrier(0);
+        const unsigned long long dma_t0 = __builtin_amdgcn_s_memtime();
+#endif
+#if FFT_BUF_LDS && FFT_DMA_IMM
+        load_step_buf4<NW>(bsr, g, sh.K[0], wave_s, voff);
+#elif FFT_BUF_LDS
         load_step_buf<NW>(bsr, g, sh.K[0], wave_s, voff);
 #else
         load_step<NW>(bsk, g, sh.K[0], wave_s, lane);
+#endif
+#if FFT_DMASTAMP
+        dma_cyc[q] += __builtin_amdgcn_s_memtime() - dma_t0;
+        __builtin_amdgcn_sched_barrier(0);
 #endif
       }
       double xr[8], xi[8];
@@ -655,6 +728,13 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
       dft512_fwd_t<true, true>(xr, xi, T, lane, tb, twA, twB);
 #endif
       if constexpr (!LDS_TW) glds_barrier();  // step g's chunk has landed
+#if FFT_CT_AHEAD
+      if constexpr (q == 0) {
+        // behind the barrier's vmcnt(0) the prefetched word is back: from here it is the scalar a of the next CMUX
+        asm volatile("" : "+v"(ct_next));
+        a_s = ms2048_hi(__builtin_amdgcn_readfirstlane(ct_next));
+      }
+#endif
 #if FFT_MACPRIO
       __builtin_amdgcn_s_setprio(3);  // the short MAC ahead of the other workgroup's transforms
 #endif
@@ -724,6 +804,15 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
       acc[e + 8] = ACC_ADD(acc[e + 8], xi[e]);
     }
   }
+#if FFT_DMASTAMP
+  if (lane == 0 && blockIdx.x < 64 && wave < 4) {
+    unsigned long long* o = g_dmast + (blockIdx.x * 4 + wave) * 4;
+    o[0] = dma_cyc[0];
+    o[1] = dma_cyc[1];
+    o[2] = dma_cyc[2];
+    o[3] = __builtin_amdgcn_s_memtime() - loop_t0;
+  }
+#endif
 #if FFT_WGTIME
   if (threadIdx.x == 0 && blockIdx.x < 16384) {
     const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
@@ -1310,6 +1399,12 @@ hipError_t launch_blind_rotate_fft(const u64* lwe_in, size_t B, int n, const u64
 extern "C" int tfhe_hip_debug_latstamps(unsigned long long* out, size_t n) {
   if (n > 8 * 8 * 6) n = 8 * 8 * 6;
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(fftk::g_latst), n * 8, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+#endif
+#if FFT_DMASTAMP
+extern "C" int tfhe_hip_debug_dmastamps(unsigned long long* out, size_t n) {
+  if (n > 64 * 4 * 4) n = 64 * 4 * 4;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(fftk::g_dmast), n * 8, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
 #endif
 #if FFT_WGTIME
