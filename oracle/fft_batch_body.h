@@ -101,7 +101,7 @@ static inline void dft8(CX x[8], int inv) {
   }
 }
 
-/* or_fft_fwd at N = 1024 (FFT_TDFT8 = 0): slot twist, then passes A (merged table), B, C; device order out */
+/* or_fft_fwd at N = 1024: slot twist, then passes A (merged table), B, C; device order out */
 static void fwd(const VD* a, CX* out, const or_fftb_tab* T) {
   CX A[64][8], Bv[64][8], x[8];
   for (int L = 0; L < 64; L++) {

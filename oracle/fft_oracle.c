@@ -153,7 +153,7 @@ static inline or_c64 w8(or_c64 t, int j, int inv) {
   return r;
 }
 
-/* dft8 (round 5, = fft512.h FFT_DFT8_FMA): the even half as below; the odd half keeps the w8 forms unscaled
+/* dft8 (round 5, = fft512.h dft8): the even half as below; the odd half keeps the w8 forms unscaled
  * (u5 = w8^1 t1 / s, u7 = w8^3 t3 / s, s = sqrt(1/2)) and folds s into the last stage:
  *   z5' = u5 + u7, z7' = u5 - u7, z4 = t0 + r t2, z6 = t0 - r t2   (r = +i forward, -i inverse)
  *   X1 = fma(s, z5', z4), X5 = fma(-s, z5', z4), X3 = z6 + r (s z7'), X7 = z6 - r (s z7') as fmas */
@@ -215,55 +215,14 @@ __attribute__((unused)) static void dft8_r4(or_c64 x[8], int inv) {
   for (int k = 0; k < 8; k++) x[k] = u[brv3[k]];
 }
 
-/* FFT_TDFT8 (default 0, = fft512.h): measured slower on the device, kept for its A/B build (make FFT_TDFT8=1 ...) */
-#ifndef FFT_TDFT8
-#define FFT_TDFT8 0
-#endif
-/* the N = 1024 forward's slot twist + pass A's DFT8 as one twisted DFT8 (round 5, = fft512.h twist_dft8_fwd): x(X) =
- * sum_e x_e X^e at the roots X_k = e^{i pi (1 + 4k)/16} of X^8 = i by a radix-2 split (X^8 - i = (X^4 - w)(X^4 + w), ...),
- * 12 butterflies a +- e^{i th} b each with b through the tangent / cotangent form and cos / sin th in the output fmas */
-#define TD_T8 0.41421356237309504880   /* tan(pi/8) */
-#define TD_C8 0.92387953251128675613   /* cos(pi/8) */
-#define TD_T16 0.19891236737965800691  /* tan(pi/16) */
-#define TD_C16 0.98078528040323044913  /* cos(pi/16) */
-#define TD_T316 0.66817863791929891999 /* tan(3pi/16) */
-#define TD_C316 0.83146961230254523708 /* cos(3pi/16) */
-static void tbfly(or_c64* a, or_c64* b, double t, double sc, int cot) {
-  double ur, ui;
-  if (!cot) { ur = fma(-t, b->im, b->re); ui = fma(t, b->re, b->im); }
-  else { ur = fma(t, b->re, -b->im); ui = fma(t, b->im, b->re); }
-  const or_c64 p = *a;
-  a->re = fma(sc, ur, p.re); a->im = fma(sc, ui, p.im);
-  b->re = fma(-sc, ur, p.re); b->im = fma(-sc, ui, p.im);
-}
-__attribute__((unused)) static void tdft8_fwd(or_c64 x[8]) {
-  for (int e = 0; e < 4; e++) {
-    const double ur = x[e + 4].re - x[e + 4].im, ui = x[e + 4].im + x[e + 4].re;
-    const or_c64 p = x[e];
-    x[e].re = fma(SQRT1_2, ur, p.re); x[e].im = fma(SQRT1_2, ui, p.im);
-    x[e + 4].re = fma(-SQRT1_2, ur, p.re); x[e + 4].im = fma(-SQRT1_2, ui, p.im);
-  }
-  tbfly(&x[0], &x[2], TD_T8, TD_C8, 0);
-  tbfly(&x[1], &x[3], TD_T8, TD_C8, 0);
-  tbfly(&x[4], &x[6], -TD_T8, TD_C8, 1);
-  tbfly(&x[5], &x[7], -TD_T8, TD_C8, 1);
-  tbfly(&x[0], &x[1], TD_T16, TD_C16, 0);
-  tbfly(&x[2], &x[3], -TD_T16, TD_C16, 1);
-  tbfly(&x[4], &x[5], TD_T316, TD_C316, 1);
-  tbfly(&x[6], &x[7], -TD_T316, -TD_C316, 0);
-  const or_c64 y[8] = {x[0], x[4], x[2], x[6], x[1], x[5], x[3], x[7]}; /* positions -> X_k */
-  memcpy(x, y, sizeof(y));
-}
-
 /* forward 3-pass DFT: natural order in, device order out; pass A multiplies slots merged ? 0..7 : 1..7 by twa
- * (the twist-merged tables multiply every slot); twin: the input is not yet twisted, pass A's DFT8 is tdft8_fwd */
-static void dft512_fwd_tab(const or_c64* in, or_c64* out, const or_c64 (*twa)[64], int merged, int twin) {
+ * (the twist-merged tables multiply every slot) */
+static void dft512_fwd_tab(const or_c64* in, or_c64* out, const or_c64 (*twa)[64], int merged) {
   const fft_tab* T = tab();
   or_c64 A[64][8], Bv[64][8], x[8];
   for (int L = 0; L < 64; L++) {
     for (int e = 0; e < 8; e++) x[e] = in[L + 64 * e];
-    if (twin) tdft8_fwd(x);
-    else dft8(x, 0);
+    dft8(x, 0);
     for (int e = merged ? 0 : 1; e < 8; e++) x[e] = cmul(x[e], twa[e][L].re, twa[e][L].im);
     memcpy(A[L], x, sizeof(x));
   }
@@ -420,7 +379,7 @@ static void radix4_s(or_c64* x, int i0, int cs, int inv) {
   x[i0 + 3] = inv ? p : q;
 }
 
-/* dft16 (round 5, = fft1k.h F1_DFT16_FMA): the first radix-4 pass, then group k0 = 0 plain, groups 1 and 3 with
+/* dft16 (round 5, = fft1k.h dft16): the first radix-4 pass, then group k0 = 0 plain, groups 1 and 3 with
  * W^1 / W^3 / W^9 as cmul and the W^2 / W^6 element unscaled (radix4_s cs = 1), group 2 with W^4 = i and the W^2 / W^6
  * elements unscaled (radix4_s cs = 0) */
 static void dft16(or_c64 x[16], int inv) {
@@ -518,18 +477,12 @@ void or_fft_fwd(const double* a, uint32_t N, or_c64* out) {
   if (N != 2 * FFT_M) abort();
   const fft_tab* T = tab();
   or_c64 z[FFT_M];
-#if FFT_TDFT8
-  for (int j = 0; j < FFT_M; j++) z[j] = (or_c64){a[j], a[j + FFT_M]};
-  /* j = L + 64 e: the slot part zeta^{64 e} of the twist inside pass A's twisted DFT8, zeta^L in pass A's table */
-  dft512_fwd_tab(z, out, T->twAm, 1, 1);
-#else
   for (int j = 0; j < FFT_M; j++) { /* j = L + 64 e: slot constant zeta^{64 e} (e > 0), zeta^L in pass A */
     const or_c64 v = {a[j], a[j + FFT_M]};
     const int e = j >> 6;
     z[j] = e ? cmul(v, T->twist[64 * e].re, T->twist[64 * e].im) : v;
   }
-  dft512_fwd_tab(z, out, T->twAm, 1, 0);
-#endif
+  dft512_fwd_tab(z, out, T->twAm, 1);
 }
 
 void or_fft_inv(const or_c64* in, uint32_t N, double* out) {
@@ -546,7 +499,7 @@ void or_fft_inv(const or_c64* in, uint32_t N, double* out) {
   }
 }
 
-/* The device's accumulator update (fft512.h torus_acc_add / torus_acc_add_wide, FFT_TORUS_NORINT, round 5): h =
+/* The device's accumulator update (fft512.h torus_acc_add_y / torus_acc_add_wide_y, round 5): h =
  * floor(x 2^-32), l = fma(-h, 2^32, x) (exact unless -2^32 < x < 0, where x + 2^32 rounds once), and the increment
  * h 2^32 + rint(l) mod 2^64 -- rint(x) mod 2^64 except for that double rounding of tiny negative x.  The device takes
  * rint(l) from the bits of l + 2^52 and h mod 2^32 from those of h + 1.5 2^52 (N = 1024) or of the exact split
@@ -596,12 +549,6 @@ static void monomial_torus(uint64_t* out, const uint64_t* in, uint32_t N, uint32
   }
 }
 
-/* the N = 2048 MAC order: 0 = one fma chain over every (c, l) from zero (pbs_fft2k.hip's slot-owned MAC), 1 = the
- * split order of N = 1024 (per-component products, then one add: pbs_fft2k.hip F1_PAIRMAC).  A/B switch, set through
- * or_set_fft2k_mac_split (oracle.py: ORACLE_FFT2K_SPLIT=1) */
-int or_fft2k_mac_split = 0;
-void or_set_fft2k_mac_split(int v) { or_fft2k_mac_split = v != 0; }
-
 /* trace (nullable): (n + 1) x (k+1)N words, the accumulator before CMUX 0 and after every CMUX i (skipped CMUXes
  * included), so tests can hand each state to the exact arbiter (exact_oracle.c) */
 static void blind_rotate_fft_impl(const or_params* p, const or_c64* bsk_f, const uint64_t* lwe_in, const uint64_t* lut,
@@ -619,7 +566,7 @@ static void blind_rotate_fft_impl(const or_params* p, const or_c64* bsk_f, const
   /* MAC order.  N = 1024 (pbs_fft.hip: component-pair and latency kernels): one fma chain per component,
    * O_j = O_j^0 + O_j^1 with O_j^c = chain over the levels of D_(c,l) (.) BSK_i[(c, l)][j] from zero.
    * N = 2048 (pbs_fft2k.hip): one chain over every (c, l) from zero. */
-  const int split = N == 2 * FFT_M || or_fft2k_mac_split;
+  const int split = N == 2 * FFT_M;
   double res[4 * FFT_M];
   int64_t d[64];
   const size_t row = (size_t)(k + 1) * N;

@@ -78,8 +78,6 @@ def lib():
         L.or_f64_to_torus.argtypes = [ctypes.c_double]
         L.or_f64_to_torus_dev.restype = ctypes.c_uint64
         L.or_f64_to_torus_dev.argtypes = [ctypes.c_double]
-        if os.environ.get("ORACLE_FFT2K_SPLIT") == "1":  # A/B of the N = 2048 MAC order (fft_oracle.c)
-            L.or_set_fft2k_mac_split(1)
         _LIB = L
     return _LIB
 
@@ -326,7 +324,7 @@ def f64_to_torus(x: float) -> int:
 
 
 def f64_to_torus_dev(x: float) -> int:
-    """the device's accumulator increment (fft512.h torus_acc_add): rint(x) mod 2^64 but for tiny negative x"""
+    """the device's accumulator increment (fft512.h torus_acc_add_y): rint(x) mod 2^64 but for tiny negative x"""
     return int(lib().or_f64_to_torus_dev(float(x)))
 
 

@@ -84,7 +84,7 @@ def test_f64_to_torus_rounding(oracle_mod):
 
 
 def test_device_accumulator_increment(oracle_mod):
-    """or_f64_to_torus_dev (the device's rint-free update, fft512.h torus_acc_add[_wide]): equal to rint(x) mod 2^64
+    """or_f64_to_torus_dev (the device's rint-free update, fft512.h): equal to rint(x) mod 2^64
     for every |x| >= 2^32 and every x >= 0, and off by at most one for tiny negative x (x + 2^32 rounded once before
     the integer rounding); the two bit-pattern words of the device form restated in Python agree with it."""
     import struct
@@ -111,7 +111,7 @@ def test_device_accumulator_increment(oracle_mod):
 
 
 def test_scaled_accumulator_update_forms(oracle_mod):
-    """Round 5 (FFT_Y32 / F1_Y32): the keys' spectra carry 2^-32, so the inverse returns y = x 2^-32 and the device
+    """Round 5: the keys' spectra carry 2^-32, so the inverse returns y = x 2^-32 and the device
     updates from y (fft512.h torus_acc_add_y at N = 1024, torus_acc_add_wide_y at N = 2048).  Restated here in IEEE
     double steps (numpy float64, one rounding per operation): both forms give or_f64_to_torus_dev(x) bit for bit,
     the wide one for every |x| < 2^96 (P-FHEVM reaches ~2^91), the N = 1024 one for |x| < 2^83 (P-GATE: 2^81.6)."""
@@ -142,7 +142,7 @@ def test_scaled_accumulator_update_forms(oracle_mod):
 
 
 def test_negated_digit_form():
-    """F1_NEGDIG (pbs_fft2k.hip dig23_neg): (int)(255 - h) >> 9 == -dig23(h) for the high word h of the rotated
+    """The negated digit of pbs_fft2k.hip's rotate_digits: (int)(255 - h) >> 9 == -dig23(h) for the high word h of the rotated
     difference (checked on the device build for all 2^32 words; here on every 2^20-th word, the ties and the wrap)."""
     h = np.concatenate([np.arange(0, 2 ** 32, 2 ** 12, dtype=np.uint64),
                         np.arange(2 ** 31 - 1024, 2 ** 31 + 1024, dtype=np.uint64),
@@ -281,7 +281,7 @@ def test_device_decomposition_steps_equal_signed_decomposer(oracle_mod):
 
 
 def test_decomp_23x1_high_word_restatement(oracle_mod):
-    """pbs_fft2k.hip (dig23) decomposes 2^23 x 1 from the high word alone: st = (hi + 2^8) >> 9,
+    """pbs_fft2k.hip (rotate_digits) decomposes 2^23 x 1 from the high word alone: st = (hi + 2^8) >> 9,
     digit = ((st + 2^22 - 1) mod 2^23) - (2^22 - 1).  Equal to or_decompose on edge and random words."""
     rng = np.random.default_rng(23)
     his = [0, 1, 255, 256, 511, 512, 2**31, 2**32 - 1, 2**32 - 256, 2**32 - 257, 2**32 - 512, 2**30 + 2**9 - 1,
@@ -296,7 +296,7 @@ def test_decomp_23x1_high_word_restatement(oracle_mod):
 
 
 def _fast_f64_to_torus(x: float) -> int:
-    """pbs_fft.hip's f64_to_torus (fft512.h), restated: rint, h = floor(t / 2^32), l = t - h 2^32, and the low
+    """The rint-based conversion of the round-1 to 4 kernels, restated: rint, h = floor(t / 2^32), l = t - h 2^32, and the low
     word of h taken from the mantissa of h + 1.5 * 2^52 -- exact only while |h| < 2^51, i.e. |x| < 2^83."""
     import struct
     t = float(np.rint(x))

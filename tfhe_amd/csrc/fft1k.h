@@ -113,18 +113,13 @@ __device__ __forceinline__ void w16(double& re, double& im) {
   if constexpr (K == 1) cmul<INV>(re, im, make_double2(C16, S16));
   else if constexpr (K == 3) cmul<INV>(re, im, make_double2(S16, C16));
   else if constexpr (K == 9) cmul<INV>(re, im, make_double2(-C16, -S16));
-  else if constexpr (K == 2) w8<INV, 1>(re, im);
-  else if constexpr (K == 6) w8<INV, 3>(re, im);
-  else w8<INV, 2>(re, im);  // K == 4: i
+  else w8<INV, 2>(re, im);  // K == 4: i (W16^2 and W16^6 go unscaled through w8u below)
 }
 
-// F1_DFT16_FMA 1 (default since round 5): the sqrt(1/2) of the W16^2 / W16^6 twiddles folded into the second radix-4
-// pass as fmas (as fft512.h's FFT_DFT8_FMA): group k0 = 2 takes b = s u9, d = s u11 (t2, t3 scaled by s: 4 fmas per
-// output pair), groups 1 and 3 take c = s u6 / s u14 (t0, t1 = a +- s u: 2 fmas each) -- 8 multiplies fewer per
-// DFT16, -32 f64 per wave and CMUX.  Restated in oracle/fft_oracle.c:dft16; 0 = the round-4 form.
-#ifndef F1_DFT16_FMA
-#define F1_DFT16_FMA 1
-#endif
+// The sqrt(1/2) of the W16^2 / W16^6 twiddles is folded into the second radix-4 pass as fmas (round 5, as fft512.h's
+// dft8): group k0 = 2 takes b = s u9, d = s u11 (t2, t3 scaled by s: 4 fmas per output pair), groups 1 and 3 take
+// c = s u6 / s u14 (t0, t1 = a +- s u: 2 fmas each) -- 8 multiplies fewer per DFT16, -32 f64 per wave and CMUX.
+// Restated in oracle/fft_oracle.c:dft16.
 // w8^J (J = 1, 3) without its sqrt(1/2) factor: the oracle's w8u
 template <bool INV, int J>
 __device__ __forceinline__ void w8u(double& re, double& im) {
@@ -180,7 +175,6 @@ __device__ __forceinline__ void dft16(double (&xr)[16], double (&xi)[16]) {
 #pragma unroll
   for (int n0 = 0; n0 < 4; n0++)
     r4<INV>(xr[n0], xi[n0], xr[n0 + 4], xi[n0 + 4], xr[n0 + 8], xi[n0 + 8], xr[n0 + 12], xi[n0 + 12]);
-#if F1_DFT16_FMA
   r4<INV>(xr[0], xi[0], xr[1], xi[1], xr[2], xi[2], xr[3], xi[3]);
   w16<INV, 1>(xr[5], xi[5]);  // group 1: W^0, W^1, s u(W^2), W^3
   w8u<INV, 1>(xr[6], xi[6]);
@@ -194,21 +188,6 @@ __device__ __forceinline__ void dft16(double (&xr)[16], double (&xi)[16]) {
   w8u<INV, 3>(xr[14], xi[14]);
   w16<INV, 9>(xr[15], xi[15]);
   r4_cs<INV>(xr[12], xi[12], xr[13], xi[13], xr[14], xi[14], xr[15], xi[15]);
-#else
-  w16<INV, 1>(xr[5], xi[5]);
-  w16<INV, 2>(xr[6], xi[6]);
-  w16<INV, 3>(xr[7], xi[7]);
-  w16<INV, 2>(xr[9], xi[9]);
-  w16<INV, 4>(xr[10], xi[10]);
-  w16<INV, 6>(xr[11], xi[11]);
-  w16<INV, 3>(xr[13], xi[13]);
-  w16<INV, 6>(xr[14], xi[14]);
-  w16<INV, 9>(xr[15], xi[15]);
-#pragma unroll
-  for (int k0 = 0; k0 < 4; k0++)
-    r4<INV>(xr[4 * k0], xi[4 * k0], xr[4 * k0 + 1], xi[4 * k0 + 1], xr[4 * k0 + 2], xi[4 * k0 + 2], xr[4 * k0 + 3],
-            xi[4 * k0 + 3]);
-#endif
   double yr[16], yi[16];
 #pragma unroll
   for (int k0 = 0; k0 < 4; k0++)

@@ -47,7 +47,7 @@ __device__ __forceinline__ void fft_fwd_real(const double (&a)[16], double (&xr)
     xr[e] = a[e];
     xi[e] = a[e + 8];
   }
-  dft512_fwd<true, true>(xr, xi, T, lane, TBase(lane), tw);  // the slot twist inside pass A (twist_dft8_fwd)
+  dft512_fwd(xr, xi, T, lane, TBase(lane), tw);  // the slot twist inside pass A (twist_dft8_fwd)
 }
 
 // inverse transform (no 1/M) + untwist: slot e -> coefficient 64 e + L (re), 64 (e + 8) + L (im)
@@ -67,24 +67,16 @@ __device__ __forceinline__ int ms2048(u64 x) { return (int)((((x >> 52) + 1) >> 
 __device__ __forceinline__ u32 decomp_state(u64 x) { return ((u32)(x >> 32) + 1024u) >> 11; }
 // bmask = 1 below the top level, 0 at the top level
 // (W & 127) - 63 - b = st - (W & ~127): the digit is the old state minus the new one shifted back
-// FFT_DIG_MAD 1 (default since round 5): the digit as st - 128 st' in one v_mad_i32_i24 (st < 2^22, st' < 2^15 fit the
-// 24-bit operands): 4 VALU per digit instead of 5 (hipcc turns the multiply into a shift + subtract, hence the asm;
-// -128 is not a VOP3 inline constant on gfx9, so it rides in an SGPR)
-#ifndef FFT_DIG_MAD
-#define FFT_DIG_MAD 1
-#endif
+// The digit as st - 128 st' in one v_mad_i32_i24 (st < 2^22, st' < 2^15 fit the 24-bit operands): 4 VALU per digit
+// instead of the 5 of st - (W & ~127) (round 5; hipcc turns the multiply into a shift + subtract, hence the asm; -128 is
+// not a VOP3 inline constant on gfx9, so it rides in an SGPR)
 __device__ __forceinline__ int decomp_step(u32& st, u32 bmask) {
   const u32 b = __builtin_amdgcn_ubfe(st, 13, bmask);
   const u32 W = st + 63u + b;
-#if FFT_DIG_MAD
   const u32 stn = W >> 7;
   int d;
   asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(d) : "v"(stn), "s"(-128), "v"(st));
   st = stn;
-#else
-  const int d = (int)(st - (W & ~127u));  // 5 VALU per digit with the bfe, add3 and shift
-  st = W >> 7;
-#endif
   return d;
 }
 // decomp_state of the complement: for S = ~x the high word is h = ~hi(x), and ~h + 1024 = 1023 - h (mod 2^32)
@@ -119,17 +111,10 @@ __device__ __forceinline__ void mac_next(double& re, double& im, double dr, doub
 }
 
 // ---------------------------------------------------------------------------------------------
-// BSK conversion: one wavefront per polynomial; [i][r][j] order kept, 512 complex natural, x 2^-9 (x 2^-41 with
-// FFT_Y32: the blind rotations then update their accumulators from y = x 2^-32, fft512.h torus_acc_add_y)
-#ifndef FFT_Y32
-#define FFT_Y32 1
-#endif
-constexpr double BSK_SCALE = FFT_Y32 ? 0x1p-41 : 0x1p-9;
-#if FFT_Y32
-#define ACC_ADD torus_acc_add_y
-#else
-#define ACC_ADD torus_acc_add
-#endif
+// BSK conversion: one wavefront per polynomial; [i][r][j] order kept, 512 complex natural, x 2^-41 (2^-9 for the
+// transform's scale, 2^-32 so that the blind rotations update their accumulators from y = x 2^-32, fft512.h
+// torus_acc_add_y; round 5)
+constexpr double BSK_SCALE = 0x1p-41;
 __global__ __launch_bounds__(64) void bsk_to_fourier_kernel(const u64* __restrict__ bsk_std,
                                                             double2* __restrict__ bsk_f,
                                                             const double2* __restrict__ tw) {
@@ -184,23 +169,17 @@ __global__ __launch_bounds__(64) void fft_inv_kernel(const double2* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
-// FFT_PRIO: the waves' base priority (what FFT_MACPRIO drops back to after each MAC phase).
-//   3 (default since round 6): the workgroups with bit 8 of blockIdx set -- on 256 CUs the second workgroup each CU
-//     receives, then every other dispatch half-round -- at base priority 1.  The hardware arbitrates oldest-first, so
-//     of the two workgroups that share a CU the older always ran ahead: in a 4096 launch one slot of every CU
-//     finished its four workgroups 2.4 ms before the other and idled (profiles/r06d_wgt_4096.json, per-workgroup
-//     s_memrealtime stamps, tools/wg_timeline.py).  With the alternation the two slots end 0.33 ms apart and the
-//     CU-slot busy fraction rises 0.945 -> 0.980: 24.04 -> 23.04 ms per 4096, C2 6.45 -> 6.24 ms (same box, three
-//     boxes; profiles/r06e_ab_prio.txt).  Round 4 had measured this scheme "neutral" -- with a C-level branch around
-//     s_setprio that made hipcc spill (below).
-//   1: s_setprio 1 for waves 4-7 of an 8-wave workgroup (round 1; no effect on the 4-wave CTS = 2 workgroup)
-//   4 / 5: A/B forms (the last FFT_TAILWG workgroups high; bit 8 xor bit 9)
-#ifndef FFT_PRIO
-#define FFT_PRIO 3
-#endif
+// The waves' base priority (what each level step drops back to after its MAC phase): the workgroups of the odd dispatch
+// half-rounds -- on 256 CUs bit 8 of blockIdx: the second workgroup each CU receives, then every other half-round -- run at
+// base priority 1.  The hardware arbitrates oldest-first, so of the two workgroups that share a CU the older always ran
+// ahead: in a 4096 launch one slot of every CU finished its four workgroups 2.4 ms before the other and idled
+// (profiles/r06d_wgt_4096.json, per-workgroup s_memrealtime stamps, tools/wg_timeline.py).  With the alternation the two
+// slots end 0.33 ms apart and the CU-slot busy fraction rises 0.945 -> 0.980: 24.04 -> 23.04 ms per 4096, C2 6.45 -> 6.24
+// ms (same box, three boxes; profiles/r06e_ab_prio.txt).  Round 4 had measured this scheme "neutral" -- with a
+// C-level branch around s_setprio that made hipcc spill (base_prio below).
 // The dispatch half-round of a workgroup on a part with `cus` compute units and two workgroups per CU: 0 = the first
-// workgroup each CU receives, 1 = the second, 2, 3 = the next round's.  FFT_PRIO 3 raises the odd half-rounds,
-// FFT_STAGGER delays half-round 1.  One division per workgroup, outside the CMUX loop.
+// workgroup each CU receives, 1 = the second, 2, 3 = the next round's.  The base priority raises the odd half-rounds,
+// the start-up stagger delays half-round 1.  One division per workgroup, outside the CMUX loop.
 constexpr unsigned dispatch_half(unsigned wg, unsigned cus) { return wg / cus; }
 constexpr bool wg_prio_hi(unsigned wg, unsigned cus) { return dispatch_half(wg, cus) & 1u; }
 constexpr bool wg_staggered(unsigned wg, unsigned cus) { return dispatch_half(wg, cus) == 1u; }
@@ -219,12 +198,12 @@ static_assert(!wg_staggered(303, 304) && wg_staggered(304, 304) && wg_staggered(
 }  // namespace dh_check
 
 // Component-pair batch kernel (round 3, the default above the latency range): workgroup = CTS ciphertexts x 2
-// waves (CTS = 2 by default, 4 in round 3), wave (p, c) owns COMPONENT c of ciphertext p.  Per CMUX i:
+// waves, wave (p, c) owns COMPONENT c of ciphertext p.  Per CMUX i:
 //   rotate + decompose acc_c (wave-local: the wave's own transpose area holds the rotation image)
 //   level steps q = 0, 1, 2 (least significant first): digits -> twist -> DFT -> MAC into BOTH outputs'
 //     partial sums  O_j^c = fma chain over q of D_(c,q) (.) BSK_i[(c, q)][j]      (j = 0, 1)
-//     one step's chunk = rows (0, q) and (1, q) of BSK_i (32 KB), streamed once per workgroup by
-//     global_load_lds (CTS = 4: double-buffered; CTS = 2: one buffer, loaded at the step's start)
+//     one step's chunk = rows (0, q) and (1, q) of BSK_i (32 KB), streamed once per workgroup by LDS DMA into
+//     one buffer, loaded at the step's start
 //   exchange: wave c publishes O_(1-c)^c in its transpose area and takes O_c^(1-c) from its partner's:
 //     O_c = O_c^c + O_c^(1-c)  (= O_c^0 + O_c^1: f64 addition commutes, the oracle's split order)
 //   ONE inverse transform: acc_c += rint(iFFT(O_c)) mod 2^64
@@ -232,117 +211,31 @@ static_assert(!wg_staggered(303, 304) && wg_staggered(304, 304) && wg_staggered(
 // ciphertext, half of them per wave, 1/2 the accumulator / partial-sum registers per wave, and twice the waves
 // per ciphertext -- a batch of 1024 fills all 256 CUs at 2 waves / SIMD.
 // The MAC order (per-component chains, then one add) is restated in oracle/fft_oracle.c.
-// LDS at CTS = 4: 8 x 9 KB transpose areas | 2 x 32 KB level steps | pass A, B, B' tables (24 KB) = 160 KB;
-// at CTS = 2: B' table (8 KB) | one 32 KB level step | 4 x 9 KB transpose areas = 76 KB, two workgroups per CU.
-// FFT_ROT_BATCH: the rotation's 16 image reads issued together before their first use (measured with the
-// first level peeled: 27.04 -> 27.55 ms per 4096, slower; kept for A/B runs)
-#ifndef FFT_ROT_BATCH
-#define FFT_ROT_BATCH 0
-#endif
-// FFT_PAIR_TWREG: pass A's twiddles held in registers across the CMUX loop (the round-2 ablation: -4 %)
-#ifndef FFT_PAIR_TWREG
-#define FFT_PAIR_TWREG 2
-#endif
 constexpr int STEP_C64 = 4 * M;                    // rows (0, q), (1, q), j = 0, 1
-// CTS = ciphertexts per workgroup.  2 (default since round 4): 4 waves, TWO independent workgroups per CU (76 KB
-// each: only the inverse's TW_I table in LDS, passes A / B from registers, one level-step buffer), so the two
-// workgroups drift apart and one's LDS phases overlap the other's VALU phases on every SIMD: 27.01 -> 26.63 ms per
-// 4096 on the same box (profiles/r04a_cts_ab.txt, two rounds).  4 (FFT_PAIR_CTS=4): 8 waves, one workgroup per CU,
-// all tables in LDS, level steps double-buffered (the round-3 kernel).
-// FFT_PAIR_LDSTW: the round-3 layout (all tables in LDS, level steps double-buffered) for CTS = 4; 0 (round 6 A/B):
-// CTS = 4 with the CTS = 2 program (passes A / B in registers, one level-step buffer): 8 waves, one workgroup per CU
-#ifndef FFT_PAIR_LDSTW
-#define FFT_PAIR_LDSTW 1
-#endif
-template <int CTS, bool LDS_TW = (CTS == 4 && FFT_PAIR_LDSTW)>
-struct FpShared {
-  double2 tw[3 * M];                               // TW_A | TW_B | TW_I of the global table (no twist table)
-  double2 T[2 * CTS][T_C64];                       // after the tables: T - 8 KB is still inside the block
-  double2 K[2][STEP_C64];
-};
-// FFT_CT_AHEAD, FFT_DMA_IMM (round 9; 0 = the parent's code each): how the LWE mask word and the level-step
-// chunk reach the wave.
-//   FFT_CT_AHEAD: the mask word of CMUX i + 1 is loaded during CMUX i (after the rotation, ahead of level step 0's
-//     chunk) and becomes the scalar ms2048 value behind the vmcnt(0) of level step 0's glds_barrier, so no CMUX opens
-//     with a global load and a full wait.  Only the word's high half is loaded (ms2048 reads bits 52..63).  Row n + 1
-//     words long: CMUX n - 1 prefetches the body word and ignores it.
-//   FFT_DMA_IMM: the eight 1 KB pieces a wave loads per level step are contiguous in the BSK row and in the chunk, so
-//     pieces 1..3 and 5..7 ride on the instruction's immediate offset (it advances the buffer address AND the LDS
-//     address): two M0 values and two soffsets per wave and level step instead of eight of each.
-// Measured and not shipped: the level-step buffer as a __shared__ object of its own and its pieces issued from asm
-// statements that hipcc's wait bookkeeping does not see (tools/ab_patches/r09_k_own_dma_asm.patch); the pieces of level
-// steps 0 and 2 issued one per iteration of the digit loop (tools/ab_patches/r09_dma_spread.patch).
-#ifndef FFT_CT_AHEAD
-#define FFT_CT_AHEAD 1
-#endif
-#ifndef FFT_DMA_IMM
-#define FFT_DMA_IMM 1
-#endif
+// CTS = ciphertexts per workgroup, 2 since round 4: 4 waves, TWO independent workgroups per CU (76 KB of LDS each: the
+// inverse's TW_I table 8 KB | one 32 KB level step | 4 x 9 KB transpose areas; passes A / B come from registers), so the
+// two workgroups drift apart and one's LDS phases overlap the other's VALU phases on every SIMD: 27.01 -> 26.63 ms per
+// 4096 on the same box against round 3's 8 waves with all tables in LDS and double-buffered level steps
+// (profiles/r04a_cts_ab.txt, two rounds).  Holding pass A's and pass B's twiddles in registers across the CMUX loop is
+// the round-2 ablation's -4 %.
 template <int CTS>
-struct FpShared<CTS, false> {
+struct FpShared {
   double2 twI[M];                                  // TW_I only (passes A, B: registers, loaded from global)
   double2 K[1][STEP_C64];
   double2 T[2 * CTS][T_C64];
 };
-#ifndef FFT_PAIR_CTS
-#define FFT_PAIR_CTS 2
-#endif
-// FFT_MACPRIO 1 (default since late round 4): each level step's MAC runs at the top wave priority (back to 0
-// when the next step starts and after the last), so the short MAC phase of one workgroup is not stalled behind
-// the other workgroup's transforms on the same SIMD: 26.62 -> 25.26 ms per 4096 on the same box, 152.2k ->
-// 160.4k PBS/s (profiles/r04k_pgate_macprio_ab.txt)
-#ifndef FFT_MACPRIO
-#define FFT_MACPRIO 1
-#endif
-#ifndef FFT_STAGGER
-#define FFT_STAGGER 1
-#endif
-#ifndef FFT_TAILWG
-#define FFT_TAILWG 256
-#endif
-#ifndef FFT_PRIO_SH
-#define FFT_PRIO_SH 0
-#endif
-#ifndef FFT_ROTPRIO
-#define FFT_ROTPRIO 0
-#endif
-#ifndef FFT_XCHPRIO
-#define FFT_XCHPRIO 0
-#endif
-// FFT_MAC_PIPE (round 7; 0 = the parent's loop): the key words of level steps q = 1 and q = 2 software-pipelined, this
-// many slots ahead.  hipcc's own schedule reads one slot's two words into the same registers eight times per level and
-// waits for each pair (eight exposed LDS round trips per level, at the MAC's raised priority and right before a
-// workgroup barrier); q = 0 already has all sixteen reads in flight (its partial sums are not live yet).  One slot ahead
-// at q = 1 and two at q = 2 (FFT_MAC_PIPE_Q2: the 16 decomposition states are dead there) is what 256 VGPRs hold: 255
-// used, none spilled; 2 / 3 spills one register, 2 / 2 five.  Measured alone 22.90 -> 22.73 ms per 4096-PBS blind
-// rotation, and 0.29 ms of the round-7 default's gain when taken out of it (same box, three interleaved rounds each,
-// profiles/r07b_ab_steps.txt).
-#ifndef FFT_MAC_PIPE
-#define FFT_MAC_PIPE 1
-#endif
-#ifndef FFT_MAC_PIPE_Q2
-#define FFT_MAC_PIPE_Q2 (FFT_MAC_PIPE ? 2 : 0)
-#endif
 typedef __attribute__((address_space(3))) u64 lds_u64;
 
-// FFT_ROT_UNIFORM 1 (default since round 5): the rotation split so that every per-slot decision is wave-uniform.
+// (X^a v - v), v = this wave's polynomial (slot e <-> coefficient 64 e + L), to decomposition states.  The rotation
+// image is the wave's transpose area, and the rotation is split so that every per-slot decision is wave-uniform (round 5).
 // a (uniform) = 1024 s + 64 A + r.  The image written is W = X^r v (lane part: each lane writes at +r, only slot 15
 // of the lanes L + r >= 64 wraps, negated, to the image start); the reads take (X^(64 A) W)[L + 64 e] = W[L + 64 (e -
 // A)] for e >= A and -W[L + 64 (e - A + 16)] for e < A, so slot e's base (two per-lane bases 8 KB apart) and sign
-// (xor s) depend only on the SGPR comparison e < A.  Per slot 8 VALU instead of 10 (no compare, no negate-and-select:
-// y = (x ^ M) - (v + M), M = 0 or all ones); the values are the same, so no operation order changes.  Since round 8 the
-// difference is taken as the complement of a sum, 7 VALU per slot (below).
-#ifndef FFT_ROT_UNIFORM
-#define FFT_ROT_UNIFORM 1
-#endif
-// (X^a v - v), v = this wave's polynomial (slot e <-> coefficient 64 e + L), to decomposition states.  The
-// rotation image is the wave's transpose area.  Coefficient 64 e + L reads image entry (u + 64 e) mod 1024 with
-// u = (L - a) mod 1024, negated iff the negacyclic source index (L - a + 64 e) mod 2048 lies in [1024, 2048):
-// reads before the per-lane wrap use base u and DS offset 512 e, wrapped reads the base 8 KB lower (one compare
-// and one select per slot instead of the index arithmetic; the sign mask is an SGPR xor).
+// (xor s) depend only on the SGPR comparison e < A.  Per slot 8 VALU instead of the 10 of a per-lane compare and
+// negate-and-select (y = (x ^ M) - (v + M), M = 0 or all ones); the values are the same, so no operation order changes.
+// Since round 8 the difference is taken as the complement of a sum, 7 VALU per slot (below).
 __device__ __forceinline__ void rotate_states(const u64 (&v)[16], int a, int lane, double2* T, u32 (&st)[16]) {
   u64* Tu = (u64*)T;
-#if FFT_ROT_UNIFORM
   a = __builtin_amdgcn_readfirstlane(a);  // ms2048(ct[i]): the same for every lane
   const int A = (a >> 6) & 15, r = a & 63;
   const bool sgn = a >= 1024;
@@ -376,50 +269,14 @@ __device__ __forceinline__ void rotate_states(const u64 (&v)[16], int a, int lan
     st[e] = decomp_state_not(~(x ^ M) + (v[e] + M));
   }
   lds_order();
-#else
-#pragma unroll
-  for (int e = 0; e < 16; e++) Tu[64 * e + lane] = v[e];
-  lds_order();
-  const int t0 = (lane - a) & 2047;        // a < 2048
-  const int u = t0 & 1023;
-  const bool neg0 = t0 >= 1024;
-  const u32 a0 = (u32)(uintptr_t)(lds_u64*)&Tu[u];
-  const u32 a1 = a0 - 8192u;
-#if FFT_ROT_BATCH
-  u64 x[16];
-#pragma unroll
-  for (int e = 0; e < 16; e++) {
-    const bool wrap = u >= 1024 - 64 * e;
-    x[e] = ((const lds_u64*)(uintptr_t)(wrap ? a1 : a0))[64 * e];
-  }
-  __builtin_amdgcn_sched_barrier(0);  // all 16 reads in flight before the first use
-#pragma unroll
-  for (int e = 0; e < 16; e++) {
-    const bool neg = neg0 != (u >= 1024 - 64 * e);
-    const u64 r = neg ? 0 - x[e] : x[e];
-    st[e] = decomp_state(r - v[e]);
-  }
-#else
-#pragma unroll
-  for (int e = 0; e < 16; e++) {
-    const bool wrap = u >= 1024 - 64 * e;
-    const u32 base = wrap ? a1 : a0;
-    const u64 x = ((const lds_u64*)(uintptr_t)base)[64 * e];
-    const bool neg = neg0 != wrap;
-    const u64 r = neg ? 0 - x : x;
-    st[e] = decomp_state(r - v[e]);
-  }
-#endif
-  lds_order();
-#endif
 }
 
 // the partial-sum exchange of wave c (compile-time): publish O_(1-c)^c in this wave's area, add O_c^(1-c) from
 // the partner's (two workgroup barriers)
-// GROUP (round 7, the pair kernel with FFT_XPOSE_OVERLAP): the eight reads of the partner's area pinned as one group
-// (the published half of the partial sums has just died, so their registers are free) and added under counted waits;
-// hipcc's own schedule for C = 1 reads two, waits, adds, four times over
-template <int C, bool GROUP = false>
+// The eight reads of the partner's area are pinned as one group (round 7: the published half of the partial sums has
+// just died, so their registers are free) and added under counted waits; hipcc's own schedule for C = 1 reads two, waits,
+// adds, four times over
+template <int C>
 __device__ __forceinline__ void exchange_partials(const double (&o0r)[8], const double (&o0i)[8], const double (&o1r)[8],
                                                   const double (&o1i)[8], double (&xr)[8], double (&xi)[8], double2* T,
                                                   const double2* Tp, int lane) {
@@ -430,61 +287,29 @@ __device__ __forceinline__ void exchange_partials(const double (&o0r)[8], const 
     xi[e] = C ? o1i[e] : o0i[e];
   }
   __syncthreads();
-  if constexpr (GROUP) {
-    double2 w[8];
-    __builtin_amdgcn_sched_barrier(0);
+  double2 w[8];
+  __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int e = 0; e < 8; e++) w[e] = Tp[64 * e + lane];
-    __builtin_amdgcn_sched_barrier(0);
+  for (int e = 0; e < 8; e++) w[e] = Tp[64 * e + lane];
+  __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int e = 0; e < 8; e++) {
-      xr[e] = xr[e] + w[e].x;
-      xi[e] = xi[e] + w[e].y;
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      const double2 w = Tp[64 * e + lane];
-      xr[e] = xr[e] + w.x;
-      xi[e] = xi[e] + w.y;
-    }
+  for (int e = 0; e < 8; e++) {
+    xr[e] = xr[e] + w[e].x;
+    xi[e] = xi[e] + w[e].y;
   }
   __syncthreads();  // the partner has read this wave's area before the inverse overwrites it
 }
 
-// level step g = 3 i + q: 32 KB in 1 KB blocks; wave w of NW loads blocks (32 / NW) w .. (16 per component row)
-template <int NW>
-__device__ __forceinline__ void load_step(const double2* __restrict__ bsk, int g, double2* dst, int wave_s, int lane) {
-  const int i = g / 3, q = g - 3 * (g / 3);
-#pragma unroll
-  for (int u = 0; u < 32 / NW; u++) {
-    const int blk = wave_s * (32 / NW) + u;
-    const int c = blk >> 4;
-    const char* src = (const char*)(bsk + ((size_t)i * 6 + c * 3 + q) * (2 * M)) + (blk & 15) * 1024;
-    __builtin_amdgcn_global_load_lds((const void*)(src + lane * 16),
-                                     (__attribute__((address_space(3))) void*)((char*)dst + blk * 1024), 16, 0, 0);
-  }
-}
-// FFT_BUF_LDS 1 (default since round 5): the same level-step chunk through buffer_load_dwordx4 ... lds with the BSK as a
-// buffer resource: the per-load byte offset is an SGPR (soffset) and the lane offset one loop-invariant VGPR, so the
-// 24 loads of a CMUX cost no VALU (the global_load_lds form needs a 64-bit VALU address add per load)
-#ifndef FFT_BUF_LDS
-#define FFT_BUF_LDS 1
-#endif
-template <int NW>
-__device__ __forceinline__ void load_step_buf(__amdgpu_buffer_rsrc_t bsr, int g, double2* dst, int wave_s, int voff) {
-  const int i = g / 3, q = g - 3 * (g / 3);
-#pragma unroll
-  for (int u = 0; u < 32 / NW; u++) {
-    const int blk = wave_s * (32 / NW) + u;
-    const int c = blk >> 4;
-    const int soff = ((i * 6 + c * 3 + q) * (2 * M)) * (int)sizeof(double2) + (blk & 15) * 1024;  // < 2^31: BSK < 2 GB
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(bsr, (__attribute__((address_space(3))) void*)((char*)dst + blk * 1024),
-                                             16, voff, soff, 0, 0);
-  }
-}
-// FFT_DMA_IMM: the wave's 32 / NW blocks in groups of four consecutive ones (NW = 4: one component row, 8 KB in a row,
-// in the BSK and in the chunk), pieces 1..3 of a group on the immediate offset
+// Level step g = 3 i + q: 32 KB in 1 KB blocks; wave w of NW loads blocks (32 / NW) w .. (16 per component row) through
+// buffer_load_dwordx4 ... lds with the BSK as a buffer resource: the per-load byte offset is an SGPR (soffset) and the
+// lane offset one loop-invariant VGPR, so the 24 loads of a CMUX cost no VALU (round 5; global_load_lds needs a 64-bit
+// VALU address add per load).  The wave's blocks go in groups of four consecutive ones (NW = 4: one component row, 8 KB
+// in a row, in the BSK and in the chunk), pieces 1..3 of a group on the instruction's immediate offset, which advances
+// the buffer address AND the LDS address: two M0 values and two soffsets per wave and level step instead of eight of
+// each (round 9).  Measured and not shipped: the level-step buffer as a __shared__ object of its own and its
+// pieces issued from asm statements that hipcc's wait bookkeeping does not see
+// (tools/ab_patches/r09_k_own_dma_asm.patch); the pieces of level steps 0 and 2 issued one per iteration of the digit
+// loop (tools/ab_patches/r09_dma_spread.patch).
 template <int NW>
 __device__ __forceinline__ void load_step_buf4(__amdgpu_buffer_rsrc_t bsr, int g, double2* dst, int wave_s, int voff) {
   static_assert((32 / NW) % 4 == 0 && 16 % (32 / NW) == 0, "groups of four blocks inside one component row");
@@ -525,7 +350,6 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
     int n_lut, const double2* __restrict__ bsk, const double2* __restrict__ tw_g, u64* __restrict__ out_big,
     u64* __restrict__ out_acc, int n_cus) {
   constexpr int NW = 2 * CTS;
-  constexpr bool LDS_TW = CTS == 4 && FFT_PAIR_LDSTW;
   __shared__ __attribute__((aligned(16))) FpShared<CTS> sh;
 #if FFT_WGTIME
   const unsigned long long wg_t0 = __builtin_amdgcn_s_memrealtime();
@@ -540,20 +364,12 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
   const double2* Tp = sh.T[wave ^ 1];
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
   const int c_s = wave_s & 1;
-  const int n_steps = 3 * n;
 
-#if FFT_BUF_LDS
   // the BSK as a raw buffer (num_records = its byte size; gfx9 dword 3 = 0x00020000, as composable_kernel uses on gfx9)
   const __amdgpu_buffer_rsrc_t bsr =
       __builtin_amdgcn_make_buffer_rsrc((void*)bsk, (short)0, n * 6 * 2 * M * (int)sizeof(double2), 0x00020000);
   const int voff = lane * 16;
-#endif
-  if constexpr (LDS_TW) {
-    for (int q = threadIdx.x; q < 3 * M; q += 64 * NW) sh.tw[q] = tw_g[TW_A + q];
-    load_step<NW>(bsk, 0, sh.K[0], wave_s, lane);
-  } else {
-    for (int q = threadIdx.x; q < M; q += 64 * NW) sh.twI[q] = tw_g[TW_I + q];
-  }
+  for (int q = threadIdx.x; q < M; q += 64 * NW) sh.twI[q] = tw_g[TW_I + q];
 
   // acc_c: A = 0, B = X^{-b~} * lut (LUT values in the Z_p encoding, mapped to the torus first)
   u64 acc[16];
@@ -575,137 +391,71 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
 
   const TBase tb(lane);
   const double2* twA = tw_g + TW_A;
-  const double2* twI;
-  if constexpr (LDS_TW) {
-    twA = sh.tw;
-    twI = sh.tw + 2 * M;
-  } else {
-    twI = sh.twI;
-  }
+  const double2* twI = sh.twI;
   const double2* twB = twA + M;
-#if FFT_PAIR_TWREG
   double2 wa[8];  // pass A's twiddles (twist merged) for the whole CMUX loop: 8 LDS reads fewer per transform
   __syncthreads();
 #pragma unroll
   for (int e = 0; e < 8; e++) wa[e] = twA[64 * e + lane];
-#endif
-#if FFT_PAIR_TWREG >= 2
   double2 wb[8];  // and pass B's (the inverse's pass C' conjugates the same table): 7 more per forward, 7 per inverse
 #pragma unroll
   for (int e = 1; e < 8; e++) wb[e] = twB[64 * e + lane];
   wb[0] = make_double2(1.0, 0.0);
-#endif
-  // the wave's base priority (FFT_PRIO), also what FFT_MACPRIO drops back to after each MAC phase
-#if FFT_PRIO == 1
-  const bool prio_hi = NW > 4 && wave_s >= 4;  // the 4-wave CTS = 2 workgroup has no second wave per SIMD
-#elif FFT_PRIO == 3
-  // with two workgroups per CU, one of them (by dispatch half-round) at the higher priority: bit 8 of the
-  // workgroup index on a 256-CU part (MI355X), the same half-rounds on any other CU count
+  // the wave's base priority, also what each level step drops back to after its MAC phase: with two workgroups per
+  // CU, one of them (by dispatch half-round) at the higher priority: bit 8 of the workgroup index on a 256-CU part
+  // (MI355X), the same half-rounds on any other CU count
   const bool prio_hi = wg_prio_hi(blockIdx.x, (unsigned)n_cus);
-#elif FFT_PRIO == 6
-  [[maybe_unused]] constexpr bool prio_hi = false;  // the per-CMUX alternation below
-#elif FFT_PRIO == 5
-  // A/B: bit 8 xor bit 9 of the workgroup index (the alternation flips every other dispatch round)
-  const bool prio_hi = ((blockIdx.x >> 8) ^ (blockIdx.x >> 9)) & 1;
-#elif FFT_PRIO == 4
-  // A/B (round 6): the workgroups of the final dispatch half-round (the last FFT_TAILWG of the grid; on 256 CUs these
-  // take the slot of each CU that frees last) at the higher base priority, against the hardware's oldest-first
-  // arbitration, so the two final workgroups of a CU end closer together (profiles/r06d_wgt_*: without it one slot
-  // of every CU idles ~2.4 ms at the end of a 4096 launch)
-  const bool prio_hi = blockIdx.x + FFT_TAILWG >= gridDim.x;
-#else
-  constexpr bool prio_hi = false;
-#endif
-#if FFT_PRIO == 1 || FFT_PRIO == 0
-  auto base_prio = [&]() {
-    if (prio_hi) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(0);
-  };
-#else
   // a runtime (wave-uniform) priority as ONE asm block with its own scalar branch: a C-level branch around the two
   // s_setprio forms splits every level step into basic blocks and hipcc then spills ~195 VGPRs (measured 71 ms)
-#if FFT_PRIO == 6
-  // A/B (round 6): the base priority alternates every 2^FFT_PRIO_SH CMUXes, in opposite phase for the two dispatch
-  // halves (blockIdx bit 8), so the two workgroups of a CU take turns instead of the older one always winning
-  const unsigned prio_ph = __builtin_amdgcn_readfirstlane((blockIdx.x >> 8) & 1);
-  unsigned prio_flag = prio_ph;
-#else
   const unsigned prio_flag = __builtin_amdgcn_readfirstlane(prio_hi ? 1u : 0u);
-#endif
   auto base_prio = [&]() {
     asm volatile(
         "s_cmp_lg_u32 %0, 0\n\ts_cbranch_scc0 .Lbp0_%=\n\ts_setprio 1\n\ts_branch .Lbp1_%=\n"
         ".Lbp0_%=:\n\ts_setprio 0\n.Lbp1_%=:" ::"s"(prio_flag) : "scc");
   };
-#endif
   base_prio();
-#if FFT_STAGGER
-  // round 6 (default 1): the second workgroup of each CU in the first dispatch round (dispatch half-round 1) starts
-  // FFT_STAGGER x ~3.4 us late, so the two workgroups of a CU do not run their phases in lockstep from the start
-  // (with FFT_PRIO 3: 23.04 -> 22.97 ms per 4096, C2 6.24 -> 6.19 ms; alone 24.04 -> 23.87 ms; 2 and 4 x 3.4 us: neutral)
-  if (wg_staggered(blockIdx.x, (unsigned)n_cus))
-    for (int k = 0; k < FFT_STAGGER; k++) __builtin_amdgcn_s_sleep(127);
-#endif
+  // round 6: the second workgroup of each CU in the first dispatch round (dispatch half-round 1) starts ~3.4 us late,
+  // so the two workgroups of a CU do not run their phases in lockstep from the start (on top of the base priority: 23.04
+  // -> 22.97 ms per 4096, C2 6.24 -> 6.19 ms; alone 24.04 -> 23.87 ms; 2 and 4 x 3.4 us: neutral)
+  if (wg_staggered(blockIdx.x, (unsigned)n_cus)) __builtin_amdgcn_s_sleep(127);
 #if FFT_DMASTAMP
   unsigned long long dma_cyc[3] = {0, 0, 0};
   const unsigned long long loop_t0 = __builtin_amdgcn_s_memtime();
 #endif
-#if FFT_CT_AHEAD
-  // ms2048 from a word's high half (bits 52..63 are all it reads); the high halves of the row
+  // The mask word of CMUX i + 1 is loaded during CMUX i (after the rotation, ahead of level step 0's chunk) and becomes
+  // the scalar ms2048 value behind the vmcnt(0) of level step 0's glds_barrier, so no CMUX opens with a global load and a
+  // full wait (round 9).  Only the word's high half is loaded (ms2048 reads bits 52..63); the row is n + 1
+  // words long, so CMUX n - 1 prefetches the body word and ignores it.
+  // ms2048 from a word's high half; the high halves of the row
   auto ms2048_hi = [](u32 hi) { return (int)((((hi >> 20) + 1u) >> 1) & 2047u); };
   const u32* ct_hi = (const u32*)ct + 1;
   int a_s = __builtin_amdgcn_readfirstlane(ms2048_hi(ct_hi[0]));
-#endif
   for (int i = 0; i < n; i++) {
-#if FFT_PRIO == 6
-    prio_flag = ((unsigned)i >> FFT_PRIO_SH ^ prio_ph) & 1u;
-    base_prio();
-#endif
     // (X^a acc_c - acc_c), decomposed: the rotation image in this wave's own transpose area (its previous
     // user, the last inverse, is this wave: DS operations of a wave run in order)
     u32 st[16];
-#if FFT_ROTPRIO
-    __builtin_amdgcn_s_setprio(FFT_ROTPRIO);  // A/B: the rotation phase at a raised priority
-#endif
-#if FFT_CT_AHEAD
     rotate_states(acc, a_s, lane, T, st);
     // the next CMUX's mask word (i = n - 1: the body word, ignored), issued ahead of level step 0's chunk and
     // consumed behind that step's glds_barrier
     u32 ct_next = ct_hi[2 * (size_t)(i + 1)];
-#else
-    rotate_states(acc, ms2048(ct[i]), lane, T, st);
-#endif
     double o0r[8], o0i[8], o1r[8], o1i[8];
     // level steps q = 0, 1, 2 (least significant first), each specialised at compile time: q = 0 starts the two
     // fma chains with a multiply (no zeroed partial sums), q = 2 takes the top digit (no carry bit, no next state)
     auto level = [&](auto qc) {
       constexpr int q = decltype(qc)::value;
       const int g = 3 * i + q;
-#if FFT_MACPRIO
-      if (q > 0 || FFT_ROTPRIO) base_prio();
-#endif
-      if constexpr (LDS_TW) {
-        glds_barrier();  // step g's chunk is in K[g & 1]; every wave is done with K[(g + 1) & 1]
-        if (g + 1 < n_steps) load_step<NW>(bsk, g + 1, sh.K[(g + 1) & 1], wave_s, lane);
-      } else {
-        // one buffer: every wave is done with step g - 1's chunk (the exchange's barriers order q = 0)
-        if (q > 0) __syncthreads();
+      if (q > 0) base_prio();  // the previous step's MAC ran at the top priority (below)
+      // one buffer: every wave is done with step g - 1's chunk (the exchange's barriers order q = 0)
+      if (q > 0) __syncthreads();
 #if FFT_DMASTAMP
-        __builtin_amdgcn_sched_barrier(0);
-        const unsigned long long dma_t0 = __builtin_amdgcn_s_memtime();
+      __builtin_amdgcn_sched_barrier(0);
+      const unsigned long long dma_t0 = __builtin_amdgcn_s_memtime();
 #endif
-#if FFT_BUF_LDS && FFT_DMA_IMM
-        load_step_buf4<NW>(bsr, g, sh.K[0], wave_s, voff);
-#elif FFT_BUF_LDS
-        load_step_buf<NW>(bsr, g, sh.K[0], wave_s, voff);
-#else
-        load_step<NW>(bsk, g, sh.K[0], wave_s, lane);
-#endif
+      load_step_buf4<NW>(bsr, g, sh.K[0], wave_s, voff);
 #if FFT_DMASTAMP
-        dma_cyc[q] += __builtin_amdgcn_s_memtime() - dma_t0;
-        __builtin_amdgcn_sched_barrier(0);
+      dma_cyc[q] += __builtin_amdgcn_s_memtime() - dma_t0;
+      __builtin_amdgcn_sched_barrier(0);
 #endif
-      }
       double xr[8], xi[8];
 #pragma unroll
       for (int e = 0; e < 8; e++) {
@@ -718,33 +468,31 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
         }
       }
       // the slot twist rides in pass A's twisted DFT8 (twist_dft8_fwd)
-#if FFT_PAIR_TWREG >= 2 && (FFT_XPOSE_OVERLAP || FFT_XPOSE_NOWAIT)
-      dft512_fwd_rab_p<true>(xr, xi, T, lane, tb, wa, wb);
-#elif FFT_PAIR_TWREG >= 2
-      dft512_fwd_rab<true>(xr, xi, T, lane, tb, wa, wb);
-#elif FFT_PAIR_TWREG
-      dft512_fwd_ra<true>(xr, xi, T, lane, tb, wa, twB);
-#else
-      dft512_fwd_t<true, true>(xr, xi, T, lane, tb, twA, twB);
-#endif
-      if constexpr (!LDS_TW) glds_barrier();  // step g's chunk has landed
-#if FFT_CT_AHEAD
+      dft512_fwd_rab_p(xr, xi, T, lane, tb, wa, wb);
+      glds_barrier();  // step g's chunk has landed
       if constexpr (q == 0) {
         // behind the barrier's vmcnt(0) the prefetched word is back: from here it is the scalar a of the next CMUX
         asm volatile("" : "+v"(ct_next));
         a_s = ms2048_hi(__builtin_amdgcn_readfirstlane(ct_next));
       }
-#endif
-#if FFT_MACPRIO
-      __builtin_amdgcn_s_setprio(3);  // the short MAC ahead of the other workgroup's transforms
-#endif
-      const double2* k0 = sh.K[LDS_TW ? (g & 1) : 0] + c * (2 * M) + lane;
+      // Each level step's MAC runs at the top wave priority (back to the base priority when the next step starts and
+      // after the last), so the short MAC phase of one workgroup is not stalled behind the other workgroup's transforms
+      // on the same SIMD: 26.62 -> 25.26 ms per 4096 on the same box, 152.2k -> 160.4k PBS/s (late round 4,
+      // profiles/r04k_pgate_macprio_ab.txt)
+      __builtin_amdgcn_s_setprio(3);
+      const double2* k0 = sh.K[0] + c * (2 * M) + lane;
       const double2* k1 = k0 + M;
-#if FFT_MAC_PIPE
       if constexpr (q > 0) {
-        // a rotating window of D slots' key words ahead of the slot being consumed, the order pinned: the reads of
-        // slot e + D go out before slot e's eight fma, which wait (counted) for slot e's pair only
-        constexpr int D = q == 2 ? FFT_MAC_PIPE_Q2 : FFT_MAC_PIPE;
+        // The key words of level steps q = 1 and q = 2 software-pipelined (round 7): a rotating window of D slots' key
+        // words ahead of the slot being consumed, the order pinned: the reads of slot e + D go out before slot e's eight
+        // fma, which wait (counted) for slot e's pair only.  hipcc's own schedule reads one slot's two words into the
+        // same registers eight times per level and waits for each pair (eight exposed LDS round trips per level, at the
+        // MAC's raised priority and right before a workgroup barrier); q = 0 already has all sixteen reads in flight
+        // (its partial sums are not live yet).  One slot ahead at q = 1 and two at q = 2 (the 16 decomposition states
+        // are dead there) is what 256 VGPRs hold: 255 used, none spilled; 2 / 3 spills one register, 2 / 2 five.
+        // Measured alone 22.90 -> 22.73 ms per 4096-PBS blind rotation, and 0.29 ms of the round-7 default's gain when
+        // taken out of it (same box, three interleaved rounds each, profiles/r07b_ab_steps.txt).
+        constexpr int D = q == 2 ? 2 : 1;
         double2 ku[8], kv[8];
 #pragma unroll
         for (int e = 0; e < D; e++) {
@@ -764,7 +512,6 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
         }
         return;
       }
-#endif
 #pragma unroll
       for (int e = 0; e < 8; e++) {
         const double2 u = k0[64 * e], v = k1[64 * e];
@@ -780,28 +527,17 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
     level(std::integral_constant<int, 0>{});
     level(std::integral_constant<int, 1>{});
     level(std::integral_constant<int, 2>{});
-#if FFT_MACPRIO && !FFT_XCHPRIO
     base_prio();
-#endif
     // exchange the partial sums: publish O_(1-c)^c, take O_c^(1-c) (c wave-uniform: a scalar branch, no selects)
     double xr[8], xi[8];
-    if (c_s) exchange_partials<1, FFT_XPOSE_OVERLAP != 0>(o0r, o0i, o1r, o1i, xr, xi, T, Tp, lane);
-    else exchange_partials<0, FFT_XPOSE_OVERLAP != 0>(o0r, o0i, o1r, o1i, xr, xi, T, Tp, lane);
-#if FFT_MACPRIO && FFT_XCHPRIO
-    base_prio();  // A/B: the partial-sum exchange still at the MAC's priority
-#endif
-#if FFT_PAIR_TWREG >= 2 && (FFT_XPOSE_OVERLAP || FFT_XPOSE_NOWAIT)
+    if (c_s) exchange_partials<1>(o0r, o0i, o1r, o1i, xr, xi, T, Tp, lane);
+    else exchange_partials<0>(o0r, o0i, o1r, o1i, xr, xi, T, Tp, lane);
     dft512_inv_rb_p(xr, xi, T, lane, tb, wb, twI);
-#elif FFT_PAIR_TWREG >= 2
-    dft512_inv_rb(xr, xi, T, lane, tb, wb, twI);
-#else
-    dft512_inv_t(xr, xi, T, lane, tb, twB, twI);
-#endif
     twist_slots<true>(xr, xi);
 #pragma unroll
     for (int e = 0; e < 8; e++) {
-      acc[e] = ACC_ADD(acc[e], xr[e]);
-      acc[e + 8] = ACC_ADD(acc[e + 8], xi[e]);
+      acc[e] = torus_acc_add_y(acc[e], xr[e]);
+      acc[e + 8] = torus_acc_add_y(acc[e + 8], xi[e]);
     }
   }
 #if FFT_DMASTAMP
@@ -846,198 +582,6 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
 }
 
 // ---------------------------------------------------------------------------------------------
-// Three waves per SIMD (round 6, FFT_G3): ONE workgroup per CU of G3_CTS = 6 ciphertexts x 2 component waves (768
-// threads, <= 168 VGPRs).  The per-wave program is the pair kernel's -- rotate + decompose acc_c, three level steps
-// (digits, DFT, MAC into both outputs' partial sums), the partial-sum exchange, one inverse -- with the same
-// operation order (the oracle is unchanged), but
-//   * every twiddle comes from LDS (pass A and the inverse's pass B' from their 8 KB tables, pass B / C' from the
-//     1 KB compact table, fft512.h dft512_fwd_c), which frees the 60 registers the pair kernel keeps them in;
-//   * one 32 KB level-step chunk serves 6 ciphertexts instead of 2: a third of the LDS-DMA bytes and of the BSK
-//     stream per ciphertext;
-//   * the batch is spread over rounds of one workgroup per CU with the ciphertext counts balanced (4096 on 256 CUs:
-//     3 rounds, 16 ciphertexts per CU as 6 + 5 + 5) instead of a fixed 6 per workgroup (2.67 rounds).  Pairs beyond a
-//     workgroup's count skip all compute but keep the barrier sequence.
-// LDS: TW_A 8 KB | TW_I 8 KB | TW_B compact 1 KB | one 32 KB level step | 12 x 9 KB transpose areas = 160,768 B.
-#ifndef FFT_G3
-#define FFT_G3 0
-#endif
-#ifndef G3_TW_GLOBAL
-#define G3_TW_GLOBAL 0
-#endif
-constexpr int G3_CTS = 6;
-constexpr int G3_NW = 2 * G3_CTS;
-struct G3Shared {
-  double2 twA[M];
-  double2 twI[M];
-  double2 twB[64];                                 // [e][L & 7]
-  double2 K[STEP_C64];
-  double2 T[G3_NW][T_C64];
-};
-static_assert(sizeof(G3Shared) <= 163840, "G3 LDS");
-
-template <bool WRITE_ACC, bool WRITE_BIG>
-__global__ __launch_bounds__(64 * G3_NW, 1) void blind_rotate_fft_g3_kernel(
-    const u64* __restrict__ lwe_in, int n, size_t B, const u64* __restrict__ luts, const u32* __restrict__ lut_index,
-    int n_lut, const double2* __restrict__ bsk, const double2* __restrict__ tw_g, u64* __restrict__ out_big,
-    u64* __restrict__ out_acc) {
-  __shared__ __attribute__((aligned(16))) G3Shared sh;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int c = wave & 1;
-  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-  const int c_s = wave_s & 1;
-  // balanced split: workgroup w takes B / G or B / G + 1 ciphertexts (G = gridDim.x)
-  const size_t G = gridDim.x, w = blockIdx.x;
-  const size_t per = B / G, extra = B % G;
-  const size_t cnt = per + (w < extra ? 1 : 0);
-  const size_t b0 = w * per + (w < extra ? w : extra);
-  const int p = wave_s >> 1;
-  const bool live = (size_t)p < cnt;
-  const size_t b = live ? b0 + p : b0;
-  const u64* ct = lwe_in + b * (size_t)(n + 1);
-  double2* T = sh.T[wave];
-  const double2* Tp = sh.T[wave ^ 1];
-  const int n_steps = 3 * n;
-  (void)n_steps;
-
-  const __amdgpu_buffer_rsrc_t bsr =
-      __builtin_amdgcn_make_buffer_rsrc((void*)bsk, (short)0, n * 6 * 2 * M * (int)sizeof(double2), 0x00020000);
-  const int voff = lane * 16;
-  for (int q = threadIdx.x; q < M; q += 64 * G3_NW) {
-    sh.twA[q] = tw_g[TW_A + q];
-    sh.twI[q] = tw_g[TW_I + q];
-  }
-  if (threadIdx.x < 64) sh.twB[threadIdx.x] = tw_g[TW_B + 64 * (threadIdx.x >> 3) + (threadIdx.x & 7)];
-
-  u64 acc[16];
-  {
-    int li = lut_index ? (int)lut_index[b] : 0;
-    li = (li < 0 || li >= n_lut) ? 0 : li;
-    const u64* lut = luts + (size_t)li * N1K;
-    const int s = (2048 - ms2048(ct[n])) & 2047;
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-      int d = 64 * e + lane - s;
-      bool neg = false;
-      if (d < 0) { d += N1K; neg = !neg; }
-      if (d < 0) { d += N1K; neg = !neg; }
-      const u64 v = gl_to_torus(lut[d]);
-      acc[e] = c ? (neg ? 0 - v : v) : 0;
-    }
-  }
-  __syncthreads();
-  const TBase tb(lane);
-#if G3_TW_GLOBAL
-  // A/B: the twiddles straight from the global tables (L1 / L2 hits) instead of LDS
-  const double2* twAl = tw_g + TW_A + lane;
-  const double2* twIl = tw_g + TW_I + lane;
-  const double2* twBc = tw_g + TW_B + (lane & 7);  // the full table at stride 64
-  constexpr int BSTR = 64;
-#else
-  const double2* twAl = sh.twA + lane;
-  const double2* twIl = sh.twI + lane;
-  const double2* twBc = sh.twB + (lane & 7);
-  constexpr int BSTR = 8;
-#endif
-
-  for (int i = 0; i < n; i++) {
-    u32 st[16];
-    if (live) rotate_states(acc, ms2048(ct[i]), lane, T, st);
-    double o0r[8], o0i[8], o1r[8], o1i[8];
-    auto level = [&](auto qc) {
-      constexpr int q = decltype(qc)::value;
-      const int g = 3 * i + q;
-#if FFT_MACPRIO
-      if (q > 0) __builtin_amdgcn_s_setprio(0);
-#endif
-      if (q > 0) __syncthreads();  // every wave is done with step g - 1's chunk (the exchange's barriers order q = 0)
-      {
-        const int ii = g / 3;
-        for (int blk = wave_s; blk < 32; blk += G3_NW) {
-          const int cc = blk >> 4;
-          const int soff = ((ii * 6 + cc * 3 + q) * (2 * M)) * (int)sizeof(double2) + (blk & 15) * 1024;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(
-              bsr, (__attribute__((address_space(3))) void*)((char*)sh.K + blk * 1024), 16, voff, soff, 0, 0);
-        }
-      }
-      double xr[8], xi[8];
-      if (live) {
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-          if constexpr (q == 2) {
-            xr[e] = decomp_top(st[e]);
-            xi[e] = decomp_top(st[e + 8]);
-          } else {
-            xr[e] = (double)decomp_step(st[e], 1u);
-            xi[e] = (double)decomp_step(st[e + 8], 1u);
-          }
-        }
-        dft512_fwd_c<true, BSTR>(xr, xi, T, lane, tb, twAl, twBc);
-      }
-      glds_barrier();  // step g's chunk has landed
-      if (live) {
-#if FFT_MACPRIO
-        __builtin_amdgcn_s_setprio(3);
-#endif
-        const double2* k0 = sh.K + c * (2 * M) + lane;
-        const double2* k1 = k0 + M;
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-          const double2 u = k0[64 * e], v = k1[64 * e];
-          if constexpr (q == 0) {
-            mac_first(o0r[e], o0i[e], xr[e], xi[e], u);
-            mac_first(o1r[e], o1i[e], xr[e], xi[e], v);
-          } else {
-            mac_next(o0r[e], o0i[e], xr[e], xi[e], u);
-            mac_next(o1r[e], o1i[e], xr[e], xi[e], v);
-          }
-        }
-      }
-    };
-    level(std::integral_constant<int, 0>{});
-    level(std::integral_constant<int, 1>{});
-    level(std::integral_constant<int, 2>{});
-#if FFT_MACPRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-    double xr[8], xi[8];
-    if (live) {
-      if (c_s) exchange_partials<1>(o0r, o0i, o1r, o1i, xr, xi, T, Tp, lane);
-      else exchange_partials<0>(o0r, o0i, o1r, o1i, xr, xi, T, Tp, lane);
-      dft512_inv_c<BSTR>(xr, xi, T, lane, tb, twBc, twIl);
-      twist_slots<true>(xr, xi);
-#pragma unroll
-      for (int e = 0; e < 8; e++) {
-        acc[e] = ACC_ADD(acc[e], xr[e]);
-        acc[e + 8] = ACC_ADD(acc[e + 8], xi[e]);
-      }
-    } else {
-      __syncthreads();  // the exchange's two barriers
-      __syncthreads();
-    }
-  }
-
-  if (!live) return;
-  if (WRITE_ACC) {
-    u64* oa = out_acc + b * 2048 + c * N1K;
-#pragma unroll
-    for (int e = 0; e < 16; e++) oa[64 * e + lane] = acc[e];
-  }
-  if (WRITE_BIG) {
-    u64* ob = out_big + b * (size_t)(N1K + 1);
-    if (c == 0) {
-#pragma unroll
-      for (int e = 0; e < 16; e++) {
-        const int idx = 64 * e + lane;
-        if (idx == 0) ob[0] = acc[e];
-        else ob[N1K - idx] = 0 - acc[e];
-      }
-    } else if (lane == 0) {
-      ob[N1K] = acc[0];
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // Latency-mode blind rotation (small batches): ONE ciphertext per workgroup of 8 waves.  Per CMUX:
 //   A  waves 0..5: wave r = chain position (c, q) (c = r / 3; q = 0, 1, 2: levels least significant
 //      first) rotates + decomposes accumulator polynomial c, keeps step q's digits and transforms
@@ -1059,9 +603,6 @@ struct FftLatShared {
   unsigned short ab[FL_MAXN];  // ms2048(ct[i]) for every CMUX
 };
 
-#ifndef FFT_LAT_PREFETCH
-#define FFT_LAT_PREFETCH 1
-#endif
 __device__ __forceinline__ void lat_load_key(const double2* __restrict__ bsk, int i, int j, int s0, int lane,
                                              double2 (&kv)[6][2]) {
 #pragma unroll
@@ -1070,19 +611,12 @@ __device__ __forceinline__ void lat_load_key(const double2* __restrict__ bsk, in
     for (int t = 0; t < 2; t++) kv[r][t] = bsk[((size_t)(i * 6 + r) * 2 + j) * M + 64 * (s0 + t) + lane];
 }
 
-// FFT_LAT_LDSBAR 1 (round 6): the latency kernel's three barriers per CMUX wait for LDS only (s_waitcnt lgkmcnt(0) +
-// s_barrier).  Every cross-wave exchange of the kernel goes through LDS; __syncthreads also drains vmcnt, which made
-// the first barrier of CMUX i wait for the key words of CMUX i + 1 that FFT_LAT_PREFETCH had just requested (an L2 /
-// HBM round trip on the critical path of every CMUX) -- with LDS-only barriers they stay in flight for a whole CMUX.
-#ifndef FFT_LAT_LDSBAR
-#define FFT_LAT_LDSBAR 1
-#endif
+// The latency kernel's three barriers per CMUX wait for LDS only (s_waitcnt lgkmcnt(0) + s_barrier; round 6).  Every
+// cross-wave exchange of the kernel goes through LDS; __syncthreads also drains vmcnt, which made the first barrier of
+// CMUX i wait for the key words of CMUX i + 1 that the kernel's prefetch had just requested (an L2 / HBM round trip on
+// the critical path of every CMUX) -- with LDS-only barriers they stay in flight for a whole CMUX.
 __device__ __forceinline__ void lat_barrier() {
-#if FFT_LAT_LDSBAR
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#else
-  __syncthreads();
-#endif
 }
 
 // one CMUX of the latency kernel (phases A, B, C and their three barriers)
@@ -1133,7 +667,7 @@ __device__ __forceinline__ void lat_cmux(FftLatShared& sh, const u64* __restrict
       xr[e] = (double)dg[e];
       xi[e] = (double)dg[e + 8];
     }
-    dft512_fwd<true, true>(xr, xi, sh.T[wave], lane, tb, sh.tw);
+    dft512_fwd(xr, xi, sh.T[wave], lane, tb, sh.tw);
 #pragma unroll
     for (int e = 0; e < 8; e++) sh.F[wave][64 * e + lane] = make_double2(xr[e], xi[e]);
   }
@@ -1172,8 +706,8 @@ __device__ __forceinline__ void lat_cmux(FftLatShared& sh, const u64* __restrict
     u64* acc = sh.A[wave];
 #pragma unroll
     for (int e = 0; e < 8; e++) {
-      acc[64 * e + lane] = ACC_ADD(acc[64 * e + lane], xr[e]);
-      acc[64 * (e + 8) + lane] = ACC_ADD(acc[64 * (e + 8) + lane], xi[e]);
+      acc[64 * e + lane] = torus_acc_add_y(acc[64 * e + lane], xr[e]);
+      acc[64 * (e + 8) + lane] = torus_acc_add_y(acc[64 * (e + 8) + lane], xi[e]);
     }
   }
   LS_MARK(ls, 4);
@@ -1213,7 +747,6 @@ __global__ __launch_bounds__(FL_THREADS, 1) void blind_rotate_fft_lat_kernel(
 
   const int j = wave >> 2, s0 = (wave & 3) * 2;  // phase B: output j, slots s0, s0 + 1
   LatStamp ls;
-#if FFT_LAT_PREFETCH
   // key words one CMUX ahead (two register sets, the loop unrolled by two): a CMUX's row arrives while the
   // previous CMUX runs instead of behind this CMUX's phase A
   double2 kva[6][2], kvb[6][2];
@@ -1225,13 +758,6 @@ __global__ __launch_bounds__(FL_THREADS, 1) void blind_rotate_fft_lat_kernel(
     if (i + 2 < n) lat_load_key(bsk, i + 2, j, s0, lane, kva);
     lat_cmux(sh, ct, i + 1, wave, lane, tb, j, s0, kvb, ls);
   }
-#else
-  for (int i = 0; i < n; i++) {
-    double2 kv[6][2];  // phase-B key words of this CMUX, requested now, consumed after phase A
-    lat_load_key(bsk, i, j, s0, lane, kv);
-    lat_cmux(sh, ct, i, wave, lane, tb, j, s0, kv, ls);
-  }
-#endif
 
 #if FFT_LATSTAMP
   if (lane == 0 && b < 8)
@@ -1359,29 +885,7 @@ hipError_t launch_blind_rotate_fft(const u64* lwe_in, size_t B, int n, const u64
                          n_lut, bk, t, out_big, out_acc);
     return hipGetLastError();
   }
-#if FFT_G3
-  {
-    // rounds of one workgroup per CU, at most G3_CTS ciphertexts each, counts balanced over the whole grid
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
-    const size_t rounds = (B + (size_t)G3_CTS * cus - 1) / ((size_t)G3_CTS * cus);
-    size_t nwg = rounds * (size_t)cus;
-    if (nwg > B) nwg = B;
-    dim3 grid((unsigned)nwg), block(64 * G3_NW);
-    if (out_acc && out_big)
-      hipLaunchKernelGGL((blind_rotate_fft_g3_kernel<true, true>), grid, block, 0, s, lwe_in, n, B, luts, lut_index,
-                         n_lut, bk, t, out_big, out_acc);
-    else if (out_acc)
-      hipLaunchKernelGGL((blind_rotate_fft_g3_kernel<true, false>), grid, block, 0, s, lwe_in, n, B, luts, lut_index,
-                         n_lut, bk, t, out_big, out_acc);
-    else
-      hipLaunchKernelGGL((blind_rotate_fft_g3_kernel<false, true>), grid, block, 0, s, lwe_in, n, B, luts, lut_index,
-                         n_lut, bk, t, out_big, out_acc);
-    return hipGetLastError();
-  }
-#endif
-  constexpr int CTS = FFT_PAIR_CTS;
+  constexpr int CTS = 2;  // ciphertexts per workgroup (FpShared)
   dim3 grid((unsigned)((B + CTS - 1) / CTS)), block(128 * CTS);
   if (out_acc && out_big)
     hipLaunchKernelGGL((blind_rotate_fft_pair_kernel<CTS, true, true>), grid, block, 0, s, lwe_in, n, B, luts,

@@ -2,7 +2,7 @@
 # Static ISA stats of the CMUX loop of the P-GATE pair kernel (blind_rotate_fft_pair_kernel<2, false, true>, the
 # instantiation bench.py runs): resources of the kernel, then the f64, non-f64 VALU, scalar, LDS, wait, M0-write and LDS-DMA counts of the loop body (both
 # branches of the partial-sum exchange counted).  Compiles with the Makefile's flags for pbs_fft.o; needs no GPU.
-# usage: tools/isa_pair_stats.sh [-k out.s] [extra hipcc flags, e.g. -DFFT_MAC_PIPE=0 ...]
+# usage: tools/isa_pair_stats.sh [-k out.s] [extra hipcc flags, e.g. -DFFT_DMASTAMP=1 ...]
 #   -k out.s: keep the loop body (its line numbers are those of the kernel's listing) for reading
 set -eu
 cd "$(dirname "$0")/.."
