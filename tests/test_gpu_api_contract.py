@@ -1,7 +1,8 @@
 """Host API contract of libtfhe_hip.so on the MI355X that no other suite pins: which timing slots one PBS call
 fills (plain and many-LUT run the same stage sequence), the plain PBS through its host-buffer and device-buffer
-entries, and the single-shard stage entries (blind rotate, sample extraction, noise reduction, NTT) that share one
-staged-call frame.  Every comparison of ciphertexts is bit-exact."""
+entries, the single-shard stage entries (blind rotate, sample extraction, noise reduction, NTT) that share one
+staged-call frame, and the rows of the back-end table (kernel names, latency crossovers).  Every comparison of
+ciphertexts is bit-exact."""
 import numpy as np
 import pytest
 
@@ -62,7 +63,7 @@ def test_pbs_device_equals_host_call(request, name):
 
 
 # ---- 3. the stage entries -------------------------------------------------------------------------------------
-def test_stage_entries_fhevm_fft(fhevm_fft_engine, fhevm_fft_keys):
+def test_stage_entries_fhevm_fft(fhevm_fft_engine, fhevm_fft_keys, oracle_mod):
     eng = fhevm_fft_engine
     ck, sk = fhevm_fft_keys
     p = eng.params
@@ -71,11 +72,55 @@ def test_stage_entries_fhevm_fft(fhevm_fft_engine, fhevm_fft_keys):
     assert small.shape == (3, p.n + 1)
     acc = eng.blind_rotate(small, luts, np.array([0, 1, 0], dtype=np.uint32))
     assert acc.shape == (3, (p.k + 1) * p.N) and acc.any()
-    assert np.array_equal(eng.sample_extract(acc), eng.sample_extract_many(acc, 1, p.N)[:, 0])
+    big = eng.sample_extract(acc)
+    prm = oracle_mod.params(tfhe_amd.PRESET_FHEVM_FFT)
+    assert big.shape == (3, p.k * p.N + 1)
+    assert all(np.array_equal(big[b], oracle_mod.sample_extract_torus(prm, acc[b])) for b in range(3))
     reduced, picks = eng.ms_reduce(small)
     assert reduced.shape == (3, p.n + 1) and picks.shape == (3,)
     count = sk.ms_zeros.shape[0]
     assert all(-1 <= int(z) < count for z in picks), picks
+
+
+# the degree-0 extraction is the n_fn = 1 case of the many-LUT kernel on every back end: against the oracle
+@pytest.mark.parametrize("name", list(ENGINES))
+def test_sample_extract_equals_oracle(request, oracle_mod, name):
+    eng = request.getfixturevalue(name)
+    p = eng.params
+    fft = p.transform == tfhe_amd.TRANSFORM_FFT64
+    prm = oracle_mod.params(list(ENGINES).index(name))      # ENGINES lists the fixtures in preset order
+    assert (prm.N, prm.k, prm.transform) == (p.N, p.k, p.transform)
+    acc = np.random.default_rng(0x5E0).integers(1, P, (3, 2 * p.N), dtype=np.uint64)   # residues: valid on both rings
+    # word 0, word N - 1 and body word 0: distinct and non-zero
+    acc[:, 0] = 0x1111_0000_0000_0001 + np.arange(3, dtype=np.uint64)
+    acc[:, p.N - 1] = 0x2222_0000_0000_0002 + np.arange(3, dtype=np.uint64)
+    acc[:, p.N] = 0x3333_0000_0000_0003 + np.arange(3, dtype=np.uint64)
+    ref = oracle_mod.sample_extract_torus if fft else oracle_mod.sample_extract
+    big = eng.sample_extract(acc)
+    assert big.shape == (3, p.k * p.N + 1)
+    for b in range(3):
+        assert np.array_equal(big[b], ref(prm, acc[b])), (name, b)
+
+
+# ---- 4. the back-end table: kernel names and default latency crossovers, one batch-size decision -----------------
+BR_ROWS = {"engine": (1024, "blind_rotate_lat_kernel", "blind_rotate_kernel"),
+           "fhevm_engine": (512, "blind_rotate2048_lat_kernel", "blind_rotate2048_kernel"),
+           "gate_fft_engine": (256, "blind_rotate_fft_lat_kernel", "blind_rotate_fft_pair_kernel"),
+           "fhevm_fft_engine": (512, "blind_rotate_fft2k_kernel", "blind_rotate_fft2k_kernel")}
+
+
+@pytest.mark.parametrize("name", list(ENGINES))
+def test_br_kernel_names_and_crossover(request, name):
+    eng = request.getfixturevalue(name)
+    crossover, lat, batch = BR_ROWS[name]
+    try:
+        assert eng.br_kernel(crossover) == lat and eng.br_kernel(crossover + 1) == batch, name
+        assert eng.br_kernel(1) == lat
+        eng.set_latency_batch(0)
+        assert eng.br_kernel(1) == batch
+    finally:
+        eng.set_latency_batch(crossover)
+    assert eng.br_kernel(crossover) == lat
 
 
 def test_ntt_roundtrip_in_place(fhevm_engine):

@@ -539,9 +539,10 @@ class Engine:
         return lut_constant(self.params.N, MU)
 
     # -- hot path ---------------------------------------------------------------------------
-    def _pbs_host_args(self, cts, luts, lut_index):
-        """Host arrays of pbs / pbs_many -> (the (B, dim+1) ciphertexts, the C arguments up to ``lut_index``)."""
-        cts = _c_u64(cts).reshape(-1, self.params.io_dim + 1)
+    def _pbs_host_args(self, cts, luts, lut_index, row_len):
+        """Host arrays of pbs / pbs_many / bootstrap / blind_rotate -> (the (B, row_len) ciphertexts, the C arguments
+        up to ``lut_index``)."""
+        cts = _c_u64(cts).reshape(-1, row_len)
         luts = _c_u64(luts).reshape(-1, self.params.N)
         li = None
         if lut_index is not None:
@@ -560,7 +561,7 @@ class Engine:
 
     def pbs(self, cts: np.ndarray, luts: np.ndarray, lut_index=None) -> np.ndarray:
         """Batched keyswitch_programmable_bootstrap over host arrays: (B, dim+1) -> (B, dim+1)."""
-        cts, head = self._pbs_host_args(cts, luts, lut_index)
+        cts, head = self._pbs_host_args(cts, luts, lut_index, self.params.io_dim + 1)
         out = np.zeros_like(cts)
         _check(lib().tfhe_hip_pbs(*head, _u64(out)))
         return out
@@ -587,16 +588,9 @@ class Engine:
         extraction with no keyswitch, (B, n+1) under the small key -> (B, kN+1) under the GLWE key.  Needs the
         bootstrapping key only (``load_bsk`` or ``load_keys``)."""
         p = self.params
-        cts = _c_u64(cts).reshape(-1, p.n + 1)
-        luts = _c_u64(luts).reshape(-1, p.N)
-        li = None
-        if lut_index is not None:
-            li = np.ascontiguousarray(np.asarray(lut_index, dtype=np.uint32))
-            if li.shape[0] != cts.shape[0]:
-                raise ValueError("lut_index must have one entry per ciphertext")
+        cts, head = self._pbs_host_args(cts, luts, lut_index, p.n + 1)
         out = np.zeros((cts.shape[0], p.k * p.N + 1), dtype=np.uint64)
-        _check(lib().tfhe_hip_bootstrap(self._h, _u64(cts), cts.shape[0], _u64(luts), luts.shape[0],
-                                        li.ctypes.data_as(_U32P) if li is not None else None, _u64(out)))
+        _check(lib().tfhe_hip_bootstrap(*head, _u64(out)))
         return out
 
     def bootstrap_async(self, d_in, d_luts, d_out, d_lut_index=None, stream=None) -> None:
@@ -617,7 +611,7 @@ class Engine:
         """tfhe-rs ``apply_many_lookup_table``, batched over host arrays: one blind rotation per input and
         ``n_fn`` outputs, function f extracted at degree ``f * stride`` (``lut_many`` builds the LUTs):
         (B, dim+1) -> (B, n_fn, dim+1)."""
-        cts, head = self._pbs_host_args(cts, luts, lut_index)
+        cts, head = self._pbs_host_args(cts, luts, lut_index, self.params.io_dim + 1)
         n_fn, stride = int(n_fn), int(stride)
         if not (0 <= n_fn < 1 << 32 and 0 <= stride < 1 << 32):
             raise ValueError("n_fn and stride must fit 32 bits")
@@ -649,12 +643,9 @@ class Engine:
 
     def blind_rotate(self, cts: np.ndarray, luts: np.ndarray, lut_index=None) -> np.ndarray:
         p = self.params
-        cts = _c_u64(cts).reshape(-1, p.n + 1)
-        luts = _c_u64(luts).reshape(-1, p.N)
+        cts, head = self._pbs_host_args(cts, luts, lut_index, p.n + 1)
         out = np.zeros((cts.shape[0], (p.k + 1) * p.N), dtype=np.uint64)
-        li = np.ascontiguousarray(np.asarray(lut_index, dtype=np.uint32)) if lut_index is not None else None
-        _check(lib().tfhe_hip_blind_rotate(self._h, _u64(cts), cts.shape[0], _u64(luts), luts.shape[0],
-                                           li.ctypes.data_as(_U32P) if li is not None else None, _u64(out)))
+        _check(lib().tfhe_hip_blind_rotate(*head, _u64(out)))
         return out
 
     def sample_extract(self, acc: np.ndarray) -> np.ndarray:

@@ -37,30 +37,26 @@ bool params_valid(const tfhe_params* p) {
          p->ks_base_log * p->ks_level < 64 && p->transform <= TFHE_HIP_TRANSFORM_FFT64;
 }
 
-// the device kernels of this build: P-GATE (N = 1024, PBS -> KS) and P-FHEVM (N = 2048, KS -> PBS)
+// the presets = the parameter shapes the device kernels of this build cover (P-GATE: N = 1024, PBS -> KS; P-FHEVM:
+// N = 2048, KS -> PBS), each on both transforms
+const struct {
+  int id;
+  tfhe_params p;
+} PRESETS[] = {
+    {TFHE_HIP_PRESET_GATE, {630, 1, 1024, 7, 3, 2, 8, -15, -25, 0, TFHE_HIP_TRANSFORM_NTT}},
+    {TFHE_HIP_PRESET_FHEVM, {918, 1, 2048, 23, 1, 4, 4, -19, -47, 1, TFHE_HIP_TRANSFORM_NTT}},
+    {TFHE_HIP_PRESET_GATE_FFT, {630, 1, 1024, 7, 3, 2, 8, -15, -25, 0, TFHE_HIP_TRANSFORM_FFT64}},
+    {TFHE_HIP_PRESET_FHEVM_FFT, {918, 1, 2048, 23, 1, 4, 4, -19, -47, 1, TFHE_HIP_TRANSFORM_FFT64}},
+};
+
+// a preset's shape: everything the kernels are specialised for (n and the noise parameters are free)
 bool params_on_device(const tfhe_params* p) {
-  const bool gate = p->k == 1 && p->N == 1024 && p->pbs_base_log == 7 && p->pbs_level == 3 && p->ks_base_log == 2 &&
-                    p->ks_level == 8 && p->order == 0;
-  const bool fhevm = p->k == 1 && p->N == 2048 && p->pbs_base_log == 23 && p->pbs_level == 1 &&
-                     p->ks_base_log == 4 && p->ks_level == 4 && p->order == 1;
-  return gate || fhevm;
-}
-
-bool is_fft(const tfhe_params& p) { return p.transform == TFHE_HIP_TRANSFORM_FFT64; }
-
-// canonical psi: primitive 2N-th root of unity with psi^(2N/64) = 8 (generator 7)
-u64 canonical_psi(uint32_t N) {
-  using namespace tfhe;
-  const u64 w = gl_pow(7, (GL_P - 1) / (2ull * N));
-  const u64 r = gl_pow(w, 2ull * N / 64);
-  u64 k = 0, t = 1;
-  for (k = 0; k < 64; k++) {
-    if (t == r) break;
-    t = gl_mul(t, 8);
-  }
-  u64 m = 1;
-  while ((k * m) % 64 != 1) m += 2;
-  return gl_pow(w, m);
+  for (auto& r : PRESETS)
+    if (p->k == r.p.k && p->N == r.p.N && p->pbs_base_log == r.p.pbs_base_log && p->pbs_level == r.p.pbs_level &&
+        p->ks_base_log == r.p.ks_base_log && p->ks_level == r.p.ks_level && p->order == r.p.order &&
+        p->transform == r.p.transform)
+      return true;
+  return false;
 }
 
 // ---- RCCL, loaded on first use (a process that already holds torch's librccl reuses that copy) -----------
@@ -137,8 +133,8 @@ struct tfhe_ctx {
   bool bsk = false;   // a BSK is resident: the rotation-only calls work (tfhe_hip_load_bsk or tfhe_hip_load_keys)
   bool keys = false;  // BSK and KSK of one key set: every call works (tfhe_hip_load_keys)
   bool ks_valu = false;  // TFHE_HIP_KS_VALU=1: the VALU keyswitch kernel instead (A/B runs)
-  size_t lat_max = 1024; // batches up to this size (per shard) use the latency blind-rotate kernel
-  u64 ninv = 0;
+  const tfhe::br_engine* eng = nullptr;  // the blind-rotation back end of (transform, N), set once in tfhe_hip_create
+  size_t lat_max = 0;  // batches up to this size (per shard) run the latency kernel (default: eng->lat_max)
   uint32_t ms_count = 0;
   double ms_bound = 0, ms_r_sigma = 0, ms_var128 = 0;
   int bcast_mode = 0;  // tfhe_hip_key_bcast_mode
@@ -204,19 +200,13 @@ void timed_end(tfhe_ctx* c, shard& s, int which, hipStream_t st) {
 
 uint32_t io_dim(const tfhe_params& p) { return p.order == 0 ? p.n : p.k * p.N; }
 
+// the one place that picks the blind-rotation kernel by batch size (launch_br, tfhe_hip_br_kernel)
+bool latency_batch(const tfhe_ctx* c, size_t B) { return B <= c->lat_max; }
+
 hipError_t launch_br(tfhe_ctx* c, shard& s, const u64* in, size_t B, const u64* luts, const u32* idx, size_t n_lut,
                      u64* out_big, u64* out_acc, hipStream_t st) {
-  if (is_fft(c->p) && c->p.N == 2048)
-    return tfhe::launch_blind_rotate_fft2k(in, B, (int)c->p.n, luts, idx, (int)n_lut, (const double*)s.d_bsk,
-                                           (const double*)s.d_tw, out_big, out_acc, st, c->lat_max);
-  if (is_fft(c->p))
-    return tfhe::launch_blind_rotate_fft(in, B, (int)c->p.n, luts, idx, (int)n_lut, (const double*)s.d_bsk,
-                                         (const double*)s.d_tw, out_big, out_acc, st, c->lat_max, s.cus);
-  if (c->p.N == 2048)
-    return tfhe::launch_blind_rotate_2048(in, B, (int)c->p.n, luts, idx, (int)n_lut, s.d_bsk, s.d_tw, out_big, out_acc,
-                                          st, c->lat_max);
-  return tfhe::launch_blind_rotate(in, B, (int)c->p.n, luts, idx, (int)n_lut, s.d_bsk, s.d_tw, out_big, out_acc, st,
-                                   c->lat_max);
+  return c->eng->blind_rotate(in, B, (int)c->p.n, luts, idx, (int)n_lut, s.d_bsk, s.d_tw, out_big, out_acc,
+                              latency_batch(c, B), s.cus, st);
 }
 
 uint32_t log2u(uint32_t x) {
@@ -280,7 +270,7 @@ int pbs_device(tfhe_ctx* c, shard& s, const u64* d_in, size_t B, const u64* d_lu
     timed_begin(c, s, 0, st);
     if (m) {
       HIP_TRY(launch_br(c, s, in, B, d_luts, d_idx, n_lut, nullptr, s.d_acc, st));
-      HIP_TRY(tfhe::launch_sample_extract_many(s.d_acc, B, (int)c->p.k, (int)c->p.N, !is_fft(c->p), (int)m->n_fn,
+      HIP_TRY(tfhe::launch_sample_extract_many(s.d_acc, B, (int)c->p.k, (int)c->p.N, !c->eng->fft, (int)m->n_fn,
                                                (int)m->stride, out, st));
     } else {
       HIP_TRY(launch_br(c, s, in, B, d_luts, d_idx, n_lut, out, nullptr, st));
@@ -519,14 +509,7 @@ int convert_keys(tfhe_ctx* c, shard& s, const u64* std_bsk, size_t bsk_len, bool
       HIP_TRY(hipMalloc(&s.d_ks_planes, tfhe::ks_planes_bytes(big_dim, (int)c->p.ks_level, (int)c->p.n)));
     HIP_TRY(tfhe::launch_ksk_planes(s.d_ksk, big_dim, (int)c->p.ks_level, (int)c->p.n, s.d_ks_planes, s.stream));
   }
-  if (is_fft(c->p) && c->p.N == 2048)
-    HIP_TRY(tfhe::launch_bsk_to_fourier2k(std_bsk, (double*)s.d_bsk, polys, (const double*)s.d_tw, s.stream));
-  else if (is_fft(c->p))
-    HIP_TRY(tfhe::launch_bsk_to_fourier(std_bsk, (double*)s.d_bsk, polys, (const double*)s.d_tw, s.stream));
-  else if (c->p.N == 2048)
-    HIP_TRY(tfhe::launch_bsk_to_ntt_2048(std_bsk, s.d_bsk, polys, s.d_tw, c->ninv, s.stream));
-  else
-    HIP_TRY(tfhe::launch_bsk_to_ntt(std_bsk, s.d_bsk, (int)(polys / 12), s.d_tw, c->ninv, s.stream));
+  HIP_TRY(c->eng->convert_bsk(std_bsk, s.d_bsk, polys, s.d_tw, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
   return 0;
 }
@@ -536,22 +519,9 @@ int shard_init(tfhe_ctx* c, shard& s) {
   HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
   HIP_TRY(hipEventCreateWithFlags(&s.ws_free, hipEventDisableTiming));
   HIP_TRY(hipDeviceGetAttribute(&s.cus, hipDeviceAttributeMultiprocessorCount, s.device));
-  const tfhe_params& p = c->p;
-  using namespace tfhe;
-  if (is_fft(p)) {  // FFT64: twist / pass tables (pbs_fft.hip: make_fft_tables)
-    std::vector<double> tw(p.N == 2048 ? fft2k_tables_len() : fft_tables_len());
-    if (p.N == 2048) make_fft2k_tables(tw.data());
-    else make_fft_tables(tw.data());
-    if (!fft_slot_constants_ok() || !fft2k_slot_constants_ok())
-      return fail(TFHE_HIP_EUNSUPPORTED, "FFT64: compile-time twist constants differ from the host tables");
-    HIP_TRY(hipMalloc(&s.d_tw, tw.size() * 8));
-    HIP_TRY(hipMemcpy(s.d_tw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice));
-    return 0;
-  }
-  // twiddle tables of the device NTT layout (pbs_kernels.hip: make_ntt_tables)
-  std::vector<u64> tw(p.N == 2048 ? ntt2048_tables_len() : 4 * p.N);
-  if (p.N == 2048) make_ntt2048_tables(canonical_psi(p.N), tw.data());
-  else make_ntt_tables(canonical_psi(p.N), tw.data());
+  std::vector<u64> tw(c->eng->table_words);  // the back end's twiddle / twist tables
+  if (!c->eng->make_tables(tw.data()))
+    return fail(TFHE_HIP_EUNSUPPORTED, "FFT64: compile-time twist constants differ from the host tables");
   HIP_TRY(hipMalloc(&s.d_tw, tw.size() * 8));
   HIP_TRY(hipMemcpy(s.d_tw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice));
   return 0;
@@ -731,22 +701,11 @@ const char* tfhe_hip_last_error(void) { return g_err.c_str(); }
 int tfhe_hip_params_preset(int preset, tfhe_params* o) {
   if (!o) return fail(TFHE_HIP_EINVAL, "null params");
   memset(o, 0, sizeof(*o));
-  if (preset == TFHE_HIP_PRESET_GATE) {
-    *o = tfhe_params{630, 1, 1024, 7, 3, 2, 8, -15, -25, 0, TFHE_HIP_TRANSFORM_NTT};
-    return 0;
-  }
-  if (preset == TFHE_HIP_PRESET_FHEVM) {
-    *o = tfhe_params{918, 1, 2048, 23, 1, 4, 4, -19, -47, 1, TFHE_HIP_TRANSFORM_NTT};
-    return 0;
-  }
-  if (preset == TFHE_HIP_PRESET_GATE_FFT) {
-    *o = tfhe_params{630, 1, 1024, 7, 3, 2, 8, -15, -25, 0, TFHE_HIP_TRANSFORM_FFT64};
-    return 0;
-  }
-  if (preset == TFHE_HIP_PRESET_FHEVM_FFT) {
-    *o = tfhe_params{918, 1, 2048, 23, 1, 4, 4, -19, -47, 1, TFHE_HIP_TRANSFORM_FFT64};
-    return 0;
-  }
+  for (auto& r : PRESETS)
+    if (r.id == preset) {
+      *o = r.p;
+      return 0;
+    }
   return fail(TFHE_HIP_EINVAL, "unknown preset %d", preset);
 }
 
@@ -916,19 +875,15 @@ int tfhe_hip_create(const tfhe_params* p, const int* devices, int ndev, tfhe_ctx
       return fail(TFHE_HIP_EINVAL, "create: device %d of %d (devices[%d])", devices[i], count, i);
   std::unique_ptr<tfhe_ctx> c(new tfhe_ctx());
   c->p = *p;
-  // measured latency-kernel crossovers (tools/latency_sweep.py, tools/latency_sweep_fft.sh): NTT engine
-  // 1024 (N = 1024) / 512 (N = 2048); FFT64 512 for both N (from the third round of latency workgroups
-  // on, workgroups that start staggered stream the BSK from L2 at different CMUX indices)
-  // round 3: the P-GATE FFT64 component-pair batch kernel runs any batch up to 1024 in one 6.7 ms round, the
-  // latency kernel 3.5-3.7 ms up to 256 and 7.1 ms from 257 (profiles/r03_latsweep.json): crossover 256
-  // round 4: P-FHEVM FFT64 runs its one-wave kernel in latency mode (two ciphertexts per workgroup, one transform
-  // wave per SIMD) up to 512 ciphertexts (one round over 256 CUs), four per workgroup above
-  c->lat_max = is_fft(*p) ? (p->N == 1024 ? 256 : 512) : p->N == 2048 ? 512 : 1024;
+  c->eng = tfhe::find_engine(p->transform == TFHE_HIP_TRANSFORM_FFT64, p->N);
+  if (!c->eng)
+    return fail(TFHE_HIP_EUNSUPPORTED, "create: no blind-rotation back end for transform %u, N = %u", p->transform,
+                p->N);
+  c->lat_max = c->eng->lat_max;  // the measured latency-kernel crossover (each engine row says how)
   {
     const char* e = getenv("TFHE_HIP_KS_VALU");
     c->ks_valu = e && e[0] == '1';
   }
-  if (!is_fft(*p)) c->ninv = tfhe::gl_pow(p->N, tfhe::GL_P - 2);
   c->sh.resize(ndev);
   for (int i = 0; i < ndev; i++) c->sh[i].device = devices[i];
   for (int i = 0; i < ndev; i++) {
@@ -1177,12 +1132,8 @@ int tfhe_hip_sample_extract(tfhe_ctx* c, const uint64_t* acc, size_t B, uint64_t
   const size_t acc_len = (size_t)(c->p.k + 1) * c->p.N, big = (size_t)c->p.k * c->p.N + 1;
   return staged_call(c, {{acc, B * acc_len * 8}}, B * big * 8, {{out, 1, B * big * 8}},
                      [&](shard& s, std::vector<void*>& d) -> int {
-                       const u64* in = (const u64*)d[0];
-                       if (is_fft(c->p) && c->p.N == 2048)
-                         HIP_TRY(tfhe::launch_sample_extract_torus2k(in, B, (u64*)d[1], s.stream));
-                       else if (is_fft(c->p)) HIP_TRY(tfhe::launch_sample_extract_torus(in, B, (u64*)d[1], s.stream));
-                       else if (c->p.N == 2048) HIP_TRY(tfhe::launch_sample_extract_2048(in, B, (u64*)d[1], s.stream));
-                       else HIP_TRY(tfhe::launch_sample_extract(in, B, (u64*)d[1], s.stream));
+                       HIP_TRY(tfhe::launch_sample_extract_many((const u64*)d[0], B, (int)c->p.k, (int)c->p.N,
+                                                                !c->eng->fft, 1, 1, (u64*)d[1], s.stream));
                        return 0;
                      });
 }
@@ -1196,7 +1147,7 @@ int tfhe_hip_sample_extract_many(tfhe_ctx* c, const uint64_t* acc, size_t B, uin
   return staged_call(c, {{acc, B * acc_len * 8}}, out_bytes, {{out, 1, out_bytes}},
                      [&](shard& s, std::vector<void*>& d) -> int {
                        HIP_TRY(tfhe::launch_sample_extract_many((const u64*)d[0], B, (int)c->p.k, (int)c->p.N,
-                                                                !is_fft(c->p), (int)n_fn, (int)stride, (u64*)d[1],
+                                                                !c->eng->fft, (int)n_fn, (int)stride, (u64*)d[1],
                                                                 s.stream));
                        return 0;
                      });
@@ -1215,19 +1166,13 @@ int tfhe_hip_keyswitch(tfhe_ctx* c, const uint64_t* in, size_t B, uint64_t* out)
 
 static int ntt_impl(tfhe_ctx* c, uint64_t* polys, size_t count, bool inverse) {
   if (!c || (count && !polys)) return fail(TFHE_HIP_EINVAL, "ntt: bad arguments");
-  if (is_fft(c->p)) return fail(TFHE_HIP_EUNSUPPORTED, "ntt: this ctx runs the FFT64 transform (tfhe_hip_fft_*)");
+  if (c->eng->fft) return fail(TFHE_HIP_EUNSUPPORTED, "ntt: this ctx runs the FFT64 transform (tfhe_hip_fft_*)");
   if (count == 0) return 0;
   for (size_t i = 0; i < count * c->p.N; i++)
     if (polys[i] >= tfhe::GL_P) return fail(TFHE_HIP_EINVAL, "ntt: value at %zu not reduced mod p", i);
   const size_t bytes = count * c->p.N * 8;
   return staged_call(c, {{polys, bytes}}, 0, {{polys, 0, bytes}}, [&](shard& s, std::vector<void*>& d) -> int {
-    if (c->p.N == 2048) {
-      if (inverse) HIP_TRY(tfhe::launch_ntt2048_inv((u64*)d[0], count, s.d_tw, c->ninv, s.stream));
-      else HIP_TRY(tfhe::launch_ntt2048_fwd((u64*)d[0], count, s.d_tw, s.stream));
-    } else {
-      if (inverse) HIP_TRY(tfhe::launch_ntt_inv((u64*)d[0], count, s.d_tw, c->ninv, s.stream));
-      else HIP_TRY(tfhe::launch_ntt_fwd((u64*)d[0], count, s.d_tw, s.stream));
-    }
+    HIP_TRY((inverse ? c->eng->inv : c->eng->fwd)((const u64*)d[0], count, (u64*)d[0], s.d_tw, s.stream));  // in place
     return 0;
   });
 }
@@ -1237,18 +1182,11 @@ int tfhe_hip_ntt_inv(tfhe_ctx* c, uint64_t* polys, size_t count) { return ntt_im
 
 static int fft_impl(tfhe_ctx* c, const void* in, size_t count, double* out, bool inverse) {
   if (!c || (count && (!in || !out))) return fail(TFHE_HIP_EINVAL, "fft: bad arguments");
-  if (!is_fft(c->p)) return fail(TFHE_HIP_EUNSUPPORTED, "fft: ctx transform is not FFT64");
+  if (!c->eng->fft) return fail(TFHE_HIP_EUNSUPPORTED, "fft: ctx transform is not FFT64");
   if (count == 0) return 0;
   const size_t bytes = count * c->p.N * 8;
   return staged_call(c, {{in, bytes}}, bytes, {{out, 1, bytes}}, [&](shard& s, std::vector<void*>& d) -> int {
-    const double* tw = (const double*)s.d_tw;
-    if (!inverse) {
-      if (c->p.N == 2048) HIP_TRY(tfhe::launch_fft2k_fwd((const u64*)d[0], count, (double*)d[1], tw, s.stream));
-      else HIP_TRY(tfhe::launch_fft_fwd((const u64*)d[0], count, (double*)d[1], tw, s.stream));
-    } else {
-      if (c->p.N == 2048) HIP_TRY(tfhe::launch_fft2k_inv((const double*)d[0], count, (double*)d[1], tw, s.stream));
-      else HIP_TRY(tfhe::launch_fft_inv((const double*)d[0], count, (double*)d[1], tw, s.stream));
-    }
+    HIP_TRY((inverse ? c->eng->inv : c->eng->fwd)((const u64*)d[0], count, (u64*)d[1], s.d_tw, s.stream));
     return 0;
   });
 }
@@ -1282,14 +1220,9 @@ int tfhe_hip_set_latency_batch(tfhe_ctx* c, size_t max_batch) {
   return 0;
 }
 
-// mirrors launch_br / the launchers' B <= latency_max_batch switch
 const char* tfhe_hip_br_kernel(const tfhe_ctx* c, size_t B) {
   if (!c) return nullptr;
-  const bool lat = B <= c->lat_max;
-  if (is_fft(c->p) && c->p.N == 2048) return "blind_rotate_fft2k_kernel";  // <2, ...> latency, <4, ...> batch
-  if (is_fft(c->p)) return lat ? "blind_rotate_fft_lat_kernel" : "blind_rotate_fft_pair_kernel";
-  if (c->p.N == 2048) return lat ? "blind_rotate2048_lat_kernel" : "blind_rotate2048_kernel";
-  return lat ? "blind_rotate_lat_kernel" : "blind_rotate_kernel";
+  return latency_batch(c, B) ? c->eng->lat_kernel : c->eng->batch_kernel;
 }
 
 int tfhe_hip_sync(tfhe_ctx* c) {

@@ -374,7 +374,7 @@ __device__ __forceinline__ u64 torus_acc_add_y(u64 acc, double y) {
 }
 
 // the update for any |x| < 2^115 (N = 2048 with 23-bit digits reaches |x| ~ 2^91, beyond the magic-number step for the
-// high word above), x = y * 2^32, given y: the N = 2048 keys' spectra carry the factor 2^-32 (launch_bsk_to_fourier2k
+// high word above), x = y * 2^32, given y: the N = 2048 keys' spectra carry the factor 2^-32 (convert_bsk_f2k
 // scales by 2^-42 instead of 2^-10) and every later step -- the MAC's fmas, the inverse transform's adds, multiplies and
 // fmas -- rounds a power-of-two multiple of its exact value, so y is x * 2^-32 bit for bit.  Then h = floor(y) directly,
 // and y - h = 2^-32 RN(x - 2^32 h) (the same scaling argument), so (y - h) + 2^20 = 2^-32 RN(l + 2^52): the same low

@@ -161,4 +161,17 @@ __host__ __device__ __forceinline__ u64 gl_pow(u64 a, u64 e) {
   return r;
 }
 
+// ---- shared by the NTT blind-rotation kernels (pbs_kernels.hip, pbs_n2048.hip)
+// (X^s v)[idx] of a negacyclic length-N polynomial v over Z_p, s in [0, 2N).  SPLIT: v in the split layout of
+// pbs_n2048.hip (coefficient c at v[(c & 1) * N / 2 + (c >> 1)])
+template <int N, bool SPLIT = false>
+__device__ __forceinline__ u64 rot_read(const u64* v, int idx, int s) {
+  int d = idx - s;
+  bool neg = false;
+  if (d < 0) { d += N; neg = !neg; }
+  if (d < 0) { d += N; neg = !neg; }
+  const u64 x = v[SPLIT ? (d & 1) * (N / 2) + (d >> 1) : d];
+  return neg ? gl_neg(x) : x;
+}
+
 }  // namespace tfhe

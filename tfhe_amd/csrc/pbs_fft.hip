@@ -774,15 +774,6 @@ __global__ __launch_bounds__(FL_THREADS, 1) void blind_rotate_fft_lat_kernel(
   }
 }
 
-__global__ void sample_extract_torus_kernel(const u64* __restrict__ acc, size_t B, u64* __restrict__ out) {
-  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= B * (N1K + 1)) return;
-  const size_t b = gid / (N1K + 1);
-  const int j = (int)(gid % (N1K + 1));
-  const u64* A = acc + b * 2048;
-  out[gid] = j == N1K ? A[N1K] : j == 0 ? A[0] : 0 - A[N1K - j];
-}
-
 // ---------------------------------------------------------------------------------------------
 // host: tables (fixed series in plain double, octant-reduced — the oracle's or_fft_twiddle)
 static double fs_sin(double x) {
@@ -831,13 +822,13 @@ static void twiddle(uint32_t t, uint32_t m, double* c, double* s) {
 
 void fft_twiddle(uint32_t t, uint32_t m, double* c, double* s) { fftk::twiddle(t, m, c, s); }
 
-size_t fft_tables_len() { return 2 * fftk::TW_C64; }
-
 // N = 1024 tables with the twist merged into the passes (fft512.h, "N = 1024 merged twist"):
 //   TW_A[e][L] = zeta^(L (1 + 4 e)),  TW_B as before,  TW_I[e][L] = zeta^((n0 + 8 e)(4 k0 + 1)) (L = n0 + 8 k0),
 // zeta = e^(2 pi i / 2048); TW_TWIST keeps zeta^j (the slot constants are its entries j = 64 e)
-void make_fft_tables(double* t) {
+// false: the compile-time slot constants differ from the table generator's zeta^(64 e) in some bit
+static bool make_tables_f1k(u64* tw) {
   using namespace fftk;
+  double* t = (double*)tw;
   for (uint32_t j = 0; j < (uint32_t)M; j++) twiddle(j, 4 * M, &t[2 * (TW_TWIST + j)], &t[2 * (TW_TWIST + j) + 1]);
   for (uint32_t e = 0; e < 8; e++)
     for (uint32_t L = 0; L < 64; L++) {
@@ -846,57 +837,39 @@ void make_fft_tables(double* t) {
       twiddle((((L & 7) + 8 * e) * (4 * (L >> 3) + 1)) % (4 * M), 4 * M, &t[2 * (TW_I + 64 * e + L)],
               &t[2 * (TW_I + 64 * e + L) + 1]);
     }
-}
-
-// the compile-time slot constants equal the table generator's zeta^(64 e) bit for bit
-bool fft_slot_constants_ok() {
   for (int e = 0; e < 8; e++) {
     double c, s, c2, s2;
-    fftk::twiddle(64u * e, 2048u, &c, &s);      // N = 1024
-    fftk::twiddle(128u * e, 4096u, &c2, &s2);   // N = 2048
-    if (c != fftk::ctw::SLOT[e].x || s != fftk::ctw::SLOT[e].y || c2 != c || s2 != s) return false;
+    twiddle(64u * e, 2048u, &c, &s);      // N = 1024
+    twiddle(128u * e, 4096u, &c2, &s2);   // N = 2048
+    if (c != ctw::SLOT[e].x || s != ctw::SLOT[e].y || c2 != c || s2 != s) return false;
   }
   return true;
 }
 
-hipError_t launch_bsk_to_fourier(const u64* bsk_std, double* bsk_f, size_t polys, const double* tw, hipStream_t s) {
+static hipError_t convert_bsk_f1k(const u64* bsk_std, u64* bsk_f, size_t polys, const u64* tw, hipStream_t s) {
+  if (polys == 0) return hipSuccess;
   hipLaunchKernelGGL(fftk::bsk_to_fourier_kernel, dim3((unsigned)polys), dim3(64), 0, s, bsk_std, (double2*)bsk_f,
                      (const double2*)tw);
   return hipGetLastError();
 }
 
-hipError_t launch_blind_rotate_fft(const u64* lwe_in, size_t B, int n, const u64* luts, const u32* lut_index,
-                                   int n_lut, const double* bsk_f, const double* tw, u64* out_big, u64* out_acc,
-                                   hipStream_t s, size_t latency_max_batch, int n_cus) {
+static hipError_t blind_rotate_f1k(const u64* lwe_in, size_t B, int n, const u64* luts, const u32* lut_index,
+                                   int n_lut, const u64* bsk_f, const u64* tw, u64* out_big, u64* out_acc,
+                                   bool latency, int n_cus, hipStream_t s) {
   using namespace fftk;
   if (B == 0) return hipSuccess;
   if (n_cus <= 0) n_cus = 256;
   const double2 *bk = (const double2*)bsk_f, *t = (const double2*)tw;
-  if (B <= latency_max_batch) {
-    dim3 grid((unsigned)B), block(FL_THREADS);
-    if (out_acc && out_big)
-      hipLaunchKernelGGL((blind_rotate_fft_lat_kernel<true, true>), grid, block, 0, s, lwe_in, n, B, luts, lut_index,
-                         n_lut, bk, t, out_big, out_acc);
-    else if (out_acc)
-      hipLaunchKernelGGL((blind_rotate_fft_lat_kernel<true, false>), grid, block, 0, s, lwe_in, n, B, luts, lut_index,
-                         n_lut, bk, t, out_big, out_acc);
-    else
-      hipLaunchKernelGGL((blind_rotate_fft_lat_kernel<false, true>), grid, block, 0, s, lwe_in, n, B, luts, lut_index,
-                         n_lut, bk, t, out_big, out_acc);
-    return hipGetLastError();
-  }
+  if (latency)
+    return launch_out_mode(out_acc, out_big, [&](auto wa, auto wb) {
+      hipLaunchKernelGGL((blind_rotate_fft_lat_kernel<wa(), wb()>), dim3((unsigned)B), dim3(FL_THREADS), 0, s, lwe_in,
+                         n, B, luts, lut_index, n_lut, bk, t, out_big, out_acc);
+    });
   constexpr int CTS = 2;  // ciphertexts per workgroup (FpShared)
-  dim3 grid((unsigned)((B + CTS - 1) / CTS)), block(128 * CTS);
-  if (out_acc && out_big)
-    hipLaunchKernelGGL((blind_rotate_fft_pair_kernel<CTS, true, true>), grid, block, 0, s, lwe_in, n, B, luts,
-                       lut_index, n_lut, bk, t, out_big, out_acc, n_cus);
-  else if (out_acc)
-    hipLaunchKernelGGL((blind_rotate_fft_pair_kernel<CTS, true, false>), grid, block, 0, s, lwe_in, n, B, luts,
-                       lut_index, n_lut, bk, t, out_big, out_acc, n_cus);
-  else
-    hipLaunchKernelGGL((blind_rotate_fft_pair_kernel<CTS, false, true>), grid, block, 0, s, lwe_in, n, B, luts,
-                       lut_index, n_lut, bk, t, out_big, out_acc, n_cus);
-  return hipGetLastError();
+  return launch_out_mode(out_acc, out_big, [&](auto wa, auto wb) {
+    hipLaunchKernelGGL((blind_rotate_fft_pair_kernel<CTS, wa(), wb()>), dim3((unsigned)((B + CTS - 1) / CTS)),
+                       dim3(128 * CTS), 0, s, lwe_in, n, B, luts, lut_index, n_lut, bk, t, out_big, out_acc, n_cus);
+  });
 }
 
 #if FFT_LATSTAMP
@@ -918,26 +891,34 @@ extern "C" int tfhe_hip_debug_wgtimes(unsigned long long* out, size_t n) {
 }
 #endif
 
-hipError_t launch_sample_extract_torus(const u64* acc, size_t B, u64* out, hipStream_t s) {
-  if (B == 0) return hipSuccess;
-  const size_t total = B * (N1K + 1);
-  hipLaunchKernelGGL(fftk::sample_extract_torus_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, acc, B,
-                     out);
-  return hipGetLastError();
-}
-
-hipError_t launch_fft_fwd(const u64* in, size_t count, double* out, const double* tw, hipStream_t s) {
+static hipError_t fft_fwd_f1k(const u64* in, size_t count, u64* out, const u64* tw, hipStream_t s) {
   if (count == 0) return hipSuccess;
   hipLaunchKernelGGL(fftk::fft_fwd_kernel, dim3((unsigned)count), dim3(64), 0, s, in, (double2*)out,
                      (const double2*)tw);
   return hipGetLastError();
 }
 
-hipError_t launch_fft_inv(const double* in, size_t count, double* out, const double* tw, hipStream_t s) {
+static hipError_t fft_inv_f1k(const u64* in, size_t count, u64* out, const u64* tw, hipStream_t s) {
   if (count == 0) return hipSuccess;
-  hipLaunchKernelGGL(fftk::fft_inv_kernel, dim3((unsigned)count), dim3(64), 0, s, (const double2*)in, out,
+  hipLaunchKernelGGL(fftk::fft_inv_kernel, dim3((unsigned)count), dim3(64), 0, s, (const double2*)in, (double*)out,
                      (const double2*)tw);
   return hipGetLastError();
 }
+
+// latency crossover 256: the component-pair batch kernel runs any batch up to 1024 in one 6.7 ms round, the latency
+// kernel 3.5-3.7 ms up to 256 and 7.1 ms from 257 (profiles/r03_latsweep.json, tools/latency_sweep.py)
+#ifndef __HIP_DEVICE_COMPILE__  // a host object: the device pass would emit it with its pointers to host functions
+const br_engine ENGINE_FFT1K = {true,
+                                N1K,
+                                256,
+                                "blind_rotate_fft_lat_kernel",
+                                "blind_rotate_fft_pair_kernel",
+                                2 * fftk::TW_C64,
+                                make_tables_f1k,
+                                convert_bsk_f1k,
+                                blind_rotate_f1k,
+                                fft_fwd_f1k,
+                                fft_inv_f1k};
+#endif
 
 }  // namespace tfhe

@@ -53,7 +53,7 @@ __device__ __forceinline__ void load_ta(double2* ta, const double2* __restrict__
 // dig23(h) = ((((h + 2^8) >> 9) + 2^22 - 1) mod 2^23) - (2^22 - 1) = ceil((h - 255) / 512) in the signed reading of h with
 // the digit range (-2^22, 2^22], so -dig23(h) = floor((255 - h) / 512) = (int)(255 - h) >> 9 (the i32 wrap of 255 - h
 // lands exactly the tie h in [2^31 - 256, 2^31 + 256) on -2^22; checked for all 2^32 words).  The transforms run on the
-// negated digits against negated key spectra (launch_bsk_to_fourier2k), and every product of the MAC -- digit term times
+// negated digits against negated key spectra (convert_bsk_f2k), and every product of the MAC -- digit term times
 // key term -- is the same double, so the accumulators do not change by a bit.
 __device__ __forceinline__ void rotate_digits(const u64 (&v)[32], int a, int lane, double2* area, double (&xr)[16],
                                               double (&xi)[16]) {
@@ -314,15 +314,6 @@ __global__ __launch_bounds__(64) void inv2k_kernel(const double2* __restrict__ i
   }
 }
 
-__global__ void sample_extract_torus2k_kernel(const u64* __restrict__ acc, size_t B, u64* __restrict__ out) {
-  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= B * (N2 + 1)) return;
-  const size_t b = gid / (N2 + 1);
-  const int j = (int)(gid % (N2 + 1));
-  const u64* A = acc + b * (2 * N2);
-  out[gid] = j == N2 ? A[N2] : j == 0 ? A[0] : 0 - A[N2 - j];
-}
-
 }  // namespace fft1k
 
 #if FFT_WGTIME
@@ -332,19 +323,11 @@ extern "C" int tfhe_hip_debug_wgtimes2k(unsigned long long* out, size_t n) {
 }
 #endif
 
-hipError_t launch_sample_extract_torus2k(const u64* acc, size_t B, u64* out, hipStream_t s) {
-  if (B == 0) return hipSuccess;
-  const size_t total = B * (fft1k::N2 + 1);
-  hipLaunchKernelGGL(fft1k::sample_extract_torus2k_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, acc,
-                     B, out);
-  return hipGetLastError();
-}
-
-size_t fft2k_tables_len() { return 2 * fft1k::K_C64; }
-
 // ta[k][L] = zeta^{L (1 + 4 k)}, tb[m][l0] = zeta^{64 l0 m}, zeta = e^{2 pi i / 4096} (the oracle's tab1k)
-void make_fft2k_tables(double* t) {
+// false: the compile-time slot constants differ from the table generator's zeta^{64 e} in some bit
+static bool make_tables_f2k(u64* tw) {
   using namespace fft1k;
+  double* t = (double*)tw;
   for (uint32_t k = 0; k < 16; k++)
     for (uint32_t L = 0; L < 64; L++) {
       const int o = K_TA + 64 * k + L;
@@ -355,35 +338,31 @@ void make_fft2k_tables(double* t) {
       const int o = K_TB + 16 * m + l;
       fft_twiddle((64 * l * m) % 4096, 4096, &t[2 * o], &t[2 * o + 1]);
     }
-}
-
-// the compile-time slot constants equal the table generator's zeta^{64 e} bit for bit
-bool fft2k_slot_constants_ok() {
   for (int e = 0; e < 16; e++) {
     double c, s;
     fft_twiddle(64u * e, 4096u, &c, &s);
-    if (c != fft1k::ctw16::SLOT[e].x || s != fft1k::ctw16::SLOT[e].y) return false;
+    if (c != ctw16::SLOT[e].x || s != ctw16::SLOT[e].y) return false;
   }
   return true;
 }
 
-hipError_t launch_bsk_to_fourier2k(const u64* bsk_std, double* bsk_f, size_t polys, const double* tw, hipStream_t s) {
-  if (polys == 0) return hipSuccess;
-  hipLaunchKernelGGL(fft1k::fwd2k_kernel, dim3((unsigned)polys), dim3(64), 0, s, bsk_std, (double2*)bsk_f,
-                     (const double2*)tw, -0x1p-42);
+// one wave per polynomial through fwd2k_kernel; the key spectra negated (rotate_digits) and x 2^-42
+static hipError_t fwd_scaled_f2k(const u64* in, size_t count, u64* out, const u64* tw, double scale, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(fft1k::fwd2k_kernel, dim3((unsigned)count), dim3(64), 0, s, in, (double2*)out, (const double2*)tw,
+                     scale);
   return hipGetLastError();
 }
-
-hipError_t launch_fft2k_fwd(const u64* in, size_t count, double* out, const double* tw, hipStream_t s) {
-  if (count == 0) return hipSuccess;
-  hipLaunchKernelGGL(fft1k::fwd2k_kernel, dim3((unsigned)count), dim3(64), 0, s, in, (double2*)out,
-                     (const double2*)tw, 1.0);
-  return hipGetLastError();
+static hipError_t convert_bsk_f2k(const u64* bsk_std, u64* bsk_f, size_t polys, const u64* tw, hipStream_t s) {
+  return fwd_scaled_f2k(bsk_std, polys, bsk_f, tw, -0x1p-42, s);
+}
+static hipError_t fft_fwd_f2k(const u64* in, size_t count, u64* out, const u64* tw, hipStream_t s) {
+  return fwd_scaled_f2k(in, count, out, tw, 1.0, s);
 }
 
-hipError_t launch_fft2k_inv(const double* in, size_t count, double* out, const double* tw, hipStream_t s) {
+static hipError_t fft_inv_f2k(const u64* in, size_t count, u64* out, const u64* tw, hipStream_t s) {
   if (count == 0) return hipSuccess;
-  hipLaunchKernelGGL(fft1k::inv2k_kernel, dim3((unsigned)count), dim3(64), 0, s, (const double2*)in, out,
+  hipLaunchKernelGGL(fft1k::inv2k_kernel, dim3((unsigned)count), dim3(64), 0, s, (const double2*)in, (double*)out,
                      (const double2*)tw);
   return hipGetLastError();
 }
@@ -391,34 +370,42 @@ hipError_t launch_fft2k_inv(const double* in, size_t count, double* out, const d
 template <int CTS, int NW>
 static hipError_t launch_br2k(const u64* lwe_in, size_t B, int n, const u64* luts, const u32* lut_index, int n_lut,
                               const double2* bk, const double2* t, u64* out_big, u64* out_acc, hipStream_t s) {
-  using namespace fft1k;
-  dim3 grid((unsigned)((B + CTS - 1) / CTS)), block(64 * NW);
-  if (out_acc && out_big)
-    hipLaunchKernelGGL((blind_rotate_fft2k_kernel<CTS, NW, true, true>), grid, block, 0, s, lwe_in, n, B, luts,
-                       lut_index, n_lut, bk, t, out_big, out_acc);
-  else if (out_acc)
-    hipLaunchKernelGGL((blind_rotate_fft2k_kernel<CTS, NW, true, false>), grid, block, 0, s, lwe_in, n, B, luts,
-                       lut_index, n_lut, bk, t, out_big, out_acc);
-  else
-    hipLaunchKernelGGL((blind_rotate_fft2k_kernel<CTS, NW, false, true>), grid, block, 0, s, lwe_in, n, B, luts,
-                       lut_index, n_lut, bk, t, out_big, out_acc);
-  return hipGetLastError();
+  return launch_out_mode(out_acc, out_big, [&](auto wa, auto wb) {
+    hipLaunchKernelGGL((fft1k::blind_rotate_fft2k_kernel<CTS, NW, wa(), wb()>), dim3((unsigned)((B + CTS - 1) / CTS)),
+                       dim3(64 * NW), 0, s, lwe_in, n, B, luts, lut_index, n_lut, bk, t, out_big, out_acc);
+  });
 }
 
-// batches up to latency_max_batch: two ciphertexts per workgroup (four transform waves on four SIMDs, eight MAC
-// waves); larger batches: two per workgroup of four waves, two workgroups per CU (16 KB areas; with the padded
-// 17 KB areas of F1_SWZ = 0 four per workgroup of eight waves, two transform waves per SIMD)
-hipError_t launch_blind_rotate_fft2k(const u64* lwe_in, size_t B, int n, const u64* luts, const u32* lut_index,
-                                     int n_lut, const double* bsk_f, const double* tw, u64* out_big, u64* out_acc,
-                                     hipStream_t s, size_t latency_max_batch) {
+// latency: two ciphertexts per workgroup (four transform waves on four SIMDs, eight MAC waves); batch: two per
+// workgroup of four waves, two workgroups per CU (16 KB areas; with the padded 17 KB areas of F1_SWZ = 0 four per
+// workgroup of eight waves, two transform waves per SIMD)
+static hipError_t blind_rotate_f2k(const u64* lwe_in, size_t B, int n, const u64* luts, const u32* lut_index,
+                                   int n_lut, const u64* bsk_f, const u64* tw, u64* out_big, u64* out_acc,
+                                   bool latency, int, hipStream_t s) {
   if (B == 0) return hipSuccess;
   const double2 *bk = (const double2*)bsk_f, *t = (const double2*)tw;
-  if (B <= latency_max_batch) return launch_br2k<2, 8>(lwe_in, B, n, luts, lut_index, n_lut, bk, t, out_big, out_acc, s);
+  if (latency) return launch_br2k<2, 8>(lwe_in, B, n, luts, lut_index, n_lut, bk, t, out_big, out_acc, s);
 #if F1_SWZ != 0
   return launch_br2k<2, 4>(lwe_in, B, n, luts, lut_index, n_lut, bk, t, out_big, out_acc, s);
 #else
   return launch_br2k<4, 8>(lwe_in, B, n, luts, lut_index, n_lut, bk, t, out_big, out_acc, s);
 #endif
 }
+
+// latency crossover 512: the one-wave kernel in latency mode covers 512 ciphertexts in one round over 256 CUs;
+// both modes run blind_rotate_fft2k_kernel (<2, 8, ...> latency, <2, 4, ...> batch)
+#ifndef __HIP_DEVICE_COMPILE__  // a host object: the device pass would emit it with its pointers to host functions
+const br_engine ENGINE_FFT2K = {true,
+                                fft1k::N2,
+                                512,
+                                "blind_rotate_fft2k_kernel",
+                                "blind_rotate_fft2k_kernel",
+                                2 * fft1k::K_C64,
+                                make_tables_f2k,
+                                convert_bsk_f2k,
+                                blind_rotate_f2k,
+                                fft_fwd_f2k,
+                                fft_inv_f2k};
+#endif
 
 }  // namespace tfhe

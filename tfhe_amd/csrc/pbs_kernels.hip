@@ -7,7 +7,6 @@
 //                   NTT -> accumulate; sample extract + Z_p -> 2^64 fused in the epilogue
 //   keyswitch       batched LWE keyswitch kN -> n (64 ciphertexts x 64 columns per workgroup)
 //   ntt_fwd/inv     natural-order NTT over the same device routines (parity tests of the NTT)
-//   sample_extract  stage-level entry point (the fused epilogue's twin)
 //
 // Register layout: one wavefront processes one polynomial at a time, 16 u64 per lane.
 //   natural (coefficient) layout: lane L, element e  <->  coefficient 64 e + L
@@ -25,16 +24,6 @@ namespace tfhe {
 
 // round(x * 2048 / 2^64) mod 2048  (modulus switch)
 __device__ __forceinline__ int ms2048(u64 x) { return (int)((((x >> 52) + 1) >> 1) & 2047u); }
-
-// (X^s * v)[idx] for a negacyclic length-1024 polynomial v, s in [0, 2048).
-__device__ __forceinline__ u64 rot_read(const u64* v, int idx, int s) {
-  int d = idx - s;
-  bool neg = false;
-  if (d < 0) { d += N1K; neg = !neg; }
-  if (d < 0) { d += N1K; neg = !neg; }
-  const u64 x = v[d];
-  return neg ? gl_neg(x) : x;
-}
 
 // tfhe-rs SignedDecomposer, base 2^7 x 3 levels, on the Z_p residue read as a 64-bit word.
 // Returns the 3 digits packed as bytes (d + 64), byte l = level l (0 = most significant).
@@ -129,7 +118,7 @@ __device__ __forceinline__ void ext_prod_component(const u64 (&acc)[16], int a, 
   wave_lds_sync();
   u32 dig[16];
 #pragma unroll
-  for (int e = 0; e < 16; e++) dig[e] = decomp_7x3(gl_sub(rot_read(T, 64 * e + lane, a), acc[e]));
+  for (int e = 0; e < 16; e++) dig[e] = decomp_7x3(gl_sub(rot_read<N1K>(T, 64 * e + lane, a), acc[e]));
   wave_lds_sync();
 #pragma unroll 1
   for (int l = 0; l < 3; l++) {
@@ -177,7 +166,7 @@ __global__ __launch_bounds__(BR_THREADS, 1) void blind_rotate_kernel(
 #pragma unroll
     for (int e = 0; e < 16; e++) {
       accA[e] = 0;
-      accB[e] = rot_read(lut, 64 * e + lane, s);
+      accB[e] = rot_read<N1K>(lut, 64 * e + lane, s);
     }
   }
 
@@ -263,7 +252,7 @@ __global__ __launch_bounds__(LAT_THREADS, 1) void blind_rotate_lat_kernel(
     const int s = (2048 - ms2048(ct[n])) & 2047;
     for (int q = threadIdx.x; q < N1K; q += LAT_THREADS) {
       sh.A[0][q] = 0;
-      sh.A[1][q] = rot_read(lut, q, s);
+      sh.A[1][q] = rot_read<N1K>(lut, q, s);
     }
   }
   __syncthreads();
@@ -278,7 +267,7 @@ __global__ __launch_bounds__(LAT_THREADS, 1) void blind_rotate_lat_kernel(
 #pragma unroll
       for (int e = 0; e < 16; e++) {
         const int idx = 64 * e + lane;
-        dig[e] = decomp_7x3(gl_sub(rot_read(acc, idx, a), acc[idx]));
+        dig[e] = decomp_7x3(gl_sub(rot_read<N1K>(acc, idx, a), acc[idx]));
       }
       u64 x[16];
       ntt1024_fwd_digits(dig, l, x, sh.T[wave], lane, sh.tw);
@@ -323,20 +312,6 @@ __global__ __launch_bounds__(LAT_THREADS, 1) void blind_rotate_lat_kernel(
       ob[q] = gl_to_torus(v);
     }
   }
-}
-
-// ---------------------------------------------------------------------------------------------
-__global__ void sample_extract_kernel(const u64* __restrict__ acc, size_t B, u64* __restrict__ out) {
-  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= B * (N1K + 1)) return;
-  const size_t b = gid / (N1K + 1);
-  const int j = (int)(gid % (N1K + 1));
-  const u64* A = acc + b * 2048;
-  u64 v;
-  if (j == N1K) v = A[N1K];
-  else if (j == 0) v = A[0];
-  else v = gl_neg(A[N1K - j]);
-  out[gid] = gl_to_torus(v);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -450,48 +425,77 @@ void make_ntt_tables(u64 psi, u64* tw) {
     }
 }
 
-// launchers
-hipError_t launch_bsk_to_ntt(const u64* bsk_std, u64* bsk_ntt, int n, const u64* tw, u64 ninv, hipStream_t s) {
-  hipLaunchKernelGGL(bsk_to_ntt_kernel, dim3((unsigned)n * 12), dim3(64), 0, s, bsk_std, bsk_ntt, tw, ninv);
-  return hipGetLastError();
-}
-
-hipError_t launch_blind_rotate(const u64* lwe_in, size_t B, int n, const u64* luts, const u32* lut_index, int n_lut,
-                               const u64* bsk, const u64* tw, u64* out_big, u64* out_acc, hipStream_t s,
-                               size_t latency_max_batch) {
-  if (B == 0) return hipSuccess;
-  if (B <= latency_max_batch) {
-    dim3 grid((unsigned)B), block(LAT_THREADS);
-    if (out_acc && out_big)
-      hipLaunchKernelGGL((blind_rotate_lat_kernel<true, true>), grid, block, 0, s, lwe_in, n, B, luts, lut_index, n_lut,
-                         bsk, tw, out_big, out_acc);
-    else if (out_acc)
-      hipLaunchKernelGGL((blind_rotate_lat_kernel<true, false>), grid, block, 0, s, lwe_in, n, B, luts, lut_index,
-                         n_lut, bsk, tw, out_big, out_acc);
-    else
-      hipLaunchKernelGGL((blind_rotate_lat_kernel<false, true>), grid, block, 0, s, lwe_in, n, B, luts, lut_index,
-                         n_lut, bsk, tw, out_big, out_acc);
-    return hipGetLastError();
+// canonical psi: primitive 2N-th root of unity with psi^(2N/64) = 8 (generator 7)
+u64 canonical_psi(unsigned N) {
+  const u64 w = gl_pow(7, (GL_P - 1) / (2ull * N));
+  const u64 r = gl_pow(w, 2ull * N / 64);
+  u64 k = 0, t = 1;
+  for (k = 0; k < 64; k++) {
+    if (t == r) break;
+    t = gl_mul(t, 8);
   }
-  dim3 grid((unsigned)((B + BR_WAVES - 1) / BR_WAVES)), block(BR_THREADS);
-  if (out_acc && out_big)
-    hipLaunchKernelGGL((blind_rotate_kernel<true, true>), grid, block, 0, s, lwe_in, n, B, luts, lut_index, n_lut, bsk,
-                       tw, out_big, out_acc);
-  else if (out_acc)
-    hipLaunchKernelGGL((blind_rotate_kernel<true, false>), grid, block, 0, s, lwe_in, n, B, luts, lut_index, n_lut,
-                       bsk, tw, out_big, out_acc);
-  else
-    hipLaunchKernelGGL((blind_rotate_kernel<false, true>), grid, block, 0, s, lwe_in, n, B, luts, lut_index, n_lut,
-                       bsk, tw, out_big, out_acc);
+  u64 m = 1;
+  while ((k * m) % 64 != 1) m += 2;
+  return gl_pow(w, m);
+}
+
+// the back end's row of the engine table (pbs_kernels.h)
+static u64 ninv_1k() { return gl_pow(N1K, GL_P - 2); }
+
+static bool make_tables_1k(u64* tw) {
+  make_ntt_tables(canonical_psi(N1K), tw);
+  return true;
+}
+
+static hipError_t convert_bsk_1k(const u64* bsk_std, u64* bsk_ntt, size_t polys, const u64* tw, hipStream_t s) {
+  if (polys == 0) return hipSuccess;
+  hipLaunchKernelGGL(bsk_to_ntt_kernel, dim3((unsigned)polys), dim3(64), 0, s, bsk_std, bsk_ntt, tw, ninv_1k());
   return hipGetLastError();
 }
 
-hipError_t launch_sample_extract(const u64* acc, size_t B, u64* out, hipStream_t s) {
+static hipError_t blind_rotate_1k(const u64* lwe_in, size_t B, int n, const u64* luts, const u32* lut_index, int n_lut,
+                                  const u64* bsk, const u64* tw, u64* out_big, u64* out_acc, bool latency, int,
+                                  hipStream_t s) {
   if (B == 0) return hipSuccess;
-  const size_t total = B * (N1K + 1);
-  hipLaunchKernelGGL(sample_extract_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, acc, B, out);
+  if (latency)
+    return launch_out_mode(out_acc, out_big, [&](auto wa, auto wb) {
+      hipLaunchKernelGGL((blind_rotate_lat_kernel<wa(), wb()>), dim3((unsigned)B), dim3(LAT_THREADS), 0, s, lwe_in, n,
+                         B, luts, lut_index, n_lut, bsk, tw, out_big, out_acc);
+    });
+  return launch_out_mode(out_acc, out_big, [&](auto wa, auto wb) {
+    hipLaunchKernelGGL((blind_rotate_kernel<wa(), wb()>), dim3((unsigned)((B + BR_WAVES - 1) / BR_WAVES)),
+                       dim3(BR_THREADS), 0, s, lwe_in, n, B, luts, lut_index, n_lut, bsk, tw, out_big, out_acc);
+  });
+}
+
+static hipError_t ntt_fwd_1k(const u64* in, size_t count, u64* polys, const u64* tw, hipStream_t s) {
+  if (in != polys) return hipErrorInvalidValue;  // in place
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(ntt_fwd_kernel, dim3((unsigned)count), dim3(64), 0, s, polys, tw);
   return hipGetLastError();
 }
+
+static hipError_t ntt_inv_1k(const u64* in, size_t count, u64* polys, const u64* tw, hipStream_t s) {
+  if (in != polys) return hipErrorInvalidValue;  // in place
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(ntt_inv_kernel, dim3((unsigned)count), dim3(64), 0, s, polys, tw, ninv_1k());
+  return hipGetLastError();
+}
+
+// latency crossover 1024: measured, tools/latency_sweep.py
+#ifndef __HIP_DEVICE_COMPILE__  // a host object: the device pass would emit it with its pointers to host functions
+const br_engine ENGINE_NTT1K = {false,
+                                N1K,
+                                1024,
+                                "blind_rotate_lat_kernel",
+                                "blind_rotate_kernel",
+                                TW_U64,
+                                make_tables_1k,
+                                convert_bsk_1k,
+                                blind_rotate_1k,
+                                ntt_fwd_1k,
+                                ntt_inv_1k};
+#endif
 
 hipError_t launch_keyswitch(const u64* in_big, size_t B, int big_dim, const u64* ksk, int n, int base_log, int levels,
                            u64* out, hipStream_t s) {
@@ -504,18 +508,6 @@ hipError_t launch_keyswitch(const u64* in_big, size_t B, int big_dim, const u64*
     hipLaunchKernelGGL((keyswitch_kernel<4, 4>), grid, dim3(256), 0, s, in_big, big_dim, (int)B, ksk, n, out);
   else
     return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
-hipError_t launch_ntt_fwd(u64* polys, size_t count, const u64* tw, hipStream_t s) {
-  if (count == 0) return hipSuccess;
-  hipLaunchKernelGGL(ntt_fwd_kernel, dim3((unsigned)count), dim3(64), 0, s, polys, tw);
-  return hipGetLastError();
-}
-
-hipError_t launch_ntt_inv(u64* polys, size_t count, const u64* tw, u64 ninv, hipStream_t s) {
-  if (count == 0) return hipSuccess;
-  hipLaunchKernelGGL(ntt_inv_kernel, dim3((unsigned)count), dim3(64), 0, s, polys, tw, ninv);
   return hipGetLastError();
 }
 

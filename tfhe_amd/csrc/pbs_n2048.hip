@@ -24,31 +24,9 @@ namespace tfhe {
 constexpr int N2K = 2048;
 constexpr int TWC_FWD = TW_U64;           // combine twiddles psi^(2j+1), [h][p][L] (1024 per h)
 constexpr int TWC_INV = TW_U64 + N2K;     // and their inverses
-constexpr int TW2K_U64 = TW_U64 + 2 * N2K;
 
 // round(x * 4096 / 2^64) mod 4096
 __device__ __forceinline__ int ms4096(u64 x) { return (int)((((x >> 51) + 1) >> 1) & 4095u); }
-
-// (X^t v)[i] for a negacyclic length-2048 polynomial v held in LDS in split layout
-// (coefficient c at R[(c & 1) * 1024 + (c >> 1)]), t in [0, 4096).
-__device__ __forceinline__ u64 rot_read_split(const u64* R, int i, int t) {
-  int d = i - t;
-  bool neg = false;
-  if (d < 0) { d += N2K; neg = !neg; }
-  if (d < 0) { d += N2K; neg = !neg; }
-  const u64 x = R[(d & 1) * N1K + (d >> 1)];
-  return neg ? gl_neg(x) : x;
-}
-
-// same, natural layout in global memory (the LUT)
-__device__ __forceinline__ u64 rot_read_2048(const u64* v, int i, int t) {
-  int d = i - t;
-  bool neg = false;
-  if (d < 0) { d += N2K; neg = !neg; }
-  if (d < 0) { d += N2K; neg = !neg; }
-  const u64 x = v[d];
-  return neg ? gl_neg(x) : x;
-}
 
 // tfhe-rs SignedDecomposer, base 2^23 x 1 level: closest representable at 23 bits, digit in
 // [-2^22, 2^22] (the tie 2^22 stays positive: the next state is 0, so no carry).
@@ -190,7 +168,7 @@ __device__ __forceinline__ void ext_prod_2048(const u64 (&acc)[16], int a, int c
   u64 x[16];
 #pragma unroll
   for (int e = 0; e < 16; e++) {
-    const int d = decomp_23x1(gl_sub(rot_read_split(R, 2 * (64 * e + lane) + h, a), acc[e]));
+    const int d = decomp_23x1(gl_sub(rot_read<N2K, true>(R, 2 * (64 * e + lane) + h, a), acc[e]));
     x[e] = gl_from_i32(d);
   }
   __syncthreads();  // rotation reads done before the NTT scratch (aliased) is written
@@ -243,7 +221,7 @@ __device__ __forceinline__ void br2048_body(Br2Shared& sh, const u64* __restrict
 #pragma unroll
     for (int e = 0; e < 16; e++) {
       accA[e] = 0;
-      accB[e] = rot_read_2048(lut, 2 * (64 * e + lane) + h, s0);
+      accB[e] = rot_read<N2K>(lut, 2 * (64 * e + lane) + h, s0);
     }
   }
 
@@ -346,7 +324,7 @@ __global__ __launch_bounds__(512, 1) void blind_rotate2048_lat_kernel(
     const int s0 = (4096 - ms4096(ct[n])) & 4095;
     for (int i = threadIdx.x; i < N2K; i += 512) {
       sh.A[0][(i & 1) * N1K + (i >> 1)] = 0;
-      sh.A[1][(i & 1) * N1K + (i >> 1)] = rot_read_2048(lut, i, s0);
+      sh.A[1][(i & 1) * N1K + (i >> 1)] = rot_read<N2K>(lut, i, s0);
     }
   }
 
@@ -359,7 +337,7 @@ __global__ __launch_bounds__(512, 1) void blind_rotate2048_lat_kernel(
 #pragma unroll
       for (int e = 0; e < 16; e++) {
         const int m = 64 * e + lane;
-        x[e] = gl_from_i32(decomp_23x1(gl_sub(rot_read_split(acc, 2 * m + h, a), acc[h * N1K + m])));
+        x[e] = gl_from_i32(decomp_23x1(gl_sub(rot_read<N2K, true>(acc, 2 * m + h, a), acc[h * N1K + m])));
       }
       ntt1024_fwd(x, sh.T[wave], lane, sh.tw);
 #pragma unroll
@@ -440,21 +418,9 @@ __global__ __launch_bounds__(512, 1) void blind_rotate2048_lat_kernel(
   }
 }
 
-__global__ void sample_extract2048_kernel(const u64* __restrict__ acc, size_t B, u64* __restrict__ out) {
-  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= B * (N2K + 1)) return;
-  const size_t b = gid / (N2K + 1);
-  const int j = (int)(gid % (N2K + 1));
-  const u64* A = acc + b * (2 * N2K);
-  u64 v;
-  if (j == N2K) v = A[N2K];
-  else if (j == 0) v = A[0];
-  else v = gl_neg(A[N2K - j]);
-  out[gid] = gl_to_torus(v);
-}
-
 // ---------------------------------------------------------------------------------------------
-void make_ntt2048_tables(u64 psi, u64* tw) {
+// host: tables, and the back end's row of the engine table (pbs_kernels.h)
+static void make_ntt2048_tables(u64 psi, u64* tw) {
   make_ntt_tables(gl_mul(psi, psi), tw);  // the halves' 1024-point transforms use psi^2
   for (int h = 0; h < 2; h++)
     for (int p = 0; p < 8; p++)
@@ -466,62 +432,61 @@ void make_ntt2048_tables(u64 psi, u64* tw) {
       }
 }
 
-size_t ntt2048_tables_len() { return TW2K_U64; }
+static u64 ninv_2k() { return gl_pow(N2K, GL_P - 2); }
 
-hipError_t launch_bsk_to_ntt_2048(const u64* bsk_std, u64* bsk_ntt, size_t polys, const u64* tw, u64 ninv,
-                                  hipStream_t s) {
+static bool make_tables_2k(u64* tw) {
+  make_ntt2048_tables(canonical_psi(N2K), tw);
+  return true;
+}
+
+static hipError_t convert_bsk_2k(const u64* bsk_std, u64* bsk_ntt, size_t polys, const u64* tw, hipStream_t s) {
   if (polys == 0) return hipSuccess;
-  hipLaunchKernelGGL(bsk_to_ntt2048_kernel, dim3((unsigned)polys), dim3(128), 0, s, bsk_std, bsk_ntt, tw, ninv);
+  hipLaunchKernelGGL(bsk_to_ntt2048_kernel, dim3((unsigned)polys), dim3(128), 0, s, bsk_std, bsk_ntt, tw, ninv_2k());
   return hipGetLastError();
 }
 
-hipError_t launch_blind_rotate_2048(const u64* lwe_in, size_t B, int n, const u64* luts, const u32* lut_index,
-                                   int n_lut, const u64* bsk, const u64* tw, u64* out_big, u64* out_acc,
-                                   hipStream_t s, size_t latency_max_batch) {
+static hipError_t blind_rotate_2k(const u64* lwe_in, size_t B, int n, const u64* luts, const u32* lut_index, int n_lut,
+                                  const u64* bsk, const u64* tw, u64* out_big, u64* out_acc, bool latency, int,
+                                  hipStream_t s) {
   if (B == 0) return hipSuccess;
-  if (B <= latency_max_batch) {
-    dim3 grid((unsigned)B), block(512);
-    if (out_acc && out_big)
-      hipLaunchKernelGGL((blind_rotate2048_lat_kernel<true, true>), grid, block, 0, s, lwe_in, n, B, luts, lut_index,
-                         n_lut, bsk, tw, out_big, out_acc);
-    else if (out_acc)
-      hipLaunchKernelGGL((blind_rotate2048_lat_kernel<true, false>), grid, block, 0, s, lwe_in, n, B, luts,
-                         lut_index, n_lut, bsk, tw, out_big, out_acc);
-    else
-      hipLaunchKernelGGL((blind_rotate2048_lat_kernel<false, true>), grid, block, 0, s, lwe_in, n, B, luts,
-                         lut_index, n_lut, bsk, tw, out_big, out_acc);
-    return hipGetLastError();
-  }
-  dim3 grid((unsigned)((B + B2_CTS - 1) / B2_CTS)), block(B2_THREADS);
-  if (out_acc && out_big)
-    hipLaunchKernelGGL((blind_rotate2048_kernel<true, true>), grid, block, 0, s, lwe_in, n, B, luts, lut_index, n_lut,
-                       bsk, tw, out_big, out_acc);
-  else if (out_acc)
-    hipLaunchKernelGGL((blind_rotate2048_kernel<true, false>), grid, block, 0, s, lwe_in, n, B, luts, lut_index,
-                       n_lut, bsk, tw, out_big, out_acc);
-  else
-    hipLaunchKernelGGL((blind_rotate2048_kernel<false, true>), grid, block, 0, s, lwe_in, n, B, luts, lut_index,
-                       n_lut, bsk, tw, out_big, out_acc);
-  return hipGetLastError();
+  if (latency)
+    return launch_out_mode(out_acc, out_big, [&](auto wa, auto wb) {
+      hipLaunchKernelGGL((blind_rotate2048_lat_kernel<wa(), wb()>), dim3((unsigned)B), dim3(512), 0, s, lwe_in, n, B,
+                         luts, lut_index, n_lut, bsk, tw, out_big, out_acc);
+    });
+  return launch_out_mode(out_acc, out_big, [&](auto wa, auto wb) {
+    hipLaunchKernelGGL((blind_rotate2048_kernel<wa(), wb()>), dim3((unsigned)((B + B2_CTS - 1) / B2_CTS)),
+                       dim3(B2_THREADS), 0, s, lwe_in, n, B, luts, lut_index, n_lut, bsk, tw, out_big, out_acc);
+  });
 }
 
-hipError_t launch_sample_extract_2048(const u64* acc, size_t B, u64* out, hipStream_t s) {
-  if (B == 0) return hipSuccess;
-  const size_t total = B * (N2K + 1);
-  hipLaunchKernelGGL(sample_extract2048_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, acc, B, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_ntt2048_fwd(u64* polys, size_t count, const u64* tw, hipStream_t s) {
+static hipError_t ntt_fwd_2k(const u64* in, size_t count, u64* polys, const u64* tw, hipStream_t s) {
+  if (in != polys) return hipErrorInvalidValue;  // in place
   if (count == 0) return hipSuccess;
   hipLaunchKernelGGL(ntt2048_fwd_kernel, dim3((unsigned)count), dim3(128), 0, s, polys, tw);
   return hipGetLastError();
 }
 
-hipError_t launch_ntt2048_inv(u64* polys, size_t count, const u64* tw, u64 ninv, hipStream_t s) {
+static hipError_t ntt_inv_2k(const u64* in, size_t count, u64* polys, const u64* tw, hipStream_t s) {
+  if (in != polys) return hipErrorInvalidValue;  // in place
   if (count == 0) return hipSuccess;
-  hipLaunchKernelGGL(ntt2048_inv_kernel, dim3((unsigned)count), dim3(128), 0, s, polys, tw, ninv);
+  hipLaunchKernelGGL(ntt2048_inv_kernel, dim3((unsigned)count), dim3(128), 0, s, polys, tw, ninv_2k());
   return hipGetLastError();
 }
+
+// latency crossover 512: measured, tools/latency_sweep.py
+#ifndef __HIP_DEVICE_COMPILE__  // a host object: the device pass would emit it with its pointers to host functions
+const br_engine ENGINE_NTT2K = {false,
+                                N2K,
+                                512,
+                                "blind_rotate2048_lat_kernel",
+                                "blind_rotate2048_kernel",
+                                TW_U64 + 2 * N2K,
+                                make_tables_2k,
+                                convert_bsk_2k,
+                                blind_rotate_2k,
+                                ntt_fwd_2k,
+                                ntt_inv_2k};
+#endif
 
 }  // namespace tfhe
