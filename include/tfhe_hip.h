@@ -290,7 +290,8 @@ int tfhe_hip_sync(tfhe_ctx* ctx);
 /* Per-kernel device timing (HIP events recorded on the launch stream around every blind-rotate /
  * keyswitch launch).  reset clears the record; stats waits for the recorded events and returns the
  * summed milliseconds and the launch count.  which: 0 = blind rotate (+sample extract), 1 = keyswitch,
- * 2 = modulus-switch noise reduction, 3 = unpack / extract of tfhe_hip_decompress.
+ * 2 = modulus-switch noise reduction, 3 = the ingest stage of a call: unpack / extract of a decompression, or the
+ * expansion of a compact list.
  * Used by bench.py for the roofline figure. */
 int tfhe_hip_timing_enable(tfhe_ctx* ctx, int enable);
 int tfhe_hip_timing_reset(tfhe_ctx* ctx);
@@ -364,6 +365,44 @@ int tfhe_hip_decompress(tfhe_ctx* ctx, const tfhe_pks_params* pp, const uint64_t
 int tfhe_hip_decompress_async(tfhe_ctx* ctx, const tfhe_pks_params* pp, const uint64_t* d_packed, size_t packed_words,
                               size_t count, const uint64_t* d_luts, size_t n_lut, const uint32_t* d_lut_index,
                               uint64_t* d_lwe_big_out, void* stream);
+
+/* ---- compact ciphertext lists: expansion and casting ------------------------------------------
+ * Replaces tfhe-rs CompactCiphertextList::expand and the cast that follows it (KeySwitchingKey, then one PBS per
+ * radix block) on the ingest side of the fhEVM coprocessor: every user input arrives as ONE compact list under the
+ * network's CompactPublicKey (sdk/relayer/src/sdk/encrypt.ts:97-148,185, build_with_proof_packed; fixtures
+ * sdk/relayer/src/test/v1/ciphertext.ts:1, src/test/assets/input-proof-payload-{1,2,3}.json).  The proof is not
+ * verified here.  `list` is the LWE compact list's data Vec<u64> in tfhe-rs order: bins x lwe_dim mask words,
+ * bins = ceil(count / lwe_dim) (every bin of up to lwe_dim ciphertexts shares one mask polynomial M), then count
+ * body words.  Output row r is list entry q = r / rep, in bin q / lwe_dim at degree i = q % lwe_dim:
+ *   a[k] = M[k + i + 1 - lwe_dim] (k + i + 1 >= lwe_dim),   a[k] = -M[k + i + 1] (otherwise),   b = bodies[q]
+ * rep = 1 is the plain expansion; rep = 2 gives one row per radix block of a packed list (two blocks per LWE), and
+ * rows (anything in 0 .. count * rep) cuts the last entry short for an odd block count.
+ * lwe_dim: a power of two in 8 .. 4096 (EUNSUPPORTED for a larger power of two, EINVAL otherwise); EINVAL if
+ * list_words is not tfhe_hip_compact_list_words, rep == 0, rows > count * rep, rows > 0x7FFFFFFF, or a buffer is
+ * null when rows > 0; rows == 0 returns OK; count == 0 is valid only with rows == 0 and list_words == 0.  Every
+ * check runs before any device work. */
+/* bins * lwe_dim + count, or 0 if lwe_dim is not a power of two in 8..4096 or count == 0 (host only) */
+size_t tfhe_hip_compact_list_words(uint32_t lwe_dim, size_t count);
+/* Stage-level: the expansion alone (tfhe_amd/csrc/expand.hip), needs no key; timed in slot 3.  lwes_out: rows x
+ * (lwe_dim + 1).  The host form runs on shard 0; _async: device pointers, on the shard whose device holds d_list,
+ * enqueued on `stream` (rules of tfhe_hip_pbs_async). */
+int tfhe_hip_expand_compact(tfhe_ctx* ctx, const uint64_t* list, size_t list_words, uint32_t lwe_dim, size_t count,
+                            uint32_t rep, size_t rows, uint64_t* lwes_out);
+int tfhe_hip_expand_compact_async(tfhe_ctx* ctx, const uint64_t* d_list, size_t list_words, uint32_t lwe_dim,
+                                  size_t count, uint32_t rep, size_t rows, uint64_t* d_lwes_out, void* stream);
+/* Expansion into a shard workspace (slot 3), then the ctx's full PBS in its `order` (keyswitch with the loaded KSK --
+ * for ingest, the casting key compact-PKE key -> small key -- optional MS noise reduction, blind rotation; slots 1,
+ * 2, 0).  The list's dimension is tfhe_hip_io_dim(params): EINVAL if that is not an allowed lwe_dim.  luts / n_lut /
+ * lut_index (rows entries or null) as tfhe_hip_pbs; lwe_out: rows x (io_dim + 1).  ENOKEYS unless a full key set is
+ * loaded (a rotation-only ctx is refused like tfhe_hip_pbs); EINVAL for n_lut == 0 or a host lut_index entry >=
+ * n_lut.  The host form runs on shard 0; a multi-shard caller hands whole lists to the async form (device buffers on
+ * the shard's device; stream and workspace rules of tfhe_hip_pbs_async). */
+int tfhe_hip_expand_cast(tfhe_ctx* ctx, const uint64_t* list, size_t list_words, size_t count, uint32_t rep,
+                         size_t rows, const uint64_t* luts, size_t n_lut, const uint32_t* lut_index,
+                         uint64_t* lwe_out);
+int tfhe_hip_expand_cast_async(tfhe_ctx* ctx, const uint64_t* d_list, size_t list_words, size_t count, uint32_t rep,
+                               size_t rows, const uint64_t* d_luts, size_t n_lut, const uint32_t* d_lut_index,
+                               uint64_t* d_lwe_out, void* stream);
 
 /* ---- switch-and-squash: noise squashing to a 128-bit LWE ----------------------
  * fhEVM's sns-worker (coprocessor-docker-compose.yml:124-140) turns each 64-bit P-FHEVM ciphertext into

@@ -116,7 +116,8 @@ ABI_SYMBOLS = (
     "tfhe_hip_decompress_ksk", "tfhe_hip_decompress_lwe_list", "tfhe_hip_pbs_many", "tfhe_hip_pbs_many_async",
     "tfhe_hip_sample_extract_many", "tfhe_hip_load_bsk", "tfhe_hip_load_bsk_device", "tfhe_hip_bootstrap",
     "tfhe_hip_bootstrap_async", "tfhe_hip_pks_unpack_extract", "tfhe_hip_pks_unpack_extract_async",
-    "tfhe_hip_decompress", "tfhe_hip_decompress_async",
+    "tfhe_hip_decompress", "tfhe_hip_decompress_async", "tfhe_hip_compact_list_words", "tfhe_hip_expand_compact",
+    "tfhe_hip_expand_compact_async", "tfhe_hip_expand_cast", "tfhe_hip_expand_cast_async",
 )
 
 # P-FHEVM modulus-switch noise reduction key (include/tfhe_hip.h TFHE_HIP_MS_FHEVM_*)
@@ -218,6 +219,18 @@ def lib():
         L.tfhe_hip_timing_stats.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_int)]
         L.tfhe_hip_device.argtypes = [ctypes.c_void_p]
+        L.tfhe_hip_compact_list_words.argtypes = [ctypes.c_uint32, ctypes.c_size_t]
+        L.tfhe_hip_compact_list_words.restype = ctypes.c_size_t
+        L.tfhe_hip_expand_compact.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_size_t,
+                                              ctypes.c_uint32, ctypes.c_size_t, _U64P]
+        L.tfhe_hip_expand_compact_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
+                                                    ctypes.c_size_t, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_void_p,
+                                                    ctypes.c_void_p]
+        L.tfhe_hip_expand_cast.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32,
+                                           ctypes.c_size_t, _U64P, ctypes.c_size_t, _U32P, _U64P]
+        L.tfhe_hip_expand_cast_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                                 ctypes.c_uint32, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         _LIB = L
     return _LIB
 
@@ -631,6 +644,76 @@ class Engine:
         d_out = d_in.new_empty((d_in.shape[0], int(n_fn), d_in.shape[1]))
         if d_in.shape[0]:
             self.pbs_many_async(d_in.contiguous(), d_luts, d_out, n_fn, stride, d_lut_index)
+        return d_out
+
+    # -- compact ciphertext lists (tfhe_amd/ctlist.py builds the words) ----------------------------------
+    @staticmethod
+    def _rows(count: int, rep: int, rows) -> int:
+        return int(count) * int(rep) if rows is None else int(rows)
+
+    def expand_compact(self, words: np.ndarray, lwe_dim: int, count: int, rep: int = 1, rows=None) -> np.ndarray:
+        """tfhe-rs ``CompactCiphertextList::expand`` on the device, over host arrays: the list's words (masks then
+        bodies) -> (rows, lwe_dim + 1) LWEs, row r = list entry ``r // rep`` (``rows`` defaults to ``count * rep``).
+        Needs no key."""
+        w = _c_u64(words).reshape(-1)
+        rows = self._rows(count, rep, rows)
+        out = np.zeros((max(rows, 0), int(lwe_dim) + 1), dtype=np.uint64)
+        _check(lib().tfhe_hip_expand_compact(self._h, _u64(w), w.size, int(lwe_dim), int(count), int(rep), rows,
+                                             _u64(out)))
+        return out
+
+    def expand_compact_async(self, d_words, lwe_dim: int, count: int, d_out, rep: int = 1, rows=None,
+                             stream=None) -> None:
+        """Device-resident ``expand_compact`` (torch tensors on this device; d_out: (rows, lwe_dim + 1)), enqueued on
+        ``stream`` like ``pbs_async``."""
+        _check(lib().tfhe_hip_expand_compact_async(
+            self._h, ctypes.c_void_p(d_words.data_ptr()), d_words.numel(), int(lwe_dim), int(count), int(rep),
+            self._rows(count, rep, rows), ctypes.c_void_p(d_out.data_ptr()),
+            ctypes.c_void_p(_stream_handle(stream, self.device))))
+
+    def expand_compact_device(self, d_words, lwe_dim: int, count: int, rep: int = 1, rows=None):
+        """expand_compact_async into a fresh (rows, lwe_dim + 1) tensor on torch's current stream (no host
+        synchronisation)."""
+        rows = self._rows(count, rep, rows)
+        d_out = d_words.new_empty((max(rows, 0), int(lwe_dim) + 1))
+        self.expand_compact_async(d_words.contiguous(), lwe_dim, count, d_out, rep, rows)
+        return d_out
+
+    def expand_cast(self, words: np.ndarray, count: int, luts: np.ndarray, rep: int = 1, rows=None,
+                    lut_index=None) -> np.ndarray:
+        """Expansion of a compact list of dimension ``io_dim`` followed by this engine's full PBS, in one call over
+        host arrays: (rows, io_dim + 1).  With the casting key as the engine's keyswitch key this is the ingest of
+        an fhEVM input (``ctlist.cast_list_to_blocks``)."""
+        w = _c_u64(words).reshape(-1)
+        luts = _c_u64(luts).reshape(-1, self.params.N)
+        rows = self._rows(count, rep, rows)
+        li = None
+        if lut_index is not None:
+            li = np.ascontiguousarray(np.asarray(lut_index, dtype=np.uint32))
+            if li.shape[0] != rows:
+                raise ValueError("lut_index must have one entry per output row")
+        out = np.zeros((max(rows, 0), self.params.io_dim + 1), dtype=np.uint64)
+        _check(lib().tfhe_hip_expand_cast(self._h, _u64(w), w.size, int(count), int(rep), rows, _u64(luts),
+                                          luts.shape[0], li.ctypes.data_as(_U32P) if li is not None else None,
+                                          _u64(out)))
+        return out
+
+    def expand_cast_async(self, d_words, count: int, d_luts, d_out, rep: int = 1, rows=None, d_lut_index=None,
+                          stream=None) -> None:
+        """Device-resident ``expand_cast`` (torch tensors on this device; d_out: (rows, io_dim + 1)), enqueued on
+        ``stream`` like ``pbs_async``."""
+        _check(lib().tfhe_hip_expand_cast_async(
+            self._h, ctypes.c_void_p(d_words.data_ptr()), d_words.numel(), int(count), int(rep),
+            self._rows(count, rep, rows), ctypes.c_void_p(d_luts.data_ptr()), d_luts.numel() // self.params.N,
+            ctypes.c_void_p(d_lut_index.data_ptr()) if d_lut_index is not None else None,
+            ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(_stream_handle(stream, self.device))))
+
+    def expand_cast_device(self, d_words, count: int, d_luts, rep: int = 1, rows=None, d_lut_index=None):
+        """expand_cast_async into a fresh (rows, io_dim + 1) tensor on torch's current stream (no host
+        synchronisation); the result is an input of ``pbs_device``."""
+        rows = self._rows(count, rep, rows)
+        d_out = d_words.new_empty((max(rows, 0), self.params.io_dim + 1))
+        self.expand_cast_async(d_words.contiguous(), count, d_luts, d_out, rep, rows, d_lut_index)
         return d_out
 
     def sample_extract_many(self, acc: np.ndarray, n_fn: int, stride: int) -> np.ndarray:

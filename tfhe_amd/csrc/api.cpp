@@ -114,6 +114,8 @@ struct tfhe_shard {
   size_t big_cap = 0;  // bytes
   u64* d_acc = nullptr;  // blind-rotation accumulators of a many-LUT PBS
   size_t acc_cap = 0;    // bytes
+  u64* d_expand = nullptr;  // expanded compact list, the PBS input of tfhe_hip_expand_cast (d_big is the PBS's own)
+  size_t expand_cap = 0;    // bytes
   void* d_stage = nullptr;
   size_t stage_cap = 0;  // bytes
   void* d_ks_dig = nullptr;
@@ -122,7 +124,7 @@ struct tfhe_shard {
   hipStream_t ws_last = nullptr;
   bool ws_used = false;
   // timing: start/stop event pairs per slot (0 = blind rotate, 1 = keyswitch, 2 = MS noise reduction,
-  // 3 = unpack / extract of a decompression)
+  // 3 = the ingest stage of a call: unpack / extract of a decompression, or the expansion of a compact list)
   std::vector<hipEvent_t> ev[TIMING_SLOTS];
   std::vector<hipEvent_t> ev_pool;
 };
@@ -541,6 +543,7 @@ void shard_free(shard& s) {
   (void)hipFree(s.d_ms_zeros);
   (void)hipFree(s.d_big);
   (void)hipFree(s.d_acc);
+  (void)hipFree(s.d_expand);
   (void)hipFree(s.d_stage);
   if (s.ws_free) (void)hipEventDestroy(s.ws_free);
   if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -683,6 +686,73 @@ int decompress_device(tfhe_ctx* c, shard& s, const tfhe_pks_params& pp, const u6
                                       (int)pp.storage_log, s.d_big, st));
   timed_end(c, s, 3, st);
   return bootstrap_device(c, s, s.d_big, count, d_luts, n_lut, d_idx, d_out, st);
+}
+
+constexpr uint32_t EXPAND_MIN_DIM = 8, EXPAND_MAX_DIM = 4096;  // expand.hip: one mask polynomial in 32 KB of LDS (+ 64 bytes)
+
+bool expand_dim_ok(uint32_t d) { return d >= EXPAND_MIN_DIM && d <= EXPAND_MAX_DIM && (d & (d - 1)) == 0; }
+
+// tfhe_hip_expand_*: the checks on the list itself, which need no ctx
+int compact_list_check(const char* what, size_t list_words, uint32_t lwe_dim, size_t count, uint32_t rep, size_t rows) {
+  if (lwe_dim > EXPAND_MAX_DIM && (lwe_dim & (lwe_dim - 1)) == 0)
+    return fail(TFHE_HIP_EUNSUPPORTED, "%s: lwe_dim = %u, the expansion kernel covers lwe_dim <= %u", what, lwe_dim,
+                EXPAND_MAX_DIM);
+  if (!expand_dim_ok(lwe_dim))
+    return fail(TFHE_HIP_EINVAL, "%s: lwe_dim = %u is not a power of two in %u .. %u", what, lwe_dim, EXPAND_MIN_DIM,
+                EXPAND_MAX_DIM);
+  if (count > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "%s: too many ciphertexts", what);
+  const size_t want = tfhe_hip_compact_list_words(lwe_dim, count);
+  if (list_words != want)
+    return fail(TFHE_HIP_EINVAL, "%s: list_words = %zu, %zu ciphertexts of dimension %u take %zu", what, list_words, count,
+                lwe_dim, want);
+  if (rep == 0 || rep > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "%s: rep = %u", what, rep);
+  if (rows > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "%s: rows = %zu, too many rows for one call", what, rows);
+  if (rows > count * (size_t)rep)
+    return fail(TFHE_HIP_EINVAL, "%s: rows = %zu, the list gives %zu x %u", what, rows, count, rep);
+  return 0;
+}
+
+// tfhe_hip_expand_compact*: every check that precedes device work
+int expand_check(const tfhe_ctx* c, const void* list, size_t list_words, uint32_t lwe_dim, size_t count, uint32_t rep,
+                 size_t rows, const void* out) {
+  RC_TRY(compact_list_check("expand_compact", list_words, lwe_dim, count, rep, rows));
+  if (!c) return fail(TFHE_HIP_EINVAL, "expand_compact: null ctx");
+  if (rows && (!list || !out)) return fail(TFHE_HIP_EINVAL, "expand_compact: null buffer");
+  return 0;
+}
+
+// tfhe_hip_expand_cast*: the list's dimension is the ctx's io_dim, so the ctx comes first here
+int expand_cast_check(const tfhe_ctx* c, const void* list, size_t list_words, size_t count, uint32_t rep, size_t rows,
+                      const void* luts, size_t n_lut, const void* out) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "expand_cast: null ctx");
+  const uint32_t dim = io_dim(c->p);
+  if (!expand_dim_ok(dim))
+    return fail(TFHE_HIP_EINVAL, "expand_cast: io_dim = %u is not a power of two in %u .. %u", dim, EXPAND_MIN_DIM,
+                EXPAND_MAX_DIM);
+  RC_TRY(compact_list_check("expand_cast", list_words, dim, count, rep, rows));
+  if (!c->keys) return fail(TFHE_HIP_ENOKEYS, "expand_cast: keys not loaded");
+  if (!n_lut) return fail(TFHE_HIP_EINVAL, "expand_cast: n_lut == 0");
+  if (rows && (!list || !luts || !out)) return fail(TFHE_HIP_EINVAL, "expand_cast: null buffer");
+  return 0;
+}
+
+// Expansion on device buffers (caller as pbs_device), timed in slot 3.
+int expand_device(tfhe_ctx* c, shard& s, const u64* d_list, size_t count, uint32_t lwe_dim, uint32_t rep, size_t rows,
+                  u64* d_out, hipStream_t st) {
+  timed_begin(c, s, 3, st);
+  HIP_TRY(tfhe::launch_expand_compact(d_list, count, (int)lwe_dim, (int)rep, rows, d_out, st));
+  timed_end(c, s, 3, st);
+  return 0;
+}
+
+// Expansion into the shard's d_expand workspace (d_big is pbs_device's own: the keyswitch output in order 1, the
+// rotation output in order 0), then the full PBS unchanged.
+int expand_cast_device(tfhe_ctx* c, shard& s, const u64* d_list, size_t count, uint32_t rep, size_t rows,
+                       const u64* d_luts, size_t n_lut, const u32* d_idx, u64* d_out, hipStream_t st) {
+  const uint32_t dim = io_dim(c->p);
+  RC_TRY(grow(s, (void**)&s.d_expand, &s.expand_cap, rows * ((size_t)dim + 1) * sizeof(u64)));
+  RC_TRY(expand_device(c, s, d_list, count, dim, rep, rows, s.d_expand, st));
+  return pbs_device(c, s, s.d_expand, rows, d_luts, n_lut, d_idx, nullptr, d_out, st);
 }
 
 }  // namespace
@@ -1105,6 +1175,63 @@ int tfhe_hip_decompress(tfhe_ctx* c, const tfhe_pks_params* pp, const uint64_t* 
                      out_bytes, {{lwe_big_out, 3, out_bytes}}, [&](shard& s, std::vector<void*>& d) {
                        return decompress_device(c, s, *pp, (const u64*)d[0], count, (const u64*)d[1], n_lut,
                                                 (const u32*)d[2], (u64*)d[3], s.stream);
+                     });
+}
+
+size_t tfhe_hip_compact_list_words(uint32_t lwe_dim, size_t count) {
+  if (!expand_dim_ok(lwe_dim) || count == 0) return 0;
+  return (count + lwe_dim - 1) / lwe_dim * lwe_dim + count;
+}
+
+int tfhe_hip_expand_compact_async(tfhe_ctx* c, const uint64_t* d_list, size_t list_words, uint32_t lwe_dim, size_t count,
+                                  uint32_t rep, size_t rows, uint64_t* d_lwes_out, void* stream) {
+  RC_TRY(expand_check(c, d_list, list_words, lwe_dim, count, rep, rows, d_lwes_out));
+  if (rows == 0) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  size_t si = 0;
+  RC_TRY(shard_of_input(c, "expand_compact", d_list, &si));
+  shard& s = c->sh[si];
+  DeviceGuard g(s.device);
+  return expand_device(c, s, d_list, count, lwe_dim, rep, rows, d_lwes_out, resolve_stream(stream, s.stream));
+}
+
+int tfhe_hip_expand_compact(tfhe_ctx* c, const uint64_t* list, size_t list_words, uint32_t lwe_dim, size_t count,
+                            uint32_t rep, size_t rows, uint64_t* lwes_out) {
+  RC_TRY(expand_check(c, list, list_words, lwe_dim, count, rep, rows, lwes_out));
+  if (rows == 0) return 0;
+  const size_t out_bytes = rows * ((size_t)lwe_dim + 1) * 8;
+  return staged_call(c, {{list, list_words * 8}}, out_bytes, {{lwes_out, 1, out_bytes}},
+                     [&](shard& s, std::vector<void*>& d) {
+                       return expand_device(c, s, (const u64*)d[0], count, lwe_dim, rep, rows, (u64*)d[1], s.stream);
+                     });
+}
+
+int tfhe_hip_expand_cast_async(tfhe_ctx* c, const uint64_t* d_list, size_t list_words, size_t count, uint32_t rep,
+                               size_t rows, const uint64_t* d_luts, size_t n_lut, const uint32_t* d_idx,
+                               uint64_t* d_out, void* stream) {
+  RC_TRY(expand_cast_check(c, d_list, list_words, count, rep, rows, d_luts, n_lut, d_out));
+  if (rows == 0) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  size_t si = 0;
+  RC_TRY(shard_of_input(c, "expand_cast", d_list, &si));
+  shard& s = c->sh[si];
+  DeviceGuard g(s.device);
+  hipStream_t st = resolve_stream(stream, s.stream);
+  RC_TRY(ws_begin(s, st));
+  RC_TRY(expand_cast_device(c, s, d_list, count, rep, rows, d_luts, n_lut, d_idx, d_out, st));
+  return ws_end(s, st);
+}
+
+int tfhe_hip_expand_cast(tfhe_ctx* c, const uint64_t* list, size_t list_words, size_t count, uint32_t rep, size_t rows,
+                         const uint64_t* luts, size_t n_lut, const uint32_t* lut_index, uint64_t* lwe_out) {
+  RC_TRY(expand_cast_check(c, list, list_words, count, rep, rows, luts, n_lut, lwe_out));
+  RC_TRY(host_lut_index_check("expand_cast", lut_index, rows, n_lut));
+  if (rows == 0) return 0;
+  const size_t out_bytes = rows * ((size_t)io_dim(c->p) + 1) * 8;
+  return staged_call(c, {{list, list_words * 8}, {luts, n_lut * c->p.N * 8}, {lut_index, lut_index ? rows * 4 : 0}},
+                     out_bytes, {{lwe_out, 3, out_bytes}}, [&](shard& s, std::vector<void*>& d) {
+                       return expand_cast_device(c, s, (const u64*)d[0], count, rep, rows, (const u64*)d[1], n_lut,
+                                                 (const u32*)d[2], (u64*)d[3], s.stream);
                      });
 }
 

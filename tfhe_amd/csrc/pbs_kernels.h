@@ -105,4 +105,10 @@ hipError_t launch_sample_extract_many(const u64* acc, size_t B, int k, int N, bo
 // at degree i of group g.  N <= 4096 (hipErrorInvalidValue above), count <= 0x7FFFFFFF
 hipError_t launch_unpack_extract(const u64* packed, size_t count, int k, int N, int lpg, int w, u64* lwes_out,
                                  hipStream_t s);
+// ---- expand.hip: compact-list expansion: `list` = ceil(count / lwe_dim) x lwe_dim mask words, then count body
+// words -> rows x (lwe_dim + 1) LWEs, row r = list entry r / rep (rep >= 1 copies of every entry; rows <= count *
+// rep).  lwe_dim a power of two in 8 .. 4096, count and rows <= 0x7FFFFFFF (hipErrorInvalidValue otherwise);
+// rows == 0 launches nothing
+hipError_t launch_expand_compact(const u64* list, size_t count, int lwe_dim, int rep, size_t rows, u64* out,
+                                 hipStream_t s);
 }  // namespace tfhe

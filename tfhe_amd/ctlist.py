@@ -31,6 +31,14 @@ whose keyswitch key is the CASTING key pke -> small LWE key (same 2^4 x 4 decomp
 bootstrapping key is the normal one turns them, with the "low block" / "high block" LUTs, into radix
 blocks under the computation key -- unpacking and refreshing in one PBS each (tfhe-rs does KS with its
 KeySwitchingKey then a PBS per block).  No other engine change is needed: KS -> PBS is that engine's order.
+
+Two routes lead from a parsed list to radix blocks.  The host route, `expand` + `cast_to_blocks`, expands in
+numpy, doubles every packed LWE on the host and uploads count x 2 x 2049 words in front of the PBS; it states the
+convention and is the reference of the device tests.  The device route, `cast_list_to_blocks` /
+`cast_list_to_blocks_device` (Engine.expand_cast, tfhe_hip_expand_cast), uploads only the list's own words
+(`list_words`: masks then bodies, 32 KB for a full bin); csrc/expand.hip expands them on the device, two rows per
+packed LWE, into a workspace the casting PBS reads, and the device form leaves the blocks resident for
+`Engine.pbs_device`.  `expand_device` is the expansion alone (tfhe_hip_expand_compact, any engine, no key).
 """
 from __future__ import annotations
 
@@ -257,3 +265,47 @@ def cast_to_blocks(cast_engine, expanded: np.ndarray, n_blocks: int) -> np.ndarr
     src = np.repeat(np.arange(expanded.shape[0]), 2)[:n_blocks]
     idx = (np.arange(n_blocks) % 2).astype(np.uint32)
     return cast_engine.pbs(expanded[src], luts, idx)
+
+
+# ---- the device route: the list's words go up, the expansion and the cast run in one call ----------------
+def list_words(cl: CompactList) -> np.ndarray:
+    """The list as tfhe-rs stores it (`data: Vec<u64>`), the input of the device calls: the bins' mask
+    polynomials, then the bodies, one contiguous u64 array of tfhe_hip_compact_list_words(lwe_dim, count)."""
+    return np.concatenate([np.ascontiguousarray(cl.masks, dtype=np.uint64).reshape(-1),
+                           np.ascontiguousarray(cl.bodies, dtype=np.uint64).reshape(-1)])
+
+
+def expand_device(engine, cl: CompactList, rep: int = 1, rows: Optional[int] = None) -> np.ndarray:
+    """`expand` on the engine's device (csrc/expand.hip; any engine, no key needed): (rows, lwe_dim + 1), every
+    list entry in `rep` consecutive rows, `rows` defaulting to count * rep."""
+    return engine.expand_compact(list_words(cl), cl.lwe_dim, cl.count, rep, rows)
+
+
+def _cast_luts(N: int) -> np.ndarray:
+    from . import lut_from_table
+    return np.stack([lut_from_table(N, PACKED_MM, list(T_LO), DELTA_PACKED),
+                     lut_from_table(N, PACKED_MM, list(T_HI), DELTA_PACKED)])
+
+
+def cast_list_to_blocks(cast_engine, cl: CompactList, n_blocks: Optional[int] = None) -> np.ndarray:
+    """`cast_to_blocks(cast_engine, expand(cl), n_blocks)` in one device call (Engine.expand_cast): the list's
+    words are uploaded, expanded two rows per packed LWE (rep = 2) into a device workspace and bootstrapped with
+    the low LUT on even rows and the high LUT on odd rows.  -> (n_blocks, 2049) radix blocks on the host;
+    n_blocks defaults to cl.blocks."""
+    n = cl.blocks if n_blocks is None else int(n_blocks)
+    idx = (np.arange(n) % 2).astype(np.uint32)
+    return cast_engine.expand_cast(list_words(cl), cl.count, _cast_luts(cast_engine.params.N), 2, n, idx)
+
+
+def cast_list_to_blocks_device(cast_engine, cl: CompactList, n_blocks: Optional[int] = None, d_words=None):
+    """The same with the result left on the device: a (n_blocks, 2049) torch tensor on the engine's device, queued
+    on torch's current stream, that `Engine.pbs_device` of the computation engine consumes.  `d_words`: the list's
+    words already resident there (a torch int64 tensor), uploaded from `cl` otherwise."""
+    import torch
+    n = cl.blocks if n_blocks is None else int(n_blocks)
+    dev = torch.device("cuda", cast_engine.device)
+    if d_words is None:
+        d_words = torch.from_numpy(list_words(cl).view(np.int64)).to(dev)
+    d_luts = torch.from_numpy(_cast_luts(cast_engine.params.N).view(np.int64)).to(dev)
+    d_idx = (torch.arange(n, dtype=torch.int32, device=dev) % 2).contiguous()
+    return cast_engine.expand_cast_device(d_words, cl.count, d_luts, 2, n, d_idx)
