@@ -429,11 +429,20 @@ int tfhe_hip_sns_create(const tfhe_sns_params* sp, int device, tfhe_sns_ctx** ou
 void tfhe_hip_sns_destroy(tfhe_sns_ctx* ctx);
 /* Loading rounds every key word (read as a signed 128-bit integer) to the nearest multiple of 2^16
  * (oracle: or_sns_bsk_round; ~2^20 of extra phase noise beside the key's 2^30).  The external product
- * splits the rounded key into seven 16-bit limbs and computes each digit x limb convolution as an
- * exact f64 FFT product (n x 9 x 3 x 7 x 1024 complex of key spectra: 2.8 GB at n = 918). */
+ * splits the rounded key into five limbs, the balanced low 48 bits and four balanced 16-bit limbs, and
+ * computes each digit x limb convolution as an f64 FFT product, exact for the 16-bit limbs
+ * (n x 9 x 3 x 5 x 1024 complex of key spectra: 2.03 GB at n = 918).  Waits for every call still in
+ * flight on the ctx before it rewrites the resident key. */
 int tfhe_hip_sns_load_key(tfhe_sns_ctx* ctx, const uint64_t* bsk, size_t len);
-/* B small-key ciphertexts (B x (n+1)) -> B x (k*N+1) x 2 u64; identity LUT over msg_modulus values */
+/* B small-key ciphertexts (B x (n+1)) -> B x (k*N+1) x 2 u64; identity LUT over msg_modulus values
+ * (a divisor of N; EINVAL otherwise, before any device work).  Host buffers, synchronous. */
 int tfhe_hip_sns_squash(tfhe_sns_ctx* ctx, const uint64_t* lwe_small, size_t B, uint32_t msg_modulus, uint64_t* out);
+/* Device buffers, enqueued on `stream` (NULL = the ctx's stream, TFHE_HIP_NULL_STREAM = the legacy null
+ * stream), in chunks of TFHE_HIP_SNS_CHUNK (512) ciphertexts.  The accumulators, spectra and the LUT are shared
+ * by every call on the ctx: calls on different streams, host calls included, are ordered on them by an event (a
+ * later call waits for the previous one's kernels on its own stream, and the host waits for them before it
+ * rewrites the LUT for another msg_modulus or regrows a workspace), so a call may follow another at once,
+ * on any stream, without a synchronisation by the caller. */
 int tfhe_hip_sns_squash_async(tfhe_sns_ctx* ctx, const uint64_t* d_lwe_small, size_t B, uint32_t msg_modulus,
                               uint64_t* d_out, void* stream);
 /* stage-level (parity tests): accumulator after the CMUX loop, B x (k+1) x (lo, hi) x N words */

@@ -6,6 +6,7 @@ reduction -> 128-bit bootstrap) decrypting every message with ~2^-63 noise."""
 import numpy as np
 import pytest
 
+import sns_inputs as I
 from conftest import KEY_SEED
 from tfhe_amd import sns as S
 
@@ -170,3 +171,86 @@ def test_device_arithmetic_replay_matches_oracle(tmp_path):
                     f"-Wl,-rpath,{root}/oracle", "-o", str(exe)], check=True)
     out = subprocess.run([str(exe), "24", "3"], capture_output=True, text=True)
     assert out.returncode == 0 and "OK: device arithmetic == oracle" in out.stdout, out.stdout + out.stderr
+
+
+# ---- the inputs of tests/test_gpu_sns_edges.py reach what they aim at (oracle alone) ----------------------------
+
+def test_tie_inputs_reach_rounding_ties(oracle_mod):
+    """The "ties" key with tie_inputs: the difference words y = X^{a} acc - acc entering CMUX 2 and later whose low
+    56 bits are exactly 2^55 (half of the last bit the 72-bit decomposition keeps: the closest-representable rounding
+    is a tie and goes up).  At least 32 of them, some decomposing with a digit carry and some without; the Python
+    digits72 recomposes to the rounded word."""
+    sp, osp = I.small_params(oracle_mod, I.TIE_N)
+    okeys = oracle_mod.SnsKeys(osp, KEY_SEED, np.zeros(I.TIE_N, dtype=np.uint64))
+    I.load_synthetic(okeys, I.synthetic_key(sp, "ties", I.TIE_SEED))
+    lut = oracle_mod.sns_lut_identity(osp, 16)
+    ties, with_carry, without = 0, 0, 0
+    per_cmux = {}
+    for ct in I.tie_inputs():
+        for i in range(1, I.TIE_N):
+            y = I.cmux_differences(oracle_mod, osp, okeys, ct, lut, i)
+            hit = (y[:, 0] & np.uint64((1 << 56) - 1)) == np.uint64(1 << 55)
+            per_cmux[i + 1] = per_cmux.get(i + 1, 0) + int(hit.sum())
+            for c, t in zip(*np.nonzero(hit)):
+                w = int(y[c, 0, t]) | (int(y[c, 1, t]) << 64)
+                d, carries = I.digits72(w)
+                assert all(-(1 << 23) <= v <= (1 << 23) for v in d)
+                assert sum(v << (104 - 24 * l) for l, v in enumerate(d)) % (1 << 128) == ((w >> 56) + 1 << 56) % (1 << 128)
+                ties += 1
+                with_carry += any(carries)
+                without += not any(carries)
+    print(f"ties {ties} (per CMUX {per_cmux}), decomposed with a carry {with_carry}, without {without}")
+    assert ties >= 32 and with_carry >= 1 and without >= 1
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 7])
+def test_edge_inputs_cover_the_modulus_switch(n):
+    """edge_inputs at the device tests' shape (B = 16): the raw edge words are present, masks and bodies each switch
+    to 0 by the wrap from 2^64 - 2^51 and to 1, 2047, 2048, 2049 and 4095; one mask is all zero, one all 2^63."""
+    cts = I.edge_inputs(n, 16, 0xED6E + n)
+    assert cts.shape == (16, n + 1) and cts.dtype == np.uint64
+    for part in (cts[:, :n].reshape(-1), cts[:, n]):
+        assert set(I.RAW) <= set(int(v) for v in part)
+        sw = I.mod_switch_4096(part)
+        assert I.mod_switch_4096(I.WRAP) == 0 and I.WRAP in part
+        assert set(I.SWITCHED) <= set(int(v) for v in sw)
+    assert not cts[14, :n].any() and (cts[15, :n] == np.uint64(1 << 63)).all()
+    assert [int(v) for v in I.mod_switch_4096(np.array(I.RAW, dtype=np.uint64))] == [0, 0, 0, 1, 1, 2, 0]
+
+
+def test_limb_edges_key_limbs(oracle_mod):
+    """The "limb_edges" key: after the load rounding (which removes the random low 16 bits) every limb of every
+    sampled word is at an end of its balanced range, both ends of every limb occur, and the limbs recombine to the
+    rounded word (limbs recovered as in test_key_rounding_and_limbs)."""
+    import ctypes
+    sp, osp = I.small_params(oracle_mod, 1)
+    okeys = oracle_mod.SnsKeys(osp, KEY_SEED, np.array([1], dtype=np.uint64))
+    I.load_synthetic(okeys, I.synthetic_key(sp, "limb_edges", 11))
+    out = np.zeros_like(okeys.bsk)
+    oracle_mod.lib().or_sns_bsk_round(ctypes.byref(osp), oracle_mod._p(okeys.bsk), oracle_mod._p(out))
+    words, rounded = _words(okeys.bsk.reshape(-1, 2, 2048)), _words(out.reshape(-1, 2, 2048))
+    limb = okeys.bsk_limb.reshape(-1, 5, 2048)
+    p1 = 0xFFFFFFFF00000001
+    signed = lambda v: v - (1 << 128) if v >> 127 else v
+    order = np.array([_digitrev4(q) for q in range(1024)])
+    psi = np.exp(1j * np.pi * np.arange(1024) / 2048)
+    seen = [set() for _ in range(5)]
+    for pp in np.random.default_rng(6).integers(0, len(words), 4):
+        lv = [oracle_mod.sns_ntt(0, limb[pp, t].copy(), inverse=True) for t in range(1, 5)]
+        low = np.zeros(2048)
+        for t in range(2048):
+            x, y = signed(words[pp][t]), signed(rounded[pp][t])
+            assert y % 65536 == 0 and abs(y - x) <= 32768
+            ls = [int(v[t]) - p1 if int(v[t]) > p1 // 2 else int(v[t]) for v in lv]
+            assert all(v in (-32768, 32767) for v in ls[:3]) and ls[3] in (-32768, 32767, 32768)
+            assert ls[3] != 32768 or ls[2] == -32768
+            m = signed((rounded[pp][t] - sum(v << (64 + 16 * u) for u, v in enumerate(ls))) % (1 << 128))
+            assert m % 65536 == 0 and (m >> 16) in (-(1 << 47), (1 << 47) - 1)
+            low[t] = m >> 16
+            for u, v in enumerate([m >> 16] + ls):
+                seen[u].add(v)
+        spec = limb[pp, 0].view(np.float64).reshape(1024, 2)
+        spec = spec[:, 0] + 1j * spec[:, 1]
+        want = np.fft.ifft((low[:1024] + 1j * low[1024:]) * psi)
+        assert np.max(np.abs(spec - want[order])) <= 2 ** -40 * np.max(np.abs(want))
+    assert [len(s) for s in seen] == [2, 2, 2, 2, 3]

@@ -51,6 +51,11 @@ struct tfhe_sns_ctx {
   u64* d_lut = nullptr;
   uint32_t lut_mm = 0;
   size_t ws_cap = 0;
+  // d_acc, d_D, d_O, d_lut and the key are shared by every call: each user waits for `ws_free` (the previous
+  // user's completion) on its own stream, as the engine shards do (api.cpp ws_begin / ws_end)
+  hipEvent_t ws_free = nullptr;
+  hipStream_t ws_last = nullptr;
+  bool ws_used = false;
   u64* d_io = nullptr;
   size_t io_cap = 0;
   std::mutex mu;
@@ -58,8 +63,27 @@ struct tfhe_sns_ctx {
 
 namespace {
 
+// Workspace ordering across streams (tfhe_hip_sns_squash_async may be called on any stream): the stream that uses
+// the workspaces next waits for the event recorded after the previous use; the host waits for it before it frees
+// or rewrites a buffer that enqueued kernels may still read.
+int ws_begin(tfhe_sns_ctx* c, hipStream_t st) {
+  if (c->ws_used && c->ws_last != st) HIP_TRY(hipStreamWaitEvent(st, c->ws_free, 0));
+  return 0;
+}
+int ws_end(tfhe_sns_ctx* c, hipStream_t st) {
+  HIP_TRY(hipEventRecord(c->ws_free, st));
+  c->ws_last = st;
+  c->ws_used = true;
+  return 0;
+}
+int ws_host_wait(tfhe_sns_ctx* c) {
+  if (c->ws_used) HIP_TRY(hipEventSynchronize(c->ws_free));
+  return 0;
+}
+
 int ensure_ws(tfhe_sns_ctx* c, size_t B) {
   if (c->ws_cap >= B) return 0;
+  RC_TRY(ws_host_wait(c));  // no launch may still use the old buffers
   (void)hipFree(c->d_acc);
   (void)hipFree(c->d_D);
   (void)hipFree(c->d_O);
@@ -78,6 +102,7 @@ int ensure_lut(tfhe_sns_ctx* c, uint32_t mm) {
   if (c->d_lut && c->lut_mm == mm) return 0;
   std::vector<u64> lut(2 * (size_t)c->sp.N);
   tfhe::client::sns_lut_identity(c->sp, mm, lut.data());
+  RC_TRY(ws_host_wait(c));  // a call in flight on another stream still reads the previous modulus' LUT
   if (!c->d_lut) HIP_TRY(hipMalloc(&c->d_lut, lut.size() * 8));
   HIP_TRY(hipMemcpy(c->d_lut, lut.data(), lut.size() * 8, hipMemcpyHostToDevice));
   c->lut_mm = mm;
@@ -88,6 +113,7 @@ int ensure_lut(tfhe_sns_ctx* c, uint32_t mm) {
 int run_device(tfhe_sns_ctx* c, const u64* d_in, size_t B, u64* d_out, u64* d_acc_out, hipStream_t s) {
   const size_t chunk = std::min(B, sns_chunk());
   RC_TRY(ensure_ws(c, chunk));
+  RC_TRY(ws_begin(c, s));
   const size_t in_dim = c->sp.n + 1, out_dim = 2 * ((size_t)c->sp.k * c->sp.N + 1);
   const size_t acc_len = (size_t)(c->sp.k + 1) * 2 * c->sp.N;
   for (size_t f = 0; f < B; f += chunk) {
@@ -98,7 +124,7 @@ int run_device(tfhe_sns_ctx* c, const u64* d_in, size_t B, u64* d_out, u64* d_ac
     if (d_acc_out)
       HIP_TRY(hipMemcpyAsync(d_acc_out + f * acc_len, c->d_acc, nb * acc_len * 8, hipMemcpyDeviceToDevice, s));
   }
-  return 0;
+  return ws_end(c, s);
 }
 
 int host_call(tfhe_sns_ctx* c, const u64* in, size_t B, uint32_t mm, u64* out, bool acc_only) {
@@ -164,6 +190,7 @@ int tfhe_hip_sns_create(const tfhe_sns_params* sp, int device, tfhe_sns_ctx** ou
   std::vector<unsigned char> F(tfhe::sns_fft_const_bytes());
   tfhe::make_sns_fft_const(F.data());
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ws_free, hipEventDisableTiming) != hipSuccess ||
       hipMalloc(&c->d_fconst, F.size()) != hipSuccess ||
       hipMemcpy(c->d_fconst, F.data(), F.size(), hipMemcpyHostToDevice) != hipSuccess) {
     tfhe_hip_sns_destroy(c);
@@ -178,8 +205,10 @@ void tfhe_hip_sns_destroy(tfhe_sns_ctx* c) {
   {
     DeviceGuard g(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->ws_used) (void)hipEventSynchronize(c->ws_free);  // a caller's stream may still run on the workspaces
     for (void* p : {c->d_fconst, c->d_bskf, (void*)c->d_acc, c->d_D, c->d_O, (void*)c->d_lut, (void*)c->d_io})
       (void)hipFree(p);
+    if (c->ws_free) (void)hipEventDestroy(c->ws_free);
     if (c->stream) (void)hipStreamDestroy(c->stream);
   }
   delete c;
@@ -191,6 +220,7 @@ int tfhe_hip_sns_load_key(tfhe_sns_ctx* c, const uint64_t* bsk, size_t len) {
     return fail(TFHE_HIP_EINVAL, "sns_load_key: length %zu, expected %zu", len, tfhe::client::sns_bsk_len(c->sp));
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
+  RC_TRY(ws_host_wait(c));  // a call in flight on a caller's stream still reads the resident key
   c->key = false;
   if (!c->d_bskf) HIP_TRY(hipMalloc(&c->d_bskf, tfhe::sns_fft_key_len(c->sp.n) * 16));
   // stage the key words in chunks of polynomials (lo, hi planes) through the io buffer, convert to limb spectra
