@@ -84,7 +84,7 @@ __device__ __forceinline__ u32 decomp_state_not(u64 S) { return (1023u - (u32)(S
 // the top level (b = 0, no next state), as a double: 2 integer VALU per digit.  A top state is 0 <= st <= 128, and there
 // st - ((st + 63) & ~127) = -sext7(-st) (every st checked in tests/test_pair_int_forms.py): v_sub_u32, v_bfe_i32, the
 // conversion, and a negation that rides in the source modifiers of the f64 consumers.  (In inline asm: hipcc's known-bits
-// have mis-folded an sbfe builtin in rotate_states below.)  The one difference from (double)(int) is a zero digit, -0.0
+// have mis-folded an sbfe builtin in rotation_states below.)  The one difference from (double)(int) is a zero digit, -0.0
 // here: it can change only the sign of exact zeros downstream (mac_first's argument: a sum or an fma with a non-zero
 // term does not see the sign of a zero term, products and sums of zeros stay zeros), and the accumulator update
 // (torus_acc_add_y) takes floor(y), y - floor(y) and the words of both plus non-zero magic numbers, which are the same
@@ -234,25 +234,62 @@ typedef __attribute__((address_space(3))) u64 lds_u64;
 // (xor s) depend only on the SGPR comparison e < A.  Per slot 8 VALU instead of the 10 of a per-lane compare and
 // negate-and-select (y = (x ^ M) - (v + M), M = 0 or all ones); the values are the same, so no operation order changes.
 // Since round 8 the difference is taken as the complement of a sum, 7 VALU per slot (below).
-__device__ __forceinline__ void rotate_states(const u64 (&v)[16], int a, int lane, double2* T, u32 (&st)[16]) {
-  u64* Tu = (u64*)T;
-  a = __builtin_amdgcn_readfirstlane(a);  // ms2048(ct[i]): the same for every lane
-  const int A = (a >> 6) & 15, r = a & 63;
-  const bool sgn = a >= 1024;
-  {
-    const u32 wb = (u32)(uintptr_t)(lds_u64*)&Tu[lane + r];
-#pragma unroll
-    for (int e = 0; e < 15; e++) ((lds_u64*)(uintptr_t)wb)[64 * e] = v[e];
-    const bool w15 = lane + r >= 64;  // coefficient 960 + L + r >= 1024: to L + r - 64, negated
-    const u32 a15 = w15 ? wb + 960u * 8u - 8192u : wb + 960u * 8u;
-    *(lds_u64*)(uintptr_t)a15 = w15 ? 0 - v[15] : v[15];
+// In two halves since round 10 (one function, rotate_states, until then): the image stores
+// (rotation_store_pair) and the reads with the differences (rotation_states).  The stores of CMUX i + 1's image go out slot pair by slot pair under the accumulator update of
+// CMUX i, whose amount a is an SGPR from level step 0 of CMUX i on; as one group behind the update they were a burst of
+// nine DS stores and a full drain at every CMUX's head with the wave issuing nothing else.
+// The write base of the image for the amount a: word L + r of the area; w15 = this lane's slot 15 wraps.  Slots 0..14
+// end at word 63 + 63 + 896 = 1022 and slot 15 lands at L + r + 960 <= 1023 or wraps to L + r - 64 >= 0: inside the
+// area's 1152 words for every a, also for an amount nobody rotates by (the body word's, behind the last CMUX)
+struct RotW {
+  u32 wb;
+  bool w15;
+  __device__ __forceinline__ RotW(int a, int lane, double2* T)
+      : wb((u32)(uintptr_t)(lds_u64*)&((u64*)T)[lane + (a & 63)]), w15(lane + (a & 63) >= 64) {}
+};
+// slots E and E + 1 of the image (two words 512 B apart: one ds_write2st64_b64); slot 15 keeps its per-lane wrap
+// (coefficient 960 + L + r >= 1024: to L + r - 64, negated)
+template <int E>
+__device__ __forceinline__ void rotation_store_pair(u64 v0, u64 v1, RotW w) {
+  ((lds_u64*)(uintptr_t)w.wb)[64 * E] = v0;
+  if constexpr (E < 14) {
+    ((lds_u64*)(uintptr_t)w.wb)[64 * (E + 1)] = v1;
+  } else {
+    const u32 a15 = w.w15 ? w.wb + 960u * 8u - 8192u : w.wb + 960u * 8u;
+    *(lds_u64*)(uintptr_t)a15 = w.w15 ? 0 - v1 : v1;
   }
-  lds_order();
+}
+// the whole image at once (the prologue: CMUX 0's)
+__device__ __forceinline__ void rotation_store(const u64 (&v)[16], int a, int lane, double2* T) {
+  const RotW w(a, lane, T);
+  rotation_store_pair<0>(v[0], v[1], w);
+  rotation_store_pair<2>(v[2], v[3], w);
+  rotation_store_pair<4>(v[4], v[5], w);
+  rotation_store_pair<6>(v[6], v[7], w);
+  rotation_store_pair<8>(v[8], v[9], w);
+  rotation_store_pair<10>(v[10], v[11], w);
+  rotation_store_pair<12>(v[12], v[13], w);
+  rotation_store_pair<14>(v[14], v[15], w);
+}
+// The reads of the image stored for the amount a (uniform: an SGPR), the differences and the states.  No drain between
+// the wave's own stores and these reads (DS operations of one wave execute in issue order): a compiler-level fence, and
+// the sixteen reads pinned as one group and consumed under counted waits, as xpose_p's are
+__device__ __forceinline__ void rotation_states(const u64 (&v)[16], int a, int lane, double2* T, u32 (&st)[16]) {
+  u64* Tu = (u64*)T;
+  const int A = (a >> 6) & 15;
+  const bool sgn = a >= 1024;
   const u32 rb = (u32)(uintptr_t)(lds_u64*)&Tu[lane] - 512u * (u32)A;  // >= T - 7.5 KB: inside the block
   // bit e of wmask: slot e reads the wrapped part (e < A); bit e of mbits: slot e negated.  Bit-field extracts of
   // these SGPR words keep every per-slot decision scalar (a compare would be rebuilt as a per-lane select)
   const u32 wmask = (1u << A) - 1u;
   const u64 mbits = (u32)__builtin_amdgcn_readfirstlane(wmask ^ (sgn ? ~0u : 0u));
+  u64 x[16];
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int e = 0; e < 16; e++)
+    x[e] = ((const lds_u64*)(uintptr_t)(rb + (__builtin_amdgcn_ubfe(wmask, e, 1) << 13)))[64 * e];
+  __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int e = 0; e < 16; e++) {
     // s_bfe_i64 (0 or all ones, both words in ONE scalar instruction) in inline asm: hipcc's known-bits treat the
@@ -262,11 +299,10 @@ __device__ __forceinline__ void rotate_states(const u64 (&v)[16], int a, int lan
     // replaced, this one 0.19 ms faster
     u64 M;
     asm("s_bfe_i64 %0, %1, %2" : "=s"(M) : "s"(mbits), "i"(e | (1 << 16)));
-    const u64 x = ((const lds_u64*)(uintptr_t)(rb + (__builtin_amdgcn_ubfe(wmask, e, 1) << 13)))[64 * e];
     // (x ^ M) - (v + M) = ~((x ^ ~M) + (v + M)), exact in all 64 bits (-(x ^ ~M) = (x ^ M) + 1): two 64-bit adds (one
     // v_lshl_add_u64 each) instead of an add and a two-instruction subtract; the complement folds into the state.
     // x ^ ~M = ~(x ^ M) is one v_xnor_b32 per word
-    st[e] = decomp_state_not(~(x ^ M) + (v[e] + M));
+    st[e] = decomp_state_not(~(x[e] ^ M) + (v[e] + M));
   }
   lds_order();
 }
@@ -430,11 +466,12 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
   auto ms2048_hi = [](u32 hi) { return (int)((((hi >> 20) + 1u) >> 1) & 2047u); };
   const u32* ct_hi = (const u32*)ct + 1;
   int a_s = __builtin_amdgcn_readfirstlane(ms2048_hi(ct_hi[0]));
+  rotation_store(acc, a_s, lane, T);  // CMUX 0's image; every later one is stored under the update before it
   for (int i = 0; i < n; i++) {
     // (X^a acc_c - acc_c), decomposed: the rotation image in this wave's own transpose area (its previous
     // user, the last inverse, is this wave: DS operations of a wave run in order)
     u32 st[16];
-    rotate_states(acc, a_s, lane, T, st);
+    rotation_states(acc, a_s, lane, T, st);
     // the next CMUX's mask word (i = n - 1: the body word, ignored), issued ahead of level step 0's chunk and
     // consumed behind that step's glds_barrier
     u32 ct_next = ct_hi[2 * (size_t)(i + 1)];
@@ -534,10 +571,26 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
     else exchange_partials<0>(o0r, o0i, o1r, o1i, xr, xi, T, Tp, lane);
     dft512_inv_rb_p(xr, xi, T, lane, tb, wb, twI);
     twist_slots<true>(xr, xi);
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      acc[e] = torus_acc_add_y(acc[e], xr[e]);
-      acc[e + 8] = torus_acc_add_y(acc[e + 8], xi[e]);
+    {
+      // the image of CMUX i + 1 (a_s is its amount since level step 0), each slot pair stored as its words become
+      // final; the area's last user, the inverse's second transpose, has been read
+      const RotW w(a_s, lane, T);
+      auto upd = [&](auto ec) {
+        constexpr int e = decltype(ec)::value;
+        acc[e] = torus_acc_add_y(acc[e], e < 8 ? xr[e & 7] : xi[e & 7]);
+        acc[e + 1] = torus_acc_add_y(acc[e + 1], e < 8 ? xr[(e + 1) & 7] : xi[(e + 1) & 7]);
+        rotation_store_pair<e>(acc[e], acc[e + 1], w);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      __builtin_amdgcn_sched_barrier(0);
+      upd(std::integral_constant<int, 0>{});
+      upd(std::integral_constant<int, 2>{});
+      upd(std::integral_constant<int, 4>{});
+      upd(std::integral_constant<int, 6>{});
+      upd(std::integral_constant<int, 8>{});
+      upd(std::integral_constant<int, 10>{});
+      upd(std::integral_constant<int, 12>{});
+      upd(std::integral_constant<int, 14>{});
     }
   }
 #if FFT_DMASTAMP
