@@ -6,6 +6,8 @@
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "gl64.h"
 #include "ntt1024.h"
 
@@ -53,53 +55,86 @@ __device__ __forceinline__ void w8(double& re, double& im) {
 // stages (4 multiplies fewer), -48 per wave and CMUX in the P-GATE pair kernel.  The rounding sequence is restated in
 // oracle/fft_oracle.c:dft8 (and judged by the exact arbiter).
 // 8-point DFT in registers, natural order in and out (radix-2 DIF, bit-reversal by renaming)
+// In pieces (round 11), so that the pair kernel's transposes can take the last stage output by output (dft8_xpose_p
+// below); dft8 itself runs the pieces in the order it always had.
+template <bool INV>
+struct Dft8 {
+  double yr[4], yi[4], tr[4], ti[4];                  // stage 1: y_j = x_j + x_(j+4), t_j = x_j - x_(j+4)
+  double ar, ai, cr, ci;                              // u5 = (ar, ai), u7 = (cr, ci), unscaled
+  double z5r, z5i, z7r, z7i, z4r, z4i, z6r, z6i;      // z5 / s, z7 / s (before its rotation by +-i), z4, z6
+  double e0r, e0i, e1r, e1i, e2r, e2i, e3r, e3i;      // even half after stage 2 (e3 rotated)
+
+  __device__ __forceinline__ void stage1(const double (&xr)[8], const double (&xi)[8]) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      yr[j] = xr[j] + xr[j + 4];
+      yi[j] = xi[j] + xi[j + 4];
+    }
+    // odd half: y4 = t0, y6 = (+-i) t2, y5 / y7 = s u5 / s u7 (u5, u7 kept unscaled)
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      tr[j] = xr[j] - xr[j + 4];
+      ti[j] = xi[j] - xi[j + 4];
+    }
+  }
+  __device__ __forceinline__ void odd_u() {
+    if (!INV) {
+      ar = tr[1] - ti[1]; ai = tr[1] + ti[1];        // w8^1 / s
+      cr = -(tr[3] + ti[3]); ci = tr[3] - ti[3];     // w8^3 / s
+    } else {
+      ar = tr[1] + ti[1]; ai = ti[1] - tr[1];
+      cr = ti[3] - tr[3]; ci = -(tr[3] + ti[3]);
+    }
+  }
+  __device__ __forceinline__ void odd_z57() {
+    z5r = ar + cr; z5i = ai + ci;
+    z7r = ar - cr; z7i = ai - ci;
+  }
+  // z4 = y4 + y6, z6 = y4 - y6 with y6 = (+-i) t2
+  __device__ __forceinline__ void odd_z46() {
+    z4r = INV ? tr[0] + ti[2] : tr[0] - ti[2]; z4i = INV ? ti[0] - tr[2] : ti[0] + tr[2];
+    z6r = INV ? tr[0] - ti[2] : tr[0] + ti[2]; z6i = INV ? ti[0] + tr[2] : ti[0] - tr[2];
+  }
+  __device__ __forceinline__ void even2() {
+    e0r = yr[0] + yr[2]; e0i = yi[0] + yi[2];
+    e2r = yr[0] - yr[2]; e2i = yi[0] - yi[2];
+    e1r = yr[1] + yr[3]; e1i = yi[1] + yi[3];
+    e3r = yr[1] - yr[3]; e3i = yi[1] - yi[3];
+    w8<INV, 2>(e3r, e3i);
+  }
+  // The last stage, one output (two instructions) at a time.  Even half: x0, x4 = e0 +- e1, x2, x6 = e2 +- e3.  Odd half
+  // with s folded: x1, x5 = z4 +- s z5', x3, x7 = z6 +- r(s z7'), r = multiplication by +i (forward: r z = (-z.im, z.re))
+  // / -i (inverse: r z = (z.im, -z.re))
+  template <int E>
+  __device__ __forceinline__ void out(double& re, double& im) const {
+    if constexpr (E == 0) { re = e0r + e1r; im = e0i + e1i; }
+    if constexpr (E == 4) { re = e0r - e1r; im = e0i - e1i; }
+    if constexpr (E == 2) { re = e2r + e3r; im = e2i + e3i; }
+    if constexpr (E == 6) { re = e2r - e3r; im = e2i - e3i; }
+    if constexpr (E == 1) { re = __builtin_fma(SQRT1_2, z5r, z4r); im = __builtin_fma(SQRT1_2, z5i, z4i); }
+    if constexpr (E == 5) { re = __builtin_fma(-SQRT1_2, z5r, z4r); im = __builtin_fma(-SQRT1_2, z5i, z4i); }
+    constexpr double S3 = INV ? SQRT1_2 : -SQRT1_2;
+    if constexpr (E == 3) { re = __builtin_fma(S3, z7i, z6r); im = __builtin_fma(-S3, z7r, z6i); }
+    if constexpr (E == 7) { re = __builtin_fma(-S3, z7i, z6r); im = __builtin_fma(S3, z7r, z6i); }
+  }
+};
+
 template <bool INV>
 __device__ __forceinline__ void dft8(double (&xr)[8], double (&xi)[8]) {
-  double yr[4], yi[4];  // stage 1, even half: y_j = x_j + x_(j+4)
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    yr[j] = xr[j] + xr[j + 4];
-    yi[j] = xi[j] + xi[j + 4];
-  }
-  // odd half: t_j = x_j - x_(j+4); y4 = t0, y6 = (+-i) t2, y5 / y7 = s u5 / s u7 (u5, u7 kept unscaled)
-  const double t0r = xr[0] - xr[4], t0i = xi[0] - xi[4];
-  const double t1r = xr[1] - xr[5], t1i = xi[1] - xi[5];
-  const double t2r = xr[2] - xr[6], t2i = xi[2] - xi[6];
-  const double t3r = xr[3] - xr[7], t3i = xi[3] - xi[7];
-  double ar, ai, cr, ci;  // u5 = (ar, ai), u7 = (cr, ci)
-  if (!INV) {
-    ar = t1r - t1i; ai = t1r + t1i;        // w8^1 / s
-    cr = -(t3r + t3i); ci = t3r - t3i;     // w8^3 / s
-  } else {
-    ar = t1r + t1i; ai = t1i - t1r;
-    cr = t3i - t3r; ci = -(t3r + t3i);
-  }
-  const double z5r = ar + cr, z5i = ai + ci;  // z5 / s
-  const double z7r = ar - cr, z7i = ai - ci;  // z7 / s (before its rotation by +-i)
-  // z4 = y4 + y6, z6 = y4 - y6 with y6 = (+-i) t2
-  const double z4r = INV ? t0r + t2i : t0r - t2i, z4i = INV ? t0i - t2r : t0i + t2r;
-  const double z6r = INV ? t0r - t2i : t0r + t2i, z6i = INV ? t0i + t2r : t0i - t2r;
-  // even half: stages 2 and 3 as before
-  const double e0r = yr[0] + yr[2], e0i = yi[0] + yi[2];
-  const double e2r = yr[0] - yr[2], e2i = yi[0] - yi[2];
-  const double e1r = yr[1] + yr[3], e1i = yi[1] + yi[3];
-  double e3r = yr[1] - yr[3], e3i = yi[1] - yi[3];
-  w8<INV, 2>(e3r, e3i);
-  xr[0] = e0r + e1r; xi[0] = e0i + e1i;
-  xr[4] = e0r - e1r; xi[4] = e0i - e1i;
-  xr[2] = e2r + e3r; xi[2] = e2i + e3i;
-  xr[6] = e2r - e3r; xi[6] = e2i - e3i;
-  // odd half, stage 3 with s folded: x1 = z4 + s z5', x5 = z4 - s z5', x3 = z6 + r(s z7'), x7 = z6 - r(s z7'),
-  // r = multiplication by +i (forward) / -i (inverse)
-  xr[1] = __builtin_fma(SQRT1_2, z5r, z4r); xi[1] = __builtin_fma(SQRT1_2, z5i, z4i);
-  xr[5] = __builtin_fma(-SQRT1_2, z5r, z4r); xi[5] = __builtin_fma(-SQRT1_2, z5i, z4i);
-  if (!INV) {  // r z = (-z.im, z.re)
-    xr[3] = __builtin_fma(-SQRT1_2, z7i, z6r); xi[3] = __builtin_fma(SQRT1_2, z7r, z6i);
-    xr[7] = __builtin_fma(SQRT1_2, z7i, z6r); xi[7] = __builtin_fma(-SQRT1_2, z7r, z6i);
-  } else {     // r z = (z.im, -z.re)
-    xr[3] = __builtin_fma(SQRT1_2, z7i, z6r); xi[3] = __builtin_fma(-SQRT1_2, z7r, z6i);
-    xr[7] = __builtin_fma(-SQRT1_2, z7i, z6r); xi[7] = __builtin_fma(SQRT1_2, z7r, z6i);
-  }
+  Dft8<INV> d;
+  d.stage1(xr, xi);
+  d.odd_u();
+  d.odd_z57();
+  d.odd_z46();
+  d.even2();
+  d.template out<0>(xr[0], xi[0]);
+  d.template out<4>(xr[4], xi[4]);
+  d.template out<2>(xr[2], xi[2]);
+  d.template out<6>(xr[6], xi[6]);
+  d.template out<1>(xr[1], xi[1]);
+  d.template out<5>(xr[5], xi[5]);
+  d.template out<3>(xr[3], xi[3]);
+  d.template out<7>(xr[7], xi[7]);
 }
 
 // 64-bit register exchanges across the wave: v_permlane32_swap / v_permlane16_swap (gfx950: each swaps one operand's upper
@@ -150,7 +185,7 @@ struct TBase {
 // (no 1/M): device order in, natural order out -- the forward's passes reversed, the twiddles conjugated: pass C' takes
 // pass B's table, pass B' the TW_I table.  Two forms of each: every twiddle from a table (twA, twB, twI: 512
 // complex each, [64 e + L]; TW_A | TW_B | TW_I of the table tw) with plain transposes -- multiply, store, full drain, load, full drain -- and the
-// pair kernel's, with pass A's and pass B's twiddles in registers and the transposes placed by hand (xpose_p below).
+// pair kernel's, with pass A's and pass B's twiddles in registers and each transpose fused with the DFT8 in front of it and placed by hand (dft8_xpose_p below).
 __device__ __forceinline__ void dft512_fwd_t(double (&xr)[8], double (&xi)[8], double2* T, int lane, TBase tb,
                                              const double2* twA, const double2* twB) {
   twist_dft8_fwd(xr, xi);
@@ -222,30 +257,55 @@ __device__ __forceinline__ void dft512_inv(double (&xr)[8], double (&xi)[8], dou
   dft512_inv_t(xr, xi, T, lane, tb, tw + TW_B, tw + TW_I);
 }
 
-// One transpose with the twiddles w[e] in registers and its LDS traffic placed by hand (round 7): slots E0.. times w
-// (INV: conj w), stores at Tw[WS e], reads from Tr[RS e].  Pure placement of stores, loads
-// and waits: the f64 operations, their operands and their order are those of the plain transposes above.
-//   * per slot, the twiddle multiply and then that slot's transpose store, the order pinned, so a ds_write_b128 goes out
-//     under the next slot's four f64 instructions (hipcc's own schedule is all eight multiplies, a full drain, then eight
-//     stores back to back with the wave issuing nothing else);
-//   * no s_waitcnt between the stores and the reads of the same private area (DS operations of one wave execute in issue
+// A DFT8 and the transpose behind it as one, with the twiddles w[e] in registers and the LDS traffic placed by hand
+// (rounds 7 and 11): slots E0.. of the DFT8's output times w (INV: conj w), stores at Tw[WS e], reads from Tr[RS e].  Pure
+// placement of stores, loads and waits: the f64 operations, their operands and their rounding are those of dft8 and the
+// plain transposes above.
+//   * The DFT8's head (stage 1 and the even half's stage 2, 24 f64 instructions) is hipcc's to schedule.  Then, output by
+//     output in the order the operands become final -- 0, 4, 2, 6, then 1, 5, 3, 7 -- the output's two last-stage
+//     instructions, its twiddle multiply and its ds_write_b128, the order pinned; the odd half's middle (u5 / u7, z5 / z7,
+//     z4 / z6: 4 f64 each) sits between the even half's stores.  Consecutive stores are 10, 10, 10, 6, 6, 6, 6 f64
+//     instructions apart.  A ds_write_b128 occupies the LDS pipe for ~14 cycles per wave-instruction and the four waves
+//     of a workgroup reach their transposes together; round 7's form (the whole DFT8, then per slot the multiply and the
+//     store: 4 f64, ~20 cycles, apart) backed the train up at issue, and the reads behind it.  hipcc's own schedule is
+//     all eight multiplies, a full drain, then eight stores back to back.
+//   * No s_waitcnt between the stores and the reads of the same private area (DS operations of one wave execute in issue
 //     order; the ordering left is compiler-only), the eight reads pinned as ONE group in the order the next DFT8's first
 //     stage consumes them (0, 4, 1, 5, 2, 6, 3, 7) and consumed under hipcc's counted lgkmcnt waits.  (A compiler-only
 //     fence in lds_order lost because it left the reads free to scatter.)
-// Measured on MI355X, same box, three interleaved rounds, ms per 4096-PBS blind rotation (profiles/r07b_ab_steps.txt,
-// DESIGN 3j): the two pay only TOGETHER.  On top of the pipelined MAC (22.73): the first alone 22.80, both 22.61 (round-6
-// code 22.90); the second without the first is slower than round 6 (23.13 against 22.95 on another box).  Reading the
-// inverse's eight pass-B' twiddles as one early group was measured too and lost 0.05-0.12 ms:
-// tools/ab_patches/r07_twi_group.patch.
+// Measured on MI355X, interleaved rounds on one box per run, ms per 4096-PBS blind rotation.  Round 7
+// (profiles/r07b_ab_steps.txt): the pinned per-slot stores and the undrained pinned reads pay only TOGETHER,
+// 22.73 -> 22.61.  Round 11 (profiles/r11_ab_dft8_stores.txt): the stores fed from the last stage, 21.70 -> 21.17
+// (-2.4 %), 22.36 -> 22.13, 21.81 -> 21.46 and, the final tree, 21.94 -> 21.38 in four runs.  Measured on top and not kept
+// (tools/ab_patches/r11_store_steps.patch): consecutive stores from alternating register quadruples (+0.01), the
+// inverse's eight pass-B' twiddle reads pinned as one group in store order (+0.03; round 7's
+// tools/ab_patches/r07_twi_group.patch lost too), the accumulator update fed from the inverse's last DFT8 the same way
+// (+0.07).
 template <bool INV, int E0, int WS, int RS>
-__device__ __forceinline__ void xpose_p(double (&xr)[8], double (&xi)[8], const double2 (&w)[8], double2* Tw,
-                                        const double2* Tr) {
-#pragma unroll
-  for (int e = 0; e < 8; e++) {
-    if (e >= E0) cmul<INV>(xr[e], xi[e], w[e]);
-    Tw[WS * e] = make_double2(xr[e], xi[e]);
+__device__ __forceinline__ void dft8_xpose_p(double (&xr)[8], double (&xi)[8], const double2 (&w)[8], double2* Tw,
+                                             const double2* Tr) {
+  Dft8<INV> d;
+  d.stage1(xr, xi);
+  d.even2();
+  auto put = [&](auto ec) {
+    constexpr int e = decltype(ec)::value;
+    double re, im;
+    d.template out<e>(re, im);
+    if (e >= E0) cmul<INV>(re, im, w[e]);
+    Tw[WS * e] = make_double2(re, im);
     __builtin_amdgcn_sched_barrier(0);
-  }
+  };
+  put(std::integral_constant<int, 0>{});
+  d.odd_u();
+  put(std::integral_constant<int, 4>{});
+  d.odd_z57();
+  put(std::integral_constant<int, 2>{});
+  d.odd_z46();
+  put(std::integral_constant<int, 6>{});
+  put(std::integral_constant<int, 1>{});
+  put(std::integral_constant<int, 5>{});
+  put(std::integral_constant<int, 3>{});
+  put(std::integral_constant<int, 7>{});
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -258,26 +318,23 @@ __device__ __forceinline__ void xpose_p(double (&xr)[8], double (&xi)[8], const 
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// wb[0] is unused
+// the twist and passes A and B ride in the two fused transposes; wb[0] is unused
 __device__ __forceinline__ void dft512_fwd_rab_p(double (&xr)[8], double (&xi)[8], double2* T, int lane, TBase tb,
                                                  const double2 (&wa)[8], const double2 (&wb)[8]) {
-  twist_dft8_fwd(xr, xi);
-  xpose_p<false, 0, S1, 8>(xr, xi, wa, T + lane, T + tb.b1);
-  dft8<false>(xr, xi);
-  xpose_p<false, 1, S2, 1>(xr, xi, wb, T + lane, T + tb.b2);
+  twist_slots<false>(xr, xi);
+  dft8_xpose_p<false, 0, S1, 8>(xr, xi, wa, T + lane, T + tb.b1);
+  dft8_xpose_p<false, 1, S2, 1>(xr, xi, wb, T + lane, T + tb.b2);
   dft8<false>(xr, xi);
 }
 
 // pass C' from wb, pass B' from the LDS table twI
 __device__ __forceinline__ void dft512_inv_rb_p(double (&xr)[8], double (&xi)[8], double2* T, int lane, TBase tb,
                                                 const double2 (&wb)[8], const double2* twI) {
-  dft8<true>(xr, xi);
-  xpose_p<true, 1, 1, S2>(xr, xi, wb, T + tb.b2, T + lane);
-  dft8<true>(xr, xi);
-  double2 wi[8];  // pass B' twiddles: a constant LDS table, read where hipcc places them (between the multiplies)
+  dft8_xpose_p<true, 1, 1, S2>(xr, xi, wb, T + tb.b2, T + lane);
+  double2 wi[8];  // pass B' twiddles: a constant LDS table, read where hipcc places them (in the DFT8's head)
 #pragma unroll
   for (int e = 0; e < 8; e++) wi[e] = twI[64 * e + lane];
-  xpose_p<true, 0, 8, S1>(xr, xi, wi, T + tb.b1, T + lane);
+  dft8_xpose_p<true, 0, 8, S1>(xr, xi, wi, T + tb.b1, T + lane);
   dft8<true>(xr, xi);
 }
 

@@ -273,7 +273,7 @@ __device__ __forceinline__ void rotation_store(const u64 (&v)[16], int a, int la
 }
 // The reads of the image stored for the amount a (uniform: an SGPR), the differences and the states.  No drain between
 // the wave's own stores and these reads (DS operations of one wave execute in issue order): a compiler-level fence, and
-// the sixteen reads pinned as one group and consumed under counted waits, as xpose_p's are
+// the sixteen reads pinned as one group and consumed under counted waits, as dft8_xpose_p's are
 __device__ __forceinline__ void rotation_states(const u64 (&v)[16], int a, int lane, double2* T, u32 (&st)[16]) {
   u64* Tu = (u64*)T;
   const int A = (a >> 6) & 15;
