@@ -452,6 +452,76 @@ int tfhe_hip_sns_blind_rotate(tfhe_sns_ctx* ctx, const uint64_t* lwe_small, size
 int tfhe_hip_sns_phase(const tfhe_sns_params* sp, const uint64_t* glwe_key, const uint64_t* cts, size_t count,
                        uint64_t* out);
 
+/* ---- compression of squashed ciphertexts: packing keyswitch over the 2^128 torus ---------------
+ * The stored form of fhEVM's sns-worker output (the ct128 bucket, coprocessor-docker-compose.yml:124-140;
+ * tfhe-rs CompressedSquashedNoiseCiphertextList): up to lwe_per_glwe squashed LWEs (dimension in_dim, words of
+ * Z_2^128) are keyswitched into the coefficients 0, 1, ... of one 128-bit GLWE under a fresh binary key
+ * (NoiseSquashingCompressionKey), then the mask and one body per ciphertext are bit-packed.  This is the rule of
+ * tfhe_hip_pks_* widened to Z_2^128; kernels tfhe_amd/csrc/sns_pks.hip.
+ *
+ * Validity (EINVAL otherwise): in_dim % 16 == 0 (> 0); out_k > 0; out_N a power of two >= 32; (out_k+1)*out_N % 64
+ * == 0; 2 <= base_log <= 63; level >= 1; base_log*level <= 127; 1 <= lwe_per_glwe <= out_N; 2 <= storage_log <= 128;
+ * -64 < noise_log2 < 0.
+ * Layouts (those of tfhe_hip_sns_*): an LWE is (in_dim+1) pairs (lo, hi), as tfhe_hip_sns_squash writes them; a
+ * polynomial is two planes [lo][N], [hi][N]; a GLWE is (out_k+1) polynomials; the key is [j][l][c][lo, hi][N],
+ * in_dim*level*(out_k+1)*2*out_N words.
+ * Digits of a mask word a (u128), prec = base_log*level, B = 2^base_log:
+ *   state = ((a >> (128 - prec - 1)) + 1) >> 1, masked to prec bits;
+ *   for l = level-1 ... 0:  res = state & (B-1);  state >>= base_log;
+ *                           carry = ((((res - 1) | state) & res) >> (base_log - 1)) & 1;
+ *                           state += carry;  digit_l = res - carry*B
+ * Pack of the cnt <= lwe_per_glwe LWEs of one group (group g takes LWEs g*lwe_per_glwe ...):
+ *   T_d = sum_{j,l} digit_{d,j,l} * PKSK[j][l]  (coefficient-wise, mod 2^128)
+ *   out = sum_d X^d * ((0, ..., 0, b_d) - T_d)  (negacyclic, mod 2^128)
+ * Key: the output key is out_k*out_N bits of ChaCha stream 6; row j comes from stream 0x500000 + j.  PKSK[j][l]
+ * encrypts in_key[j] * 2^(128 - base_log*(l+1)) at coefficient 0: masks uniform (lo word, then hi word, per
+ * coefficient), then one Gaussian integer round(N(0,1) * 2^(64 + noise_log2)) per body coefficient,
+ * body = sum_c mask_c (*) S_c + e + m.
+ * Stored form: out_k*out_N mask values, then `bodies` body values; for storage_log s < 128 a value is
+ * ((x >> (128 - s - 1)) + 1) >> 1 mod 2^s, for s = 128 the word itself; values are packed LSB-first into
+ * ceil(values * s / 64) u64 words (a value may span three words).  Extraction puts each value back at the top of
+ * its word (<< (128 - s)) and zeroes the unused body coefficients. */
+typedef struct tfhe_sns_pks_params {
+  uint32_t in_dim, out_k, out_N, base_log, level, lwe_per_glwe, storage_log;
+  int32_t noise_log2;
+} tfhe_sns_pks_params;
+/* PARITY UNPINNED.  in_dim 4096 (the squashing key's k*N), 2^61 x 1 level, out k = 6, N = 1024, 128 LWEs per GLWE,
+ * storage 128 bits, noise 2^2: tfhe-rs NOISE_SQUASHING_COMP_PARAM_MESSAGE_2_CARRY_2_KS_PBS_TUNIFORM_2M128 restated
+ * from memory (no copy to compare with); tfhe-rs draws the key noise from TUniform(3), this engine from its Gaussian
+ * sampler at std 4, as for the squashing key. */
+#define TFHE_HIP_SNS_PKS_PRESET_FHEVM 0
+int tfhe_hip_sns_pks_params_preset(int preset, tfhe_sns_pks_params* out);
+size_t tfhe_hip_sns_pksk_len(const tfhe_sns_pks_params* pp); /* 0 for a null pp */
+int tfhe_hip_sns_pks_keygen(const tfhe_sns_pks_params* pp, uint64_t seed, const uint64_t* in_key, uint64_t* out_key,
+                            uint64_t* pksk /* nullable */);
+/* the same from a 192-bit rng key (OS entropy for production keys) */
+int tfhe_hip_sns_pks_keygen_k(const tfhe_sns_pks_params* pp, const tfhe_rng_key* rk, const uint64_t* in_key,
+                              uint64_t* out_key, uint64_t* pksk /* nullable */);
+typedef struct tfhe_sns_pks_ctx tfhe_sns_pks_ctx;
+/* The T workspace of a pack holds whole groups up to 512 MB; TFHE_HIP_SNS_PKS_CHUNK (read here, at create) sets
+ * the groups per chunk instead. */
+int tfhe_hip_sns_pks_create(const tfhe_sns_pks_params* pp, int device, tfhe_sns_pks_ctx** out);
+void tfhe_hip_sns_pks_destroy(tfhe_sns_pks_ctx* ctx);
+/* Waits for every call still in flight on the ctx before it rewrites the resident key. */
+int tfhe_hip_sns_pks_load_key(tfhe_sns_pks_ctx* ctx, const uint64_t* pksk, size_t len);
+/* count LWEs (count x (in_dim+1) x (lo, hi)) -> ceil(count / lwe_per_glwe) GLWEs ((out_k+1) x [lo][N], [hi][N]).
+ * ENOKEYS without a key; count == 0 returns OK; EINVAL for a null buffer or count > 0x7FFFFFFF; every check runs
+ * before any device work.  Host buffers, synchronous. */
+int tfhe_hip_sns_pks_pack(tfhe_sns_pks_ctx* ctx, const uint64_t* lwes, size_t count, uint64_t* glwes);
+/* Device buffers, enqueued on `stream` (NULL = the ctx stream, TFHE_HIP_NULL_STREAM = the null stream), as
+ * tfhe_hip_pks_pack_async.  The digit and T workspaces are shared by every call on the ctx: calls on different
+ * streams are ordered on them by an event, as tfhe_hip_sns_squash_async orders its own. */
+int tfhe_hip_sns_pks_pack_async(tfhe_sns_pks_ctx* ctx, const uint64_t* d_lwes, size_t count, uint64_t* d_glwes,
+                                void* stream);
+/* The same rule on the CPU (no device, no ctx): the reference of the device path. */
+int tfhe_hip_sns_pks_pack_host(const tfhe_sns_pks_params* pp, const uint64_t* pksk, const uint64_t* lwes, size_t count,
+                               uint64_t* glwes);
+size_t tfhe_hip_sns_pks_packed_words(const tfhe_sns_pks_params* pp, uint32_t bodies);
+int tfhe_hip_sns_pks_compress(const tfhe_sns_pks_params* pp, const uint64_t* glwe, uint32_t bodies, uint64_t* packed);
+int tfhe_hip_sns_pks_extract(const tfhe_sns_pks_params* pp, const uint64_t* packed, uint32_t bodies, uint64_t* glwe);
+/* client-side decryption of a 128-bit GLWE: body - sum_c mask_c * S_c -> [lo][N], [hi][N] */
+int tfhe_hip_glwe_phase128(uint32_t k, uint32_t N, const uint64_t* key, const uint64_t* glwe, uint64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,10 @@ ABI_SYMBOLS = (
     "tfhe_hip_bootstrap_async", "tfhe_hip_pks_unpack_extract", "tfhe_hip_pks_unpack_extract_async",
     "tfhe_hip_decompress", "tfhe_hip_decompress_async", "tfhe_hip_compact_list_words", "tfhe_hip_expand_compact",
     "tfhe_hip_expand_compact_async", "tfhe_hip_expand_cast", "tfhe_hip_expand_cast_async",
+    "tfhe_hip_sns_pks_params_preset", "tfhe_hip_sns_pksk_len", "tfhe_hip_sns_pks_keygen", "tfhe_hip_sns_pks_keygen_k",
+    "tfhe_hip_sns_pks_create", "tfhe_hip_sns_pks_destroy", "tfhe_hip_sns_pks_load_key", "tfhe_hip_sns_pks_pack",
+    "tfhe_hip_sns_pks_pack_async", "tfhe_hip_sns_pks_pack_host", "tfhe_hip_sns_pks_packed_words",
+    "tfhe_hip_sns_pks_compress", "tfhe_hip_sns_pks_extract", "tfhe_hip_glwe_phase128",
 )
 
 # P-FHEVM modulus-switch noise reduction key (include/tfhe_hip.h TFHE_HIP_MS_FHEVM_*)

@@ -468,5 +468,184 @@ void sns_phase(const tfhe_sns_params& sp, const uint64_t* glwe_key, const uint64
   }
 }
 
+// ------------------------------------------------------------ compression of squashed ciphertexts (Z_2^128)
+// The packing keyswitch of pks_keygen / pks.hip widened to 128-bit words; rule: include/tfhe_hip.h tfhe_sns_pks_params.
+size_t sns_pksk_len(const tfhe_sns_pks_params& pp) {
+  return (size_t)pp.in_dim * pp.level * (pp.out_k + 1) * 2 * pp.out_N;
+}
+
+// acc += (sign) mask (*) S over the set bits of S (negacyclic, mod 2^128)
+static void sns_mul_bits(const std::vector<uint32_t>& bits, const u128* mask, uint32_t N, bool negate, u128* acc) {
+  for (const uint32_t u : bits) {
+    if (negate) {
+      for (uint32_t x = 0; x < u; x++) acc[x] += mask[x + N - u];
+      for (uint32_t x = u; x < N; x++) acc[x] -= mask[x - u];
+    } else {
+      for (uint32_t x = 0; x < u; x++) acc[x] -= mask[x + N - u];
+      for (uint32_t x = u; x < N; x++) acc[x] += mask[x - u];
+    }
+  }
+}
+
+static std::vector<std::vector<uint32_t>> sns_key_bits(uint32_t k, uint32_t N, const uint64_t* key) {
+  std::vector<std::vector<uint32_t>> bits(k);
+  for (uint32_t c = 0; c < k; c++)
+    for (uint32_t u = 0; u < N; u++)
+      if (key[(size_t)c * N + u]) bits[c].push_back(u);
+  return bits;
+}
+
+// output GLWE key from ChaCha stream 6, PKSK row j from stream 0x500000 + j; draws as sns_keygen draws a BSK row
+void sns_pks_keygen(const tfhe_sns_pks_params& pp, const tfhe_rng_key& rk, const uint64_t* in_key, uint64_t* out_key,
+                    uint64_t* pksk) {
+  const uint32_t k = pp.out_k, N = pp.out_N, L = pp.level;
+  {
+    ChaCha r(rk, 6);
+    for (uint32_t i = 0; i < k * N; i++) out_key[i] = r.next() & 1;
+  }
+  if (!pksk) return;
+  const std::vector<std::vector<uint32_t>> bits = sns_key_bits(k, N, out_key);
+  const size_t row = (size_t)(k + 1) * 2 * N;
+  parallel_for((int64_t)pp.in_dim, [&](int64_t j) {
+    ChaCha r(rk, 0x500000 + (uint64_t)j);
+    std::vector<u128> body(N), mask(N);
+    for (uint32_t l = 0; l < L; l++) {
+      uint64_t* out = pksk + ((size_t)j * L + l) * row;
+      for (uint32_t c = 0; c < k; c++)
+        for (uint32_t t = 0; t < N; t++) {
+          const uint64_t lo = r.next(), hi = r.next();
+          sns_st(out + (size_t)c * 2 * N, N, t, ((u128)hi << 64) | lo);
+        }
+      for (uint32_t t = 0; t < N; t++) body[t] = (u128)(__int128)r.gauss(pp.noise_log2);
+      for (uint32_t c = 0; c < k; c++) {
+        for (uint32_t t = 0; t < N; t++) mask[t] = sns_ld(out + (size_t)c * 2 * N, N, t);
+        sns_mul_bits(bits[c], mask.data(), N, false, body.data());
+      }
+      if (in_key[j]) body[0] += (u128)1 << (128 - pp.base_log * (l + 1));
+      for (uint32_t t = 0; t < N; t++) sns_st(out + (size_t)k * 2 * N, N, t, body[t]);
+    }
+  });
+}
+
+// balanced digits of one mask word, d[0] most significant (pks_digits_kernel's recurrence on a u128 state)
+static void sns_pks_digits(u128 a, uint32_t base_log, uint32_t L, int64_t* d) {
+  const uint32_t prec = base_log * L;
+  u128 state = ((a >> (128 - prec - 1)) + 1) >> 1;
+  state &= ((u128)1 << prec) - 1;
+  const u128 low = ((u128)1 << base_log) - 1;
+  for (uint32_t l = L; l-- > 0;) {
+    const u128 res = state & low;
+    state >>= base_log;
+    const u128 carry = ((((res - 1) | state) & res) >> (base_log - 1)) & 1;
+    state += carry;
+    d[l] = (int64_t)((uint64_t)res - (uint64_t)(carry << base_log));
+  }
+}
+
+void sns_pks_pack_host(const tfhe_sns_pks_params& pp, const uint64_t* pksk, const uint64_t* lwes, size_t count,
+                       uint64_t* glwes) {
+  const size_t N = pp.out_N, k = pp.out_k, Nc = (k + 1) * N, L = pp.level, lpg = pp.lwe_per_glwe;
+  const size_t ct_words = 2 * ((size_t)pp.in_dim + 1);
+  std::vector<u128> T;
+  for (size_t first = 0, g = 0; first < count; first += lpg, g++) {
+    const size_t cnt = std::min(lpg, count - first);
+    T.assign(cnt * Nc, 0);
+    parallel_for((int64_t)cnt, [&](int64_t d) {
+      u128* Td = T.data() + (size_t)d * Nc;
+      const uint64_t* ct = lwes + (first + (size_t)d) * ct_words;
+      std::vector<int64_t> dig(L);
+      for (size_t j = 0; j < pp.in_dim; j++) {
+        sns_pks_digits(((u128)ct[2 * j + 1] << 64) | ct[2 * j], pp.base_log, pp.level, dig.data());
+        for (size_t l = 0; l < L; l++) {
+          if (!dig[l]) continue;
+          const u128 w = (u128)(__int128)dig[l];
+          const uint64_t* P = pksk + (j * L + l) * 2 * Nc;
+          for (size_t c = 0; c <= k; c++)
+            for (size_t t = 0; t < N; t++) Td[c * N + t] += w * sns_ld(P + c * 2 * N, N, t);
+        }
+      }
+    });
+    uint64_t* out = glwes + g * 2 * Nc;
+    parallel_for((int64_t)Nc, [&](int64_t col) {
+      const size_t c = (size_t)col / N, t = (size_t)col % N;
+      const u128* Tg = T.data() + c * N;
+      u128 acc = 0;
+      for (size_t d = 0; d < cnt; d++) {
+        if (d <= t) acc -= Tg[d * Nc + (t - d)];
+        else acc += Tg[d * Nc + (t + N - d)];
+      }
+      if (c == k && t < cnt) {
+        const uint64_t* b = lwes + (first + t) * ct_words + 2 * (size_t)pp.in_dim;
+        acc += ((u128)b[1] << 64) | b[0];
+      }
+      sns_st(out + c * 2 * N, N, t, acc);
+    });
+  }
+}
+
+void glwe_phase128(uint32_t k, uint32_t N, const uint64_t* key, const uint64_t* glwe, uint64_t* out) {
+  const std::vector<std::vector<uint32_t>> bits = sns_key_bits(k, N, key);
+  std::vector<u128> acc(N), mask(N);
+  for (uint32_t t = 0; t < N; t++) acc[t] = sns_ld(glwe + (size_t)k * 2 * N, N, t);
+  for (uint32_t c = 0; c < k; c++) {
+    for (uint32_t t = 0; t < N; t++) mask[t] = sns_ld(glwe + (size_t)c * 2 * N, N, t);
+    sns_mul_bits(bits[c], mask.data(), N, true, acc.data());
+  }
+  for (uint32_t t = 0; t < N; t++) sns_st(out, N, t, acc[t]);
+}
+
+size_t sns_pks_packed_words(const tfhe_sns_pks_params& pp, uint32_t bodies) {
+  return (((size_t)pp.out_k * pp.out_N + bodies) * pp.storage_log + 63) / 64;
+}
+
+// stored value v of a GLWE: the out_k * out_N mask coefficients, then the body's
+static inline size_t sns_pks_slot(const tfhe_sns_pks_params& pp, size_t v, size_t* t) {
+  const size_t N = pp.out_N, c = std::min(v / N, (size_t)pp.out_k);
+  *t = v - c * N;
+  return c * 2 * N;
+}
+
+// modulus switch to storage_log bits (none at 128), LSB-first bit packing; a value spans up to three words
+void sns_pks_compress(const tfhe_sns_pks_params& pp, const uint64_t* glwe, uint32_t bodies, uint64_t* packed) {
+  const uint32_t s = pp.storage_log;
+  const size_t vals = (size_t)pp.out_k * pp.out_N + bodies;
+  memset(packed, 0, sns_pks_packed_words(pp, bodies) * 8);
+  for (size_t v = 0; v < vals; v++) {
+    size_t t;
+    const size_t off = sns_pks_slot(pp, v, &t);
+    u128 x = sns_ld(glwe + off, pp.out_N, t);
+    if (s < 128) x = (((x >> (128 - s - 1)) + 1) >> 1) & (((u128)1 << s) - 1);
+    size_t bit = v * s;
+    for (uint32_t left = s; left;) {
+      const uint32_t o = (uint32_t)(bit & 63), take = std::min(64 - o, left);
+      const uint64_t part = (uint64_t)x & (take == 64 ? ~0ull : (1ull << take) - 1);
+      packed[bit >> 6] |= part << o;
+      x >>= take;
+      bit += take;
+      left -= take;
+    }
+  }
+}
+
+void sns_pks_extract(const tfhe_sns_pks_params& pp, const uint64_t* packed, uint32_t bodies, uint64_t* glwe) {
+  const uint32_t s = pp.storage_log;
+  const size_t vals = (size_t)pp.out_k * pp.out_N + bodies;
+  memset(glwe, 0, (size_t)(pp.out_k + 1) * 2 * pp.out_N * 8);
+  for (size_t v = 0; v < vals; v++) {
+    u128 x = 0;
+    size_t bit = v * s;
+    for (uint32_t got = 0; got < s;) {
+      const uint32_t o = (uint32_t)(bit & 63), take = std::min(64 - o, s - got);
+      const uint64_t part = (packed[bit >> 6] >> o) & (take == 64 ? ~0ull : (1ull << take) - 1);
+      x |= (u128)part << got;
+      bit += take;
+      got += take;
+    }
+    size_t t;
+    const size_t off = sns_pks_slot(pp, v, &t);
+    sns_st(glwe + off, pp.out_N, t, x << (128 - s));
+  }
+}
+
 }  // namespace client
 }  // namespace tfhe

@@ -35,6 +35,16 @@ size_t sns_bsk_len(const tfhe_sns_params& sp);
 void sns_keygen(const tfhe_sns_params& sp, const tfhe_rng_key& rk, const uint64_t* lwe_key, uint64_t* glwe_key, uint64_t* bsk);
 void sns_lut_identity(const tfhe_sns_params& sp, uint32_t msg_modulus, uint64_t* lut);
 void sns_phase(const tfhe_sns_params& sp, const uint64_t* glwe_key, const uint64_t* cts, size_t count, uint64_t* out);
+// compression of squashed ciphertexts: the packing keyswitch over Z_2^128 (include/tfhe_hip.h tfhe_hip_sns_pks_*)
+size_t sns_pksk_len(const tfhe_sns_pks_params& pp);
+void sns_pks_keygen(const tfhe_sns_pks_params& pp, const tfhe_rng_key& rk, const uint64_t* in_key, uint64_t* out_key,
+                    uint64_t* pksk);
+void sns_pks_pack_host(const tfhe_sns_pks_params& pp, const uint64_t* pksk, const uint64_t* lwes, size_t count,
+                       uint64_t* glwes);
+size_t sns_pks_packed_words(const tfhe_sns_pks_params& pp, uint32_t bodies);
+void sns_pks_compress(const tfhe_sns_pks_params& pp, const uint64_t* glwe, uint32_t bodies, uint64_t* packed);
+void sns_pks_extract(const tfhe_sns_pks_params& pp, const uint64_t* packed, uint32_t bodies, uint64_t* glwe);
+void glwe_phase128(uint32_t k, uint32_t N, const uint64_t* key, const uint64_t* glwe, uint64_t* out);
 }  // namespace client
 
 // compressed (seeded) server keys (seeded.cpp)

@@ -1,4 +1,4 @@
-// host_common.h — plumbing shared by the C ABI translation units (api.cpp, pks_api.cpp, sns_api.cpp):
+// host_common.h — plumbing shared by the C ABI translation units (api.cpp, pks_api.cpp, sns_api.cpp, sns_pks_api.cpp):
 // error reporting, HIP call checking, the device guard, stream resolution, buffer growth.  Host code only.
 #pragma once
 #include <hip/hip_runtime_api.h>

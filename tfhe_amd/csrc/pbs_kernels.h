@@ -89,6 +89,12 @@ hipError_t launch_sns_bsk_to_fft(const u64* bsk_std, void* bsk_fft, size_t polys
 hipError_t launch_sns_blind_rotate(const u64* lwe, size_t B, int n, const u64* lut, const void* bsk_fft, u64* acc,
                                    void* D, void* Oprod, const void* d_fconst, hipStream_t s);
 hipError_t launch_sns_extract(const u64* acc, size_t B, u64* out, hipStream_t s);
+// ---- sns_pks.hip: packing keyswitch over the 2^128 torus (squashed LWEs -> GLWE planes).  corr: Nc x 16 bytes,
+// built once per key; A: count x in_dim*L u64 of digits; T: count x Nc x 16 bytes.  hipErrorInvalidValue for a
+// count beyond the grids (more than 65535 row tiles)
+hipError_t launch_sns_pks_corr(const u64* pksk, int K, int Nc, int N, int base_log, u64* corr, hipStream_t s);
+hipError_t launch_sns_pks_pack(const u64* lwes, size_t count, int in_dim, int base_log, int L, int k, int N, int lpg,
+                               const u64* pksk, const u64* corr, u64* A, u64* T, u64* out, hipStream_t s);
 // ---- ms_reduce.hip: modulus-switch noise reduction, in place on B x (n+1); picks (device, nullable).
 // `zeros` holds the rows [count][n+1] followed by their element-major transpose [n+1][ms_zeros_pitch(count)]
 // (padding columns zero).

@@ -1,0 +1,257 @@
+// sns_pks_api.cpp — C ABI of the compression of squashed ciphertexts (include/tfhe_hip.h, tfhe_hip_sns_pks_*):
+// key residency, workspaces, chunked launches.  Kernels: sns_pks.hip; host key material and the CPU pack: client.cpp.
+#include <hip/hip_runtime_api.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <mutex>
+
+#include "../../include/tfhe_hip.h"
+#include "client.h"
+#include "host_common.h"
+#include "pbs_kernels.h"
+
+using tfhe::u64;
+
+namespace {
+
+bool spk_valid(const tfhe_sns_pks_params* pp) {
+  return pp && pp->in_dim > 0 && pp->in_dim % 16 == 0 && pp->out_k > 0 && pp->out_N >= 32 &&
+         (pp->out_N & (pp->out_N - 1)) == 0 && ((uint64_t)(pp->out_k + 1) * pp->out_N) % 64 == 0 &&
+         pp->base_log >= 2 && pp->base_log <= 63 && pp->level >= 1 && (uint64_t)pp->base_log * pp->level <= 127 &&
+         pp->lwe_per_glwe >= 1 && pp->lwe_per_glwe <= pp->out_N && pp->storage_log >= 2 && pp->storage_log <= 128 &&
+         pp->noise_log2 < 0 && pp->noise_log2 > -64;
+}
+
+constexpr size_t SPK_T_BUDGET = 512ull << 20;    // T workspace per chunk of groups
+constexpr size_t SPK_MAX_ROWS = 65535ull * 64;   // the GEMM grid's row tiles (sns_pks.hip)
+
+}  // namespace
+
+struct tfhe_sns_pks_ctx {
+  tfhe_sns_pks_params pp{};
+  int device = 0;
+  hipStream_t stream = nullptr;
+  size_t chunk_groups = 0;  // TFHE_HIP_SNS_PKS_CHUNK at create; 0: by the T budget
+  u64* d_pksk = nullptr;
+  u64* d_corr = nullptr;
+  bool key = false;
+  u64* d_A = nullptr;
+  u64* d_T = nullptr;
+  size_t rows_cap = 0;  // LWEs the A / T workspaces hold
+  // d_A, d_T and the key are shared by every call: each user waits for `ws_free` (the previous user's
+  // completion) on its own stream, as sns_api.cpp orders its workspaces
+  hipEvent_t ws_free = nullptr;
+  hipStream_t ws_last = nullptr;
+  bool ws_used = false;
+  u64* d_io = nullptr;
+  size_t io_cap = 0;  // bytes
+  std::mutex mu;
+};
+
+namespace {
+
+int ws_begin(tfhe_sns_pks_ctx* c, hipStream_t st) {
+  if (c->ws_used && c->ws_last != st) HIP_TRY(hipStreamWaitEvent(st, c->ws_free, 0));
+  return 0;
+}
+int ws_end(tfhe_sns_pks_ctx* c, hipStream_t st) {
+  HIP_TRY(hipEventRecord(c->ws_free, st));
+  c->ws_last = st;
+  c->ws_used = true;
+  return 0;
+}
+int ws_host_wait(tfhe_sns_pks_ctx* c) {
+  if (c->ws_used) HIP_TRY(hipEventSynchronize(c->ws_free));
+  return 0;
+}
+
+int ensure_rows(tfhe_sns_pks_ctx* c, size_t rows) {
+  if (c->rows_cap >= rows) return 0;
+  RC_TRY(ws_host_wait(c));  // no launch may still use the old buffers
+  (void)hipFree(c->d_A);
+  (void)hipFree(c->d_T);
+  c->d_A = c->d_T = nullptr;
+  c->rows_cap = 0;
+  const size_t K = (size_t)c->pp.in_dim * c->pp.level, Nc = (size_t)(c->pp.out_k + 1) * c->pp.out_N;
+  HIP_TRY(hipMalloc(&c->d_A, rows * K * sizeof(u64)));
+  HIP_TRY(hipMalloc(&c->d_T, rows * Nc * 16));
+  c->rows_cap = rows;
+  return 0;
+}
+
+// chunks of whole groups: the T workspace stays under its budget (or holds chunk_groups groups)
+int pack_device(tfhe_sns_pks_ctx* c, const u64* d_lwes, size_t count, u64* d_out, hipStream_t s) {
+  const tfhe_sns_pks_params& p = c->pp;
+  const size_t Nc = (size_t)(p.out_k + 1) * p.out_N, lpg = p.lwe_per_glwe, ct_words = 2 * ((size_t)p.in_dim + 1);
+  size_t groups = c->chunk_groups ? c->chunk_groups : std::max<size_t>(1, SPK_T_BUDGET / (lpg * Nc * 16));
+  groups = std::max<size_t>(1, std::min(groups, SPK_MAX_ROWS / lpg));
+  const size_t rows = std::min(count, groups * lpg);
+  RC_TRY(ensure_rows(c, rows));
+  RC_TRY(ws_begin(c, s));
+  for (size_t first = 0; first < count; first += rows) {
+    const size_t n = std::min(rows, count - first);
+    HIP_TRY(tfhe::launch_sns_pks_pack(d_lwes + first * ct_words, n, (int)p.in_dim, (int)p.base_log, (int)p.level,
+                                      (int)p.out_k, (int)p.out_N, (int)lpg, c->d_pksk, c->d_corr, c->d_A, c->d_T,
+                                      d_out + (first / lpg) * 2 * Nc, s));
+  }
+  return ws_end(c, s);
+}
+
+int pack_checks(tfhe_sns_pks_ctx* c, const void* in, size_t count, const void* out) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "sns_pks_pack: null ctx");
+  if (!c->key) return fail(TFHE_HIP_ENOKEYS, "sns_pks_pack: key not loaded");
+  if (count == 0) return 0;
+  if (!in || !out) return fail(TFHE_HIP_EINVAL, "sns_pks_pack: null buffer");
+  if (count > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "sns_pks_pack: too many ciphertexts");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tfhe_hip_sns_pks_params_preset(int preset, tfhe_sns_pks_params* o) {
+  if (!o) return fail(TFHE_HIP_EINVAL, "sns_pks_params_preset: null out");
+  if (preset != TFHE_HIP_SNS_PKS_PRESET_FHEVM) return fail(TFHE_HIP_EINVAL, "unknown squashed-packing preset %d", preset);
+  *o = tfhe_sns_pks_params{4096, 6, 1024, 61, 1, 128, 128, -62};
+  return 0;
+}
+
+size_t tfhe_hip_sns_pksk_len(const tfhe_sns_pks_params* pp) { return pp ? tfhe::client::sns_pksk_len(*pp) : 0; }
+
+int tfhe_hip_sns_pks_keygen_k(const tfhe_sns_pks_params* pp, const tfhe_rng_key* rk, const uint64_t* in_key,
+                              uint64_t* out_key, uint64_t* pksk) {
+  if (!spk_valid(pp) || !rk || !in_key || !out_key) return fail(TFHE_HIP_EINVAL, "sns_pks_keygen: bad arguments");
+  RC_TRY(check_binary(in_key, pp->in_dim, "sns_pks_keygen: in_key"));
+  tfhe::client::sns_pks_keygen(*pp, *rk, in_key, out_key, pksk);
+  return 0;
+}
+
+int tfhe_hip_sns_pks_keygen(const tfhe_sns_pks_params* pp, uint64_t seed, const uint64_t* in_key, uint64_t* out_key,
+                            uint64_t* pksk) {
+  const tfhe_rng_key rk = tfhe::client::rng_key_from_seed(seed);
+  return tfhe_hip_sns_pks_keygen_k(pp, &rk, in_key, out_key, pksk);
+}
+
+int tfhe_hip_sns_pks_create(const tfhe_sns_pks_params* pp, int device, tfhe_sns_pks_ctx** out) {
+  if (!out) return fail(TFHE_HIP_EINVAL, "sns_pks_create: null out");
+  *out = nullptr;
+  if (!spk_valid(pp)) return fail(TFHE_HIP_EINVAL, "sns_pks_create: invalid parameters");
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail(TFHE_HIP_EINVAL, "sns_pks_create: device %d of %d", device, ndev);
+  DeviceGuard g(device);
+  tfhe_sns_pks_ctx* c = new tfhe_sns_pks_ctx();
+  c->pp = *pp;
+  c->device = device;
+  {
+    const char* e = getenv("TFHE_HIP_SNS_PKS_CHUNK");
+    const long x = e ? atol(e) : 0;
+    c->chunk_groups = x > 0 ? (size_t)x : 0;
+  }
+  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ws_free, hipEventDisableTiming) != hipSuccess) {
+    tfhe_hip_sns_pks_destroy(c);
+    return fail(TFHE_HIP_EDEVICE, "sns_pks_create: device setup failed");
+  }
+  *out = c;
+  return 0;
+}
+
+void tfhe_hip_sns_pks_destroy(tfhe_sns_pks_ctx* c) {
+  if (!c) return;
+  {
+    DeviceGuard g(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->ws_used) (void)hipEventSynchronize(c->ws_free);  // a caller's stream may still run on the workspaces
+    for (u64* p : {c->d_pksk, c->d_corr, c->d_A, c->d_T, c->d_io}) (void)hipFree(p);
+    if (c->ws_free) (void)hipEventDestroy(c->ws_free);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+  }
+  delete c;
+}
+
+int tfhe_hip_sns_pks_load_key(tfhe_sns_pks_ctx* c, const uint64_t* pksk, size_t len) {
+  if (!c || !pksk) return fail(TFHE_HIP_EINVAL, "sns_pks_load_key: null argument");
+  if (len != tfhe::client::sns_pksk_len(c->pp))
+    return fail(TFHE_HIP_EINVAL, "sns_pks_load_key: length %zu, expected %zu", len, tfhe::client::sns_pksk_len(c->pp));
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  RC_TRY(ws_host_wait(c));  // a call in flight on a caller's stream still reads the resident key
+  c->key = false;
+  const size_t Nc = (size_t)(c->pp.out_k + 1) * c->pp.out_N;
+  if (!c->d_pksk) HIP_TRY(hipMalloc(&c->d_pksk, len * 8));
+  if (!c->d_corr) HIP_TRY(hipMalloc(&c->d_corr, Nc * 16));
+  HIP_TRY(hipMemcpyAsync(c->d_pksk, pksk, len * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(tfhe::launch_sns_pks_corr(c->d_pksk, (int)(c->pp.in_dim * c->pp.level), (int)Nc, (int)c->pp.out_N,
+                                    (int)c->pp.base_log, c->d_corr, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->key = true;
+  return 0;
+}
+
+int tfhe_hip_sns_pks_pack_async(tfhe_sns_pks_ctx* c, const uint64_t* d_lwes, size_t count, uint64_t* d_glwes,
+                                void* stream) {
+  RC_TRY(pack_checks(c, d_lwes, count, d_glwes));
+  if (count == 0) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  return pack_device(c, d_lwes, count, d_glwes, resolve_stream(stream, c->stream));
+}
+
+int tfhe_hip_sns_pks_pack(tfhe_sns_pks_ctx* c, const uint64_t* lwes, size_t count, uint64_t* glwes) {
+  RC_TRY(pack_checks(c, lwes, count, glwes));
+  if (count == 0) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const tfhe_sns_pks_params& p = c->pp;
+  const size_t in_bytes = count * 2 * ((size_t)p.in_dim + 1) * 8;
+  const size_t groups = (count + p.lwe_per_glwe - 1) / p.lwe_per_glwe;
+  const size_t out_bytes = groups * (p.out_k + 1) * 2 * p.out_N * 8, in_off = (out_bytes + 255) & ~(size_t)255;
+  RC_TRY(grow_device_buffer((void**)&c->d_io, &c->io_cap, in_off + in_bytes));
+  u64* d_out = c->d_io;
+  u64* d_in = (u64*)((char*)c->d_io + in_off);
+  HIP_TRY(hipMemcpyAsync(d_in, lwes, in_bytes, hipMemcpyHostToDevice, c->stream));
+  RC_TRY(pack_device(c, d_in, count, d_out, c->stream));
+  HIP_TRY(hipMemcpyAsync(glwes, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int tfhe_hip_sns_pks_pack_host(const tfhe_sns_pks_params* pp, const uint64_t* pksk, const uint64_t* lwes, size_t count,
+                               uint64_t* glwes) {
+  if (!spk_valid(pp)) return fail(TFHE_HIP_EINVAL, "sns_pks_pack_host: invalid parameters");
+  if (count == 0) return 0;
+  if (!pksk || !lwes || !glwes) return fail(TFHE_HIP_EINVAL, "sns_pks_pack_host: null buffer");
+  if (count > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "sns_pks_pack_host: too many ciphertexts");
+  tfhe::client::sns_pks_pack_host(*pp, pksk, lwes, count, glwes);
+  return 0;
+}
+
+size_t tfhe_hip_sns_pks_packed_words(const tfhe_sns_pks_params* pp, uint32_t bodies) {
+  return pp ? tfhe::client::sns_pks_packed_words(*pp, bodies) : 0;
+}
+
+int tfhe_hip_sns_pks_compress(const tfhe_sns_pks_params* pp, const uint64_t* glwe, uint32_t bodies, uint64_t* packed) {
+  if (!spk_valid(pp) || !glwe || !packed || bodies > pp->out_N)
+    return fail(TFHE_HIP_EINVAL, "sns_pks_compress: bad arguments");
+  tfhe::client::sns_pks_compress(*pp, glwe, bodies, packed);
+  return 0;
+}
+
+int tfhe_hip_sns_pks_extract(const tfhe_sns_pks_params* pp, const uint64_t* packed, uint32_t bodies, uint64_t* glwe) {
+  if (!spk_valid(pp) || !glwe || !packed || bodies > pp->out_N)
+    return fail(TFHE_HIP_EINVAL, "sns_pks_extract: bad arguments");
+  tfhe::client::sns_pks_extract(*pp, packed, bodies, glwe);
+  return 0;
+}
+
+int tfhe_hip_glwe_phase128(uint32_t k, uint32_t N, const uint64_t* key, const uint64_t* glwe, uint64_t* out) {
+  if (!k || !N || !key || !glwe || !out) return fail(TFHE_HIP_EINVAL, "glwe_phase128: bad arguments");
+  tfhe::client::glwe_phase128(k, N, key, glwe, out);
+  return 0;
+}
+
+}  // extern "C"
