@@ -202,8 +202,9 @@ static_assert(!wg_staggered(303, 304) && wg_staggered(304, 304) && wg_staggered(
 //   rotate + decompose acc_c (wave-local: the wave's own transpose area holds the rotation image)
 //   level steps q = 0, 1, 2 (least significant first): digits -> twist -> DFT -> MAC into BOTH outputs'
 //     partial sums  O_j^c = fma chain over q of D_(c,q) (.) BSK_i[(c, q)][j]      (j = 0, 1)
-//     one step's chunk = rows (0, q) and (1, q) of BSK_i (32 KB), streamed once per workgroup by LDS DMA into
-//     one buffer, loaded at the step's start
+//     q = 1, 2: one step's chunk = rows (0, q) and (1, q) of BSK_i (32 KB), streamed once per workgroup by LDS DMA
+//     into one buffer (q = 1's issued behind step 0's MAC, q = 2's at its step's start); q = 0: the wave's own two
+//     rows (c, 0) straight from L2 into registers, no LDS and no barrier (round 12, load_step0_keys)
 //   exchange: wave c publishes O_(1-c)^c in its transpose area and takes O_c^(1-c) from its partner's:
 //     O_c = O_c^c + O_c^(1-c)  (= O_c^0 + O_c^1: f64 addition commutes, the oracle's split order)
 //   ONE inverse transform: acc_c += rint(iFFT(O_c)) mod 2^64
@@ -213,7 +214,8 @@ static_assert(!wg_staggered(303, 304) && wg_staggered(304, 304) && wg_staggered(
 // The MAC order (per-component chains, then one add) is restated in oracle/fft_oracle.c.
 constexpr int STEP_C64 = 4 * M;                    // rows (0, q), (1, q), j = 0, 1
 // CTS = ciphertexts per workgroup, 2 since round 4: 4 waves, TWO independent workgroups per CU (76 KB of LDS each: the
-// inverse's TW_I table 8 KB | one 32 KB level step | 4 x 9 KB transpose areas; passes A / B come from registers), so the
+// inverse's TW_I table 8 KB | one 32 KB chunk, level steps 1 and 2 in turn | 4 x 9 KB transpose areas; passes A / B come
+// from registers, and so do level step 0's key words since round 12), so the
 // two workgroups drift apart and one's LDS phases overlap the other's VALU phases on every SIMD: 27.01 -> 26.63 ms per
 // 4096 on the same box against round 3's 8 waves with all tables in LDS and double-buffered level steps
 // (profiles/r04a_cts_ab.txt, two rounds).  Holding pass A's and pass B's twiddles in registers across the CMUX loop is
@@ -336,16 +338,16 @@ __device__ __forceinline__ void exchange_partials(const double (&o0r)[8], const 
   __syncthreads();  // the partner has read this wave's area before the inverse overwrites it
 }
 
-// Level step g = 3 i + q: 32 KB in 1 KB blocks; wave w of NW loads blocks (32 / NW) w .. (16 per component row) through
-// buffer_load_dwordx4 ... lds with the BSK as a buffer resource: the per-load byte offset is an SGPR (soffset) and the
-// lane offset one loop-invariant VGPR, so the 24 loads of a CMUX cost no VALU (round 5; global_load_lds needs a 64-bit
-// VALU address add per load).  The wave's blocks go in groups of four consecutive ones (NW = 4: one component row, 8 KB
-// in a row, in the BSK and in the chunk), pieces 1..3 of a group on the instruction's immediate offset, which advances
-// the buffer address AND the LDS address: two M0 values and two soffsets per wave and level step instead of eight of
-// each (round 9).  Measured and not shipped: the level-step buffer as a __shared__ object of its own and its
-// pieces issued from asm statements that hipcc's wait bookkeeping does not see
-// (tools/ab_patches/r09_k_own_dma_asm.patch); the pieces of level steps 0 and 2 issued one per iteration of the digit
-// loop (tools/ab_patches/r09_dma_spread.patch).
+// Level step g = 3 i + q, q = 1 or 2 (step 0 uses no chunk: load_step0_keys): 32 KB in 1 KB blocks; wave w of NW loads
+// blocks (32 / NW) w .. (16 per component row) through buffer_load_dwordx4 ... lds with the BSK as a buffer resource:
+// the per-load byte offset is an SGPR (soffset) and the lane offset one VGPR, so the 16 pieces of a CMUX cost no VALU
+// (round 5; global_load_lds needs a 64-bit VALU address add per load).  The wave's blocks go in groups of four
+// consecutive ones (NW = 4: one component row, 8 KB in a row, in the BSK and in the chunk), pieces 1..3 of a group on
+// the instruction's immediate offset, which advances the buffer address AND the LDS address: two M0 values and two
+// soffsets per wave and level step instead of eight of each (round 9).  Measured and not shipped: the
+// level-step buffer as a __shared__ object of its own and its pieces issued from asm statements that hipcc's wait
+// bookkeeping does not see (tools/ab_patches/r09_k_own_dma_asm.patch); the pieces of level steps 0 and 2 issued one
+// per iteration of the digit loop (tools/ab_patches/r09_dma_spread.patch, round 9: step 0 had a chunk then).
 template <int NW>
 __device__ __forceinline__ void load_step_buf4(__amdgpu_buffer_rsrc_t bsr, int g, double2* dst, int wave_s, int voff) {
   static_assert((32 / NW) % 4 == 0 && 16 % (32 / NW) == 0, "groups of four blocks inside one component row");
@@ -360,6 +362,27 @@ __device__ __forceinline__ void load_step_buf4(__amdgpu_buffer_rsrc_t bsr, int g
     __builtin_amdgcn_raw_ptr_buffer_load_lds(bsr, ld, 16, voff, soff, 1024, 0);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(bsr, ld, 16, voff, soff, 2048, 0);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(bsr, ld, 16, voff, soff, 3072, 0);
+  }
+}
+
+// Level step 0 takes its key words from L2 into registers, not through the chunk (round 12): wave (p, c)
+// needs only rows (c, 0, j = 0, 1) of BSK_i, 16 KB contiguous in the device layout, and the 64 VGPRs of the partial sums
+// are free until that step's MAC, which turns each key word into the partial sum that takes its registers.  Slots
+// E0 .. E1 - 1 as buffer_load_dwordx4 into registers: the row offset in SGPRs (one per 4 KB), the lane offset the loop's
+// voff, the slot on the immediate offset; no VALU.  The rows end at byte (6 i + 3 c + 1) 16 KB <= 6 n 16 KB, the
+// buffer's num_records.  Slot e's two words go out together, in the order the MAC consumes them under counted vmcnt
+// waits (vector loads return in order).  The two waves of a workgroup with the same c fetch the same 16 KB: key bytes
+// from L2 / L1 per workgroup and CMUX 96 -> 128 KB.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+template <int E0, int E1>
+__device__ __forceinline__ void load_step0_keys(__amdgpu_buffer_rsrc_t bsr, int i, int c_s, int voff, double2 (&ku)[8],
+                                                double2 (&kv)[8]) {
+  const int soff = ((i * 6 + c_s * 3) * (2 * M)) * (int)sizeof(double2);  // < 2^31: BSK < 2 GB
+#pragma unroll
+  for (int e = E0; e < E1; e++) {
+    const int so = soff + (e >> 2) * 4096, vo = voff + (e & 3) * 1024;
+    ku[e] = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(bsr, vo, so, 0));
+    kv[e] = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(bsr, vo, so + M * (int)sizeof(double2), 0));
   }
 }
 
@@ -390,7 +413,8 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
 #if FFT_WGTIME
   const unsigned long long wg_t0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  int lane = threadIdx.x & 63;
   const int c = wave & 1;
   const size_t b_raw = (size_t)blockIdx.x * CTS + (wave >> 1);
   const bool live = b_raw < B;
@@ -404,7 +428,7 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
   // the BSK as a raw buffer (num_records = its byte size; gfx9 dword 3 = 0x00020000, as composable_kernel uses on gfx9)
   const __amdgpu_buffer_rsrc_t bsr =
       __builtin_amdgcn_make_buffer_rsrc((void*)bsk, (short)0, n * 6 * 2 * M * (int)sizeof(double2), 0x00020000);
-  const int voff = lane * 16;
+  int voff = lane * 16;
   for (int q = threadIdx.x; q < M; q += 64 * NW) sh.twI[q] = tw_g[TW_I + q];
 
   // acc_c: A = 0, B = X^{-b~} * lut (LUT values in the Z_p encoding, mapped to the torus first)
@@ -458,10 +482,11 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
   unsigned long long dma_cyc[3] = {0, 0, 0};
   const unsigned long long loop_t0 = __builtin_amdgcn_s_memtime();
 #endif
-  // The mask word of CMUX i + 1 is loaded during CMUX i (after the rotation, ahead of level step 0's chunk) and becomes
-  // the scalar ms2048 value behind the vmcnt(0) of level step 0's glds_barrier, so no CMUX opens with a global load and a
-  // full wait (round 9).  Only the word's high half is loaded (ms2048 reads bits 52..63); the row is n + 1
-  // words long, so CMUX n - 1 prefetches the body word and ignores it.
+  // The mask word of CMUX i + 1 is loaded during CMUX i (after the rotation, ahead of level step 0's key loads) and
+  // becomes the scalar ms2048 value in front of level step 0's MAC, behind a counted wait that the key words' own waits
+  // follow, so no CMUX opens with a global load and a full wait (round 9; round 12, 3q).  Only the word's
+  // high half is loaded (ms2048 reads bits 52..63); the row is n + 1 words long, so CMUX n - 1 prefetches the body word
+  // and ignores it.
   // ms2048 from a word's high half; the high halves of the row
   auto ms2048_hi = [](u32 hi) { return (int)((((hi >> 20) + 1u) >> 1) & 2047u); };
   const u32* ct_hi = (const u32*)ct + 1;
@@ -472,8 +497,11 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
     // user, the last inverse, is this wave: DS operations of a wave run in order)
     u32 st[16];
     rotation_states(acc, a_s, lane, T, st);
-    // the next CMUX's mask word (i = n - 1: the body word, ignored), issued ahead of level step 0's chunk and
-    // consumed behind that step's glds_barrier
+    // opaque per CMUX: hipcc otherwise hoists voff + 1024, + 2048, + 3072 of the key loads into three loop-long VGPRs
+    // instead of the loads' immediate offsets
+    asm volatile("" : "+v"(voff));
+    // the next CMUX's mask word (i = n - 1: the body word, ignored), issued ahead of level step 0's key loads and
+    // consumed in front of that step's MAC
     u32 ct_next = ct_hi[2 * (size_t)(i + 1)];
     double o0r[8], o0i[8], o1r[8], o1i[8];
     // level steps q = 0, 1, 2 (least significant first), each specialised at compile time: q = 0 starts the two
@@ -482,13 +510,27 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
       constexpr int q = decltype(qc)::value;
       const int g = 3 * i + q;
       if (q > 0) base_prio();  // the previous step's MAC ran at the top priority (below)
-      // one buffer: every wave is done with step g - 1's chunk (the exchange's barriers order q = 0)
-      if (q > 0) __syncthreads();
+      // One key buffer, used by level steps 1 and 2.  Step 1's chunk is issued behind step 0's MAC with no barrier in
+      // front of it: the buffer's last readers were the q = 2 MACs of CMUX i - 1 in all four waves, each of which has
+      // its key words in registers (consumed by its fma) before it reaches the exchange's first barrier, and a wave
+      // issues these pieces only behind the exchange's second barrier (in CMUX 0 nothing has read the buffer yet).
+      // Its arrival is published by step 1's glds_barrier as before.  Step 2 overwrites what step 1's MACs read, so it
+      // keeps its barrier: every wave is done with step 1's chunk.
+      if (q == 1) __builtin_amdgcn_sched_barrier(0);  // no barrier opens this step: keep its work behind the priority drop
+      if (q == 2) __syncthreads();
+      // step 0's key words: slots 0..3 here, slots 4..7 behind the digits (sixteen loads back to back at either point,
+      // or two per digit pair, measured slower: DESIGN 3q, tools/ab_patches/r12_k0_issue_points.patch)
+      double2 ku0[8], kv0[8];
+      if constexpr (q == 0) {
+        __builtin_amdgcn_sched_barrier(0);
+        load_step0_keys<0, 4>(bsr, i, c_s, voff, ku0, kv0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
 #if FFT_DMASTAMP
       __builtin_amdgcn_sched_barrier(0);
       const unsigned long long dma_t0 = __builtin_amdgcn_s_memtime();
 #endif
-      load_step_buf4<NW>(bsr, g, sh.K[0], wave_s, voff);
+      if (q == 2) load_step_buf4<NW>(bsr, g, sh.K[0], wave_s, voff);
 #if FFT_DMASTAMP
       dma_cyc[q] += __builtin_amdgcn_s_memtime() - dma_t0;
       __builtin_amdgcn_sched_barrier(0);
@@ -504,61 +546,71 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
           xi[e] = (double)decomp_step(st[e + 8], 1u);
         }
       }
+      if constexpr (q == 0) {
+        __builtin_amdgcn_sched_barrier(0);
+        load_step0_keys<4, 8>(bsr, i, c_s, voff, ku0, kv0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       // the slot twist rides in pass A's twisted DFT8 (twist_dft8_fwd)
       dft512_fwd_rab_p(xr, xi, T, lane, tb, wa, wb);
-      glds_barrier();  // step g's chunk has landed
-      if constexpr (q == 0) {
-        // behind the barrier's vmcnt(0) the prefetched word is back: from here it is the scalar a of the next CMUX
-        asm volatile("" : "+v"(ct_next));
-        a_s = ms2048_hi(__builtin_amdgcn_readfirstlane(ct_next));
-      }
       // Each level step's MAC runs at the top wave priority (back to the base priority when the next step starts and
       // after the last), so the short MAC phase of one workgroup is not stalled behind the other workgroup's transforms
       // on the same SIMD: 26.62 -> 25.26 ms per 4096 on the same box, 152.2k -> 160.4k PBS/s (late round 4,
       // profiles/r04k_pgate_macprio_ab.txt)
+      if constexpr (q == 0) {
+        // no chunk and no barrier in this step.  The mask word went out ahead of the key loads, so the wait for it
+        // (hipcc's, counted) passes before the first key word's does: from here it is the scalar a of the next CMUX
+        asm volatile("" : "+v"(ct_next));
+        a_s = ms2048_hi(__builtin_amdgcn_readfirstlane(ct_next));
+        __builtin_amdgcn_s_setprio(3);
+        // the key word and the partial sum it starts share registers: slot e's two words die in its eight instructions
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+          mac_first(o0r[e], o0i[e], xr[e], xi[e], ku0[e]);
+          mac_first(o1r[e], o1i[e], xr[e], xi[e], kv0[e]);
+        }
+        // no barrier ends this step: keep the MAC in it, at its priority; then step 1's chunk (above), behind the MAC's
+        // waits, which hipcc would otherwise turn into vmcnt(0)
+        __builtin_amdgcn_sched_barrier(0);
+#if FFT_DMASTAMP
+        const unsigned long long dma_t1 = __builtin_amdgcn_s_memtime();
+#endif
+        load_step_buf4<NW>(bsr, g + 1, sh.K[0], wave_s, voff);
+#if FFT_DMASTAMP
+        dma_cyc[1] += __builtin_amdgcn_s_memtime() - dma_t1;
+#endif
+        __builtin_amdgcn_sched_barrier(0);
+        return;
+      }
+      glds_barrier();  // step g's chunk has landed
       __builtin_amdgcn_s_setprio(3);
       const double2* k0 = sh.K[0] + c * (2 * M) + lane;
       const double2* k1 = k0 + M;
-      if constexpr (q > 0) {
-        // The key words of level steps q = 1 and q = 2 software-pipelined (round 7): a rotating window of D slots' key
-        // words ahead of the slot being consumed, the order pinned: the reads of slot e + D go out before slot e's eight
-        // fma, which wait (counted) for slot e's pair only.  hipcc's own schedule reads one slot's two words into the
-        // same registers eight times per level and waits for each pair (eight exposed LDS round trips per level, at the
-        // MAC's raised priority and right before a workgroup barrier); q = 0 already has all sixteen reads in flight
-        // (its partial sums are not live yet).  One slot ahead at q = 1 and two at q = 2 (the 16 decomposition states
-        // are dead there) is what 256 VGPRs hold: 255 used, none spilled; 2 / 3 spills one register, 2 / 2 five.
-        // Measured alone 22.90 -> 22.73 ms per 4096-PBS blind rotation, and 0.29 ms of the round-7 default's gain when
-        // taken out of it (same box, three interleaved rounds each, profiles/r07b_ab_steps.txt).
-        constexpr int D = q == 2 ? 2 : 1;
-        double2 ku[8], kv[8];
+      // The key words of level steps q = 1 and q = 2 software-pipelined (round 7): a rotating window of D slots' key
+      // words ahead of the slot being consumed, the order pinned: the reads of slot e + D go out before slot e's eight
+      // fma, which wait (counted) for slot e's pair only.  hipcc's own schedule reads one slot's two words into the
+      // same registers eight times per level and waits for each pair (eight exposed LDS round trips per level, at the
+      // MAC's raised priority and right before a workgroup barrier).  One slot ahead at q = 1 and two at q = 2 (the 16
+      // decomposition states are dead there) is what 256 VGPRs hold.  Measured alone 22.90 -> 22.73 ms per 4096-PBS
+      // blind rotation, and 0.29 ms of the round-7 default's gain when taken out of it (same box, three interleaved
+      // rounds each, profiles/r07b_ab_steps.txt).
+      constexpr int D = q == 2 ? 2 : 1;
+      double2 ku[8], kv[8];
 #pragma unroll
-        for (int e = 0; e < D; e++) {
-          ku[e] = k0[64 * e];
-          kv[e] = k1[64 * e];
-        }
-#pragma unroll
-        for (int e = 0; e < 8; e++) {
-          if (e + D < 8) {
-            ku[e + D] = k0[64 * (e + D)];
-            kv[e + D] = k1[64 * (e + D)];
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          mac_next(o0r[e], o0i[e], xr[e], xi[e], ku[e]);
-          mac_next(o1r[e], o1i[e], xr[e], xi[e], kv[e]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        return;
+      for (int e = 0; e < D; e++) {
+        ku[e] = k0[64 * e];
+        kv[e] = k1[64 * e];
       }
 #pragma unroll
       for (int e = 0; e < 8; e++) {
-        const double2 u = k0[64 * e], v = k1[64 * e];
-        if constexpr (q == 0) {
-          mac_first(o0r[e], o0i[e], xr[e], xi[e], u);
-          mac_first(o1r[e], o1i[e], xr[e], xi[e], v);
-        } else {
-          mac_next(o0r[e], o0i[e], xr[e], xi[e], u);
-          mac_next(o1r[e], o1i[e], xr[e], xi[e], v);
+        if (e + D < 8) {
+          ku[e + D] = k0[64 * (e + D)];
+          kv[e + D] = k1[64 * (e + D)];
         }
+        __builtin_amdgcn_sched_barrier(0);
+        mac_next(o0r[e], o0i[e], xr[e], xi[e], ku[e]);
+        mac_next(o1r[e], o1i[e], xr[e], xi[e], kv[e]);
+        __builtin_amdgcn_sched_barrier(0);
       }
     };
     level(std::integral_constant<int, 0>{});
@@ -613,15 +665,25 @@ __global__ __launch_bounds__(128 * CTS, 4 / CTS) void blind_rotate_fft_pair_kern
 #endif
 
   if (!live) return;
+  // the output's row and component from wave-uniform values and the lane counted anew (mbcnt over an opaque zero, so
+  // that it is not the prologue's value): hipcc otherwise keeps the prologue's per-lane b, c, L and 64 e + L alive
+  // through the loop, which has no register left for them
+  const size_t bo = (size_t)blockIdx.x * CTS + (size_t)(wave_s >> 1);  // = b: the wave is live
+  const int co = c_s;
+  {
+    u32 z;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+    lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
+  }
   if (WRITE_ACC) {
-    u64* oa = out_acc + b * 2048 + c * N1K;
+    u64* oa = out_acc + bo * 2048 + co * N1K;
 #pragma unroll
     for (int e = 0; e < 16; e++) oa[64 * e + lane] = acc[e];
   }
   if (WRITE_BIG) {
     // sample extraction at degree 0 (computations.rs:109-132): a'_0 = A[0], a'_j = -A[N-j], b' = B[0]
-    u64* ob = out_big + b * (size_t)(N1K + 1);
-    if (c == 0) {
+    u64* ob = out_big + bo * (size_t)(N1K + 1);
+    if (co == 0) {
 #pragma unroll
       for (int e = 0; e < 16; e++) {
         const int idx = 64 * e + lane;

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Static ISA stats of the CMUX loop of the P-GATE pair kernel (blind_rotate_fft_pair_kernel<2, false, true>, the
-# instantiation bench.py runs): resources of the kernel, then the f64, non-f64 VALU, scalar, LDS, wait, M0-write and LDS-DMA counts of the loop body (both
+# instantiation bench.py runs): resources of the kernel, then the f64, non-f64 VALU, scalar, LDS, wait, M0-write, LDS-DMA and register key-load counts of the loop body (both
 # branches of the partial-sum exchange counted).  Compiles with the Makefile's flags for pbs_fft.o; needs no GPU.
 # usage: tools/isa_pair_stats.sh [-k out.s] [extra hipcc flags, e.g. -DFFT_DMASTAMP=1 ...]
 #   -k out.s: keep the loop body (its line numbers are those of the kernel's listing) for reading
@@ -33,5 +33,5 @@ echo "  v_add_f64 $(cnt v_add_f64)  v_mul_f64 $(cnt v_mul_f64)  v_fma_f64+v_fmac
 echo "  non-f64 VALU $(grep -E '^\s+v_' "$D/loop.s" | grep -cvE '^\s+v_(add|mul|fma|fmac|floor)_f64(_e32|_e64)?(\s|$)' || true)  (every v_* but the four above)  scalar $(grep -cE '^\s+s_' "$D/loop.s" || true)  (every s_*, waits and s_nop included)"
 echo "  ds_read_b128 $(cnt ds_read_b128)  ds_write_b128 $(cnt ds_write_b128)  ds_read_b64 $(cnt ds_read_b64)  ds_write_b64 $(cnt ds_write_b64)"
 echo "  s_waitcnt $(cnt s_waitcnt)  of which lgkmcnt(0) $(grep -cE '^\s+s_waitcnt.*lgkmcnt\(0\)' "$D/loop.s" || true)  s_barrier $(cnt s_barrier)"
-echo "  s_waitcnt vmcnt $(grep -cE '^\s+s_waitcnt.*vmcnt' "$D/loop.s" || true)  s_mov_b32 m0 $(grep -cE '^\s+s_mov_b32 m0,' "$D/loop.s" || true)  LDS-DMA (buffer_load / global_load ... lds) $(grep -cE '^\s+(buffer_load|global_load_lds)_.*\slds(\s|$)|^\s+global_load_lds_' "$D/loop.s" || true)  global_load $(grep -cE '^\s+global_load_dword' "$D/loop.s" || true)"
+echo "  s_waitcnt vmcnt $(grep -cE '^\s+s_waitcnt.*vmcnt' "$D/loop.s" || true)  s_mov_b32 m0 $(grep -cE '^\s+s_mov_b32 m0,' "$D/loop.s" || true)  LDS-DMA (buffer_load / global_load ... lds) $(grep -cE '^\s+(buffer_load|global_load_lds)_.*\slds(\s|$)|^\s+global_load_lds_' "$D/loop.s" || true)  buffer_load_dwordx4 into registers $(grep -E '^\s+buffer_load_dwordx4\s' "$D/loop.s" | grep -cvE '\slds(\s|$)' || true)  global_load $(grep -cE '^\s+global_load_dword' "$D/loop.s" || true)"
 if [ -n "$KEEP" ]; then cp "$D/loop.s" "$KEEP"; echo "loop body kept in $KEEP"; fi
