@@ -404,6 +404,56 @@ int tfhe_hip_expand_cast_async(tfhe_ctx* ctx, const uint64_t* d_list, size_t lis
                                size_t rows, const uint64_t* d_luts, size_t n_lut, const uint32_t* d_lut_index,
                                uint64_t* d_lwe_out, void* stream);
 
+/* ---- oblivious pseudo-random ciphertexts from a seed (fhEVM rand / randBounded) ------------------
+ * tfhe-rs ServerKey::generate_oblivious_pseudo_random* (the fheRand / fheRandBounded operators,
+ * tests/fhevm-suite/e2e/test/operatorsPrices.json:439-468): a 128-bit seed expands through the AES-CTR CSPRNG into
+ * the mask of an LWE ciphertext under the small key with body 0, whose phase nobody without the secret key knows;
+ * a blind rotation with a staircase LUT and one plaintext addition turn that phase into an encryption of
+ * random_bits uniform bits.  The masks are generated on the device (tfhe_amd/csrc/csprng.hip): a request uploads
+ * 16 bytes per row.  PARITY UNPINNED at the byte level, as every seeded path here (the reference mount holds no
+ * OPRF vector): the conventions are restated from tfhe-rs and are, all arithmetic mod 2^64,
+ *   row mask     row seed s = (lo, hi): mask = words 0 .. n-1 of the seed's stream (tfhe_hip_csprng_words(s, 0, n)),
+ *                body 0, i.e. tfhe_hip_decompress_lwe_list(n, 1, s, {0})
+ *   block seeds  block j of a request with parent seed S uses (lo, hi) = words (2j, 2j + 1) of S's stream (tfhe-rs
+ *                DeterministicSeeder: 16 consecutive stream bytes per seed, little endian)
+ *   LUT          p = 2^random_bits, delta = 2^(64 - full_bits), 1 <= random_bits < full_bits <= 63, p <= 2N:
+ *                lut[x] = (2 floor(x / (2N / p)) + 1) delta / 2 for x < N, post_add = (p - 1) delta / 2, no half-box
+ *                rotation (tfhe_hip_lut_oprf)
+ *   result       with x = (-sum a~_i s_i) mod 2N, a~ the standard modulus switch of the mask (no noise reduction),
+ *                row r encrypts v delta: v = floor(x / (2N / p)) + p / 2 if x < N, else
+ *                v = p / 2 - 1 - floor((x - N) / (2N / p))
+ *   gate bits    LUT = tfhe_hip_lut_constant(N, 2^61), post_add = 0: the bit is true iff x < N
+ * Pipeline: order 1 (KS -> PBS, P-FHEVM): masks -> blind rotation -> sample extraction -> post-add, no keyswitch and
+ * no modulus-switch noise reduction: rows of kN + 1 words, the BSK alone suffices (a rotation-only ctx works).
+ * Order 0 (PBS -> KS, P-GATE): masks -> the full PBS (rotation, extraction, keyswitch) -> post-add: rows of n + 1
+ * words, both keys.  Either way a row is io_dim + 1 words.  Timing: the mask kernel in slot 3, then the slots of
+ * the PBS. */
+/* host: the LUT (N words) and post-add of the convention above; EINVAL for N not a power of two, random_bits == 0,
+ * random_bits >= full_bits, full_bits > 63 or 2^random_bits > 2N */
+int tfhe_hip_lut_oprf(uint32_t N, uint32_t random_bits, uint32_t full_bits, uint64_t* lut, uint64_t* post_add);
+/* Stage-level: the mask kernel alone, host buffers, shard 0, needs no keys.  out: rows x dim, row r = words
+ * first_word .. first_word + dim - 1 of the stream of seed (seeds[2r], seeds[2r + 1]).  EINVAL for a null buffer,
+ * dim == 0, rows > 0x7FFFFFFF, rows * ceil(dim / 1022) > 0x7FFFFFFF or first_word + dim > 2^60; rows == 0
+ * returns OK */
+int tfhe_hip_csprng_rows(tfhe_ctx* ctx, const uint64_t* seeds, size_t rows, uint64_t first_word, uint32_t dim,
+                         uint64_t* out);
+/* _async: device pointers, on the shard whose device holds d_seeds, enqueued on `stream` (no workspace is used).
+ * Row r starts at d_out + r * row_stride (row_stride >= dim, EINVAL otherwise); words dim .. row_stride - 1 of a row
+ * are not written. */
+int tfhe_hip_csprng_rows_async(tfhe_ctx* ctx, const uint64_t* d_seeds, size_t rows, uint64_t first_word, uint32_t dim,
+                               size_t row_stride, uint64_t* d_out, void* stream);
+/* seeds: rows x 2; luts: n_lut x N with post_adds[n_lut] added to the body of every row that uses the LUT;
+ * lut_index (rows entries, or null = LUT 0) as tfhe_hip_pbs; lwe_out: rows x (io_dim + 1).  Every check precedes
+ * device work: EINVAL for a null buffer, n_lut == 0, a host lut_index entry >= n_lut or rows > 0x7FFFFFFF; ENOKEYS
+ * without a BSK, and in order 0 without the KSK; rows == 0 returns OK.  The host form slices the rows over the
+ * shards (outputs in seed order); _async: device pointers, on the shard whose device holds d_seeds, enqueued on
+ * `stream` (stream and workspace rules of tfhe_hip_pbs_async; a device lut_index is trusted as there). */
+int tfhe_hip_oprf(tfhe_ctx* ctx, const uint64_t* seeds, size_t rows, const uint64_t* luts, const uint64_t* post_adds,
+                  size_t n_lut, const uint32_t* lut_index, uint64_t* lwe_out);
+int tfhe_hip_oprf_async(tfhe_ctx* ctx, const uint64_t* d_seeds, size_t rows, const uint64_t* d_luts,
+                        const uint64_t* d_post_adds, size_t n_lut, const uint32_t* d_lut_index, uint64_t* d_lwe_out,
+                        void* stream);
+
 /* ---- switch-and-squash: noise squashing to a 128-bit LWE ----------------------
  * fhEVM's sns-worker (coprocessor-docker-compose.yml:124-140) turns each 64-bit P-FHEVM ciphertext into
  * a Z_2^128 LWE with tiny noise for threshold decryption: keyswitch to the small key, modulus-switch

@@ -122,6 +122,7 @@ ABI_SYMBOLS = (
     "tfhe_hip_sns_pks_create", "tfhe_hip_sns_pks_destroy", "tfhe_hip_sns_pks_load_key", "tfhe_hip_sns_pks_pack",
     "tfhe_hip_sns_pks_pack_async", "tfhe_hip_sns_pks_pack_host", "tfhe_hip_sns_pks_packed_words",
     "tfhe_hip_sns_pks_compress", "tfhe_hip_sns_pks_extract", "tfhe_hip_glwe_phase128",
+    "tfhe_hip_lut_oprf", "tfhe_hip_csprng_rows", "tfhe_hip_csprng_rows_async", "tfhe_hip_oprf", "tfhe_hip_oprf_async",
 )
 
 # P-FHEVM modulus-switch noise reduction key (include/tfhe_hip.h TFHE_HIP_MS_FHEVM_*)
@@ -235,6 +236,16 @@ def lib():
         L.tfhe_hip_expand_cast_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
                                                  ctypes.c_uint32, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.tfhe_hip_lut_oprf.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _U64P, _U64P]
+        L.tfhe_hip_csprng_rows.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32,
+                                           _U64P]
+        L.tfhe_hip_csprng_rows_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64,
+                                                 ctypes.c_uint32, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+        L.tfhe_hip_oprf.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, _U64P, _U64P, ctypes.c_size_t, _U32P,
+                                    _U64P]
+        L.tfhe_hip_oprf_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p]
         _LIB = L
     return _LIB
 
@@ -440,6 +451,28 @@ def lut_many(N: int, msg_modulus: int, tables: Sequence[Sequence[int]], delta_ou
             raise ValueError(f"lut_many: table {f} has {len(t)} entries, expected msg_modulus / n_fn = {per}")
     flat = [v for t in tables for v in t]
     return lut_from_table(N, msg_modulus, flat, delta_out), N // n_fn
+
+
+def lut_oprf(N: int, random_bits: int, full_bits: int):
+    """The staircase LUT and post-add of tfhe-rs ``generate_oblivious_pseudo_random*`` (include/tfhe_hip.h, PARITY
+    UNPINNED): with p = 2^random_bits and delta = 2^(64 - full_bits), ``lut[x] = (2 (x // (2N/p)) + 1) delta/2`` and
+    ``post_add = (p - 1) delta/2`` -> (lut, post_add)."""
+    for v in (N, random_bits, full_bits):
+        if not 0 <= int(v) < 1 << 32:
+            raise ValueError("lut_oprf: arguments must fit 32 bits")
+    lut = np.zeros(max(int(N), 1), dtype=np.uint64)
+    post = ctypes.c_uint64()
+    _check(lib().tfhe_hip_lut_oprf(int(N), int(random_bits), int(full_bits), _u64(lut), ctypes.byref(post)))
+    return lut, int(post.value)
+
+
+def oprf_block_seeds(seed, count: int) -> np.ndarray:
+    """The row seeds of one rand request: block j uses (lo, hi) = words (2j, 2j + 1) of the stream of the parent
+    ``seed`` = (lo, hi) (tfhe-rs DeterministicSeeder, PARITY UNPINNED) -> (count, 2) uint64."""
+    s = _c_u64([int(seed[0]) % (1 << 64), int(seed[1]) % (1 << 64)])
+    out = np.zeros((int(count), 2), dtype=np.uint64)
+    _check(lib().tfhe_hip_csprng_words(_u64(s), 0, out.size, _u64(out)))
+    return out
 
 
 # ------------------------------------------------------------------------------------- engine
@@ -718,6 +751,66 @@ class Engine:
         rows = self._rows(count, rep, rows)
         d_out = d_words.new_empty((max(rows, 0), self.params.io_dim + 1))
         self.expand_cast_async(d_words.contiguous(), count, d_luts, d_out, rep, rows, d_lut_index)
+        return d_out
+
+    # -- oblivious pseudo-random ciphertexts (fhEVM rand / randBounded; radix.py and integer.py build on these) ----
+    def csprng_rows(self, seeds: np.ndarray, dim: int, first_word: int = 0) -> np.ndarray:
+        """Stage-level: the device's seeded mask stream over host arrays, (rows, 2) seeds -> (rows, dim), row r =
+        words ``first_word .. first_word + dim - 1`` of seed r's stream (``tfhe_hip_csprng_words``).  Needs no key."""
+        s = _c_u64(seeds).reshape(-1, 2)
+        if not (0 <= int(dim) < 1 << 32 and 0 <= int(first_word) < 1 << 64):
+            raise ValueError("csprng_rows: dim must fit 32 bits and first_word 64")
+        out = np.zeros((s.shape[0], int(dim)), dtype=np.uint64)
+        _check(lib().tfhe_hip_csprng_rows(self._h, _u64(s), s.shape[0], int(first_word), int(dim), _u64(out)))
+        return out
+
+    def csprng_rows_async(self, d_seeds, dim: int, d_out, first_word: int = 0, stream=None) -> None:
+        """Device-resident ``csprng_rows`` (torch tensors on this device: d_seeds (rows, 2), d_out (rows, stride) with
+        stride >= dim; words past ``dim`` of a row are left alone), enqueued on ``stream`` like ``pbs_async``."""
+        _check(lib().tfhe_hip_csprng_rows_async(
+            self._h, ctypes.c_void_p(d_seeds.data_ptr()), d_seeds.shape[0], int(first_word), int(dim),
+            d_out.shape[1], ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(_stream_handle(stream, self.device))))
+
+    def _oprf_tables(self, luts, post_adds):
+        luts = _c_u64(luts).reshape(-1, self.params.N)
+        post = _c_u64([int(v) % (1 << 64) for v in np.atleast_1d(post_adds)])
+        if post.shape[0] != luts.shape[0]:
+            raise ValueError("oprf: one post_add per LUT")
+        return luts, post
+
+    def oprf(self, seeds: np.ndarray, luts: np.ndarray, post_adds, lut_index=None) -> np.ndarray:
+        """tfhe-rs ``generate_oblivious_pseudo_random*``, batched over host arrays: (rows, 2) row seeds -> (rows,
+        io_dim + 1) encryptions of pseudo-random values that nobody without the secret key knows.  Row r's mask comes
+        from its seed on the device, is rotated through ``luts[lut_index[r]]`` (``lut_oprf``, or the gate LUT with
+        post-add 0) and gets ``post_adds[lut_index[r]]`` added.  KS -> PBS parameter sets need the bootstrapping key
+        only."""
+        s = _c_u64(seeds).reshape(-1, 2)
+        luts, post = self._oprf_tables(luts, post_adds)
+        li = None
+        if lut_index is not None:
+            li = np.ascontiguousarray(np.asarray(lut_index, dtype=np.uint32))
+            if li.shape[0] != s.shape[0]:
+                raise ValueError("lut_index must have one entry per seed")
+        out = np.zeros((s.shape[0], self.params.io_dim + 1), dtype=np.uint64)
+        _check(lib().tfhe_hip_oprf(self._h, _u64(s), s.shape[0], _u64(luts), _u64(post), luts.shape[0],
+                                   li.ctypes.data_as(_U32P) if li is not None else None, _u64(out)))
+        return out
+
+    def oprf_async(self, d_seeds, d_luts, d_post_adds, d_out, d_lut_index=None, stream=None) -> None:
+        """Device-resident ``oprf`` (torch tensors on this device: d_seeds (rows, 2), d_post_adds one word per LUT,
+        d_out (rows, io_dim + 1)), enqueued on ``stream`` like ``pbs_async``."""
+        _check(lib().tfhe_hip_oprf_async(
+            self._h, ctypes.c_void_p(d_seeds.data_ptr()), d_seeds.shape[0], ctypes.c_void_p(d_luts.data_ptr()),
+            ctypes.c_void_p(d_post_adds.data_ptr()), d_luts.numel() // self.params.N,
+            ctypes.c_void_p(d_lut_index.data_ptr()) if d_lut_index is not None else None,
+            ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(_stream_handle(stream, self.device))))
+
+    def oprf_device(self, d_seeds, d_luts, d_post_adds, d_lut_index=None):
+        """oprf_async into a fresh tensor: (rows, 2) seeds on this device -> (rows, io_dim + 1), queued on torch's
+        current stream (no host synchronisation)."""
+        d_out = d_seeds.new_empty((d_seeds.shape[0], self.params.io_dim + 1))
+        if d_seeds.shape[0]:
+            self.oprf_async(d_seeds.contiguous(), d_luts, d_post_adds, d_out, d_lut_index)
         return d_out
 
     def sample_extract_many(self, acc: np.ndarray, n_fn: int, stride: int) -> np.ndarray:

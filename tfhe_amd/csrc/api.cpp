@@ -116,6 +116,8 @@ struct tfhe_shard {
   size_t acc_cap = 0;    // bytes
   u64* d_expand = nullptr;  // expanded compact list, the PBS input of tfhe_hip_expand_cast (d_big is the PBS's own)
   size_t expand_cap = 0;    // bytes
+  u64* d_oprf = nullptr;  // seeded masks with body 0, the PBS input of tfhe_hip_oprf (rows x (n + 1))
+  size_t oprf_cap = 0;    // bytes
   void* d_stage = nullptr;
   size_t stage_cap = 0;  // bytes
   void* d_ks_dig = nullptr;
@@ -124,7 +126,8 @@ struct tfhe_shard {
   hipStream_t ws_last = nullptr;
   bool ws_used = false;
   // timing: start/stop event pairs per slot (0 = blind rotate, 1 = keyswitch, 2 = MS noise reduction,
-  // 3 = the ingest stage of a call: unpack / extract of a decompression, or the expansion of a compact list)
+  // 3 = the ingest stage of a call: unpack / extract of a decompression, the expansion of a compact list, or the
+  // seeded masks of tfhe_hip_oprf)
   std::vector<hipEvent_t> ev[TIMING_SLOTS];
   std::vector<hipEvent_t> ev_pool;
 };
@@ -544,6 +547,7 @@ void shard_free(shard& s) {
   (void)hipFree(s.d_big);
   (void)hipFree(s.d_acc);
   (void)hipFree(s.d_expand);
+  (void)hipFree(s.d_oprf);
   (void)hipFree(s.d_stage);
   if (s.ws_free) (void)hipEventDestroy(s.ws_free);
   if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -753,6 +757,41 @@ int expand_cast_device(tfhe_ctx* c, shard& s, const u64* d_list, size_t count, u
   RC_TRY(grow(s, (void**)&s.d_expand, &s.expand_cap, rows * ((size_t)dim + 1) * sizeof(u64)));
   RC_TRY(expand_device(c, s, d_list, count, dim, rep, rows, s.d_expand, st));
   return pbs_device(c, s, s.d_expand, rows, d_luts, n_lut, d_idx, nullptr, d_out, st);
+}
+
+// tfhe_hip_oprf*: every check that precedes device work
+int oprf_check(const tfhe_ctx* c, const void* seeds, size_t rows, const void* luts, const void* post_adds, size_t n_lut,
+               const void* out) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "oprf: null ctx");
+  if (!c->bsk) return fail(TFHE_HIP_ENOKEYS, "oprf: bootstrapping key not loaded");
+  if (c->p.order == 0 && !c->keys)
+    return fail(TFHE_HIP_ENOKEYS, "oprf: a PBS -> KS parameter set keyswitches the result: keyswitching key not loaded");
+  if (rows > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "oprf: rows = %zu, too many rows for one call", rows);
+  if (!n_lut) return fail(TFHE_HIP_EINVAL, "oprf: n_lut == 0");
+  if (rows && (!seeds || !luts || !post_adds || !out)) return fail(TFHE_HIP_EINVAL, "oprf: null buffer");
+  return 0;
+}
+
+// The seeded masks (slot 3)
+int csprng_device(tfhe_ctx* c, shard& s, const u64* d_seeds, size_t rows, u64 first_word, u32 dim, size_t row_stride,
+                  bool zero_body, u64* d_out, hipStream_t st) {
+  timed_begin(c, s, 3, st);
+  HIP_TRY(tfhe::launch_csprng_rows(d_seeds, rows, first_word, dim, row_stride, zero_body, d_out, st));
+  timed_end(c, s, 3, st);
+  return 0;
+}
+
+// OPRF on device buffers (caller as pbs_device): the masks of the rows' seeds with body 0 into the shard's d_oprf
+// workspace (d_big is pbs_device's own), the rotation alone (order 1) or the full PBS (order 0), then the post-add.
+int oprf_device(tfhe_ctx* c, shard& s, const u64* d_seeds, size_t rows, const u64* d_luts, const u64* d_post,
+                size_t n_lut, const u32* d_idx, u64* d_out, hipStream_t st) {
+  const size_t small = (size_t)c->p.n + 1;
+  RC_TRY(grow(s, (void**)&s.d_oprf, &s.oprf_cap, rows * small * sizeof(u64)));
+  RC_TRY(csprng_device(c, s, d_seeds, rows, 0, c->p.n, small, true, s.d_oprf, st));
+  if (c->p.order == 1) RC_TRY(bootstrap_device(c, s, s.d_oprf, rows, d_luts, n_lut, d_idx, d_out, st));
+  else RC_TRY(pbs_device(c, s, s.d_oprf, rows, d_luts, n_lut, d_idx, nullptr, d_out, st));
+  HIP_TRY(tfhe::launch_body_add(d_out, rows, (size_t)io_dim(c->p) + 1, d_post, n_lut, d_idx, st));
+  return 0;
 }
 
 }  // namespace
@@ -1233,6 +1272,91 @@ int tfhe_hip_expand_cast(tfhe_ctx* c, const uint64_t* list, size_t list_words, s
                        return expand_cast_device(c, s, (const u64*)d[0], count, rep, rows, (const u64*)d[1], n_lut,
                                                  (const u32*)d[2], (u64*)d[3], s.stream);
                      });
+}
+
+int tfhe_hip_lut_oprf(uint32_t N, uint32_t random_bits, uint32_t full_bits, uint64_t* lut, uint64_t* post_add) {
+  if (!N || (N & (N - 1)) || !lut || !post_add) return fail(TFHE_HIP_EINVAL, "lut_oprf: bad arguments (N = %u)", N);
+  if (random_bits < 1 || random_bits >= full_bits || full_bits > 63)
+    return fail(TFHE_HIP_EINVAL, "lut_oprf: need 1 <= random_bits < full_bits <= 63, got %u and %u", random_bits,
+                full_bits);
+  const uint64_t p = 1ull << random_bits;
+  if (p > 2ull * N) return fail(TFHE_HIP_EINVAL, "lut_oprf: 2^random_bits = 2^%u exceeds 2N = %u", random_bits, 2 * N);
+  const uint64_t half = 1ull << (63 - full_bits), box = 2ull * N / p;  // delta / 2; x values per step
+  for (uint32_t x = 0; x < N; x++) lut[x] = (2 * (x / box) + 1) * half;
+  *post_add = (p - 1) * half;
+  return 0;
+}
+
+// tfhe_hip_csprng_rows*: every check that precedes device work; rows == 0 passes
+static int csprng_check(const tfhe_ctx* c, const void* seeds, size_t rows, uint64_t first_word, uint32_t dim,
+                        size_t row_stride, const void* out) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "csprng_rows: null ctx");
+  if (!dim) return fail(TFHE_HIP_EINVAL, "csprng_rows: dim == 0");
+  if (row_stride < dim) return fail(TFHE_HIP_EINVAL, "csprng_rows: row_stride = %zu < dim = %u", row_stride, dim);
+  if (first_word > (1ull << 60) || dim > (1ull << 60) - first_word)
+    return fail(TFHE_HIP_EINVAL, "csprng_rows: first_word + dim exceeds 2^60");
+  if (rows > 0x7FFFFFFF || rows > 0x7FFFFFFF / (((size_t)dim + 1021) / 1022))
+    return fail(TFHE_HIP_EINVAL, "csprng_rows: rows = %zu x dim = %u, too large for one call", rows, dim);
+  if (rows && (!seeds || !out)) return fail(TFHE_HIP_EINVAL, "csprng_rows: null buffer");
+  return 0;
+}
+
+int tfhe_hip_csprng_rows_async(tfhe_ctx* c, const uint64_t* d_seeds, size_t rows, uint64_t first_word, uint32_t dim,
+                               size_t row_stride, uint64_t* d_out, void* stream) {
+  RC_TRY(csprng_check(c, d_seeds, rows, first_word, dim, row_stride, d_out));
+  if (rows == 0) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  size_t si = 0;
+  RC_TRY(shard_of_input(c, "csprng_rows", d_seeds, &si));
+  shard& s = c->sh[si];
+  DeviceGuard g(s.device);
+  return csprng_device(c, s, d_seeds, rows, first_word, dim, row_stride, false, d_out, resolve_stream(stream, s.stream));
+}
+
+int tfhe_hip_csprng_rows(tfhe_ctx* c, const uint64_t* seeds, size_t rows, uint64_t first_word, uint32_t dim,
+                         uint64_t* out) {
+  RC_TRY(csprng_check(c, seeds, rows, first_word, dim, dim, out));
+  if (rows == 0) return 0;
+  const size_t out_bytes = rows * (size_t)dim * 8;
+  return staged_call(c, {{seeds, rows * 16}}, out_bytes, {{out, 1, out_bytes}}, [&](shard& s, std::vector<void*>& d) {
+    return csprng_device(c, s, (const u64*)d[0], rows, first_word, dim, dim, false, (u64*)d[1], s.stream);
+  });
+}
+
+int tfhe_hip_oprf_async(tfhe_ctx* c, const uint64_t* d_seeds, size_t rows, const uint64_t* d_luts,
+                        const uint64_t* d_post_adds, size_t n_lut, const uint32_t* d_idx, uint64_t* d_out,
+                        void* stream) {
+  RC_TRY(oprf_check(c, d_seeds, rows, d_luts, d_post_adds, n_lut, d_out));
+  if (rows == 0) return 0;
+  std::lock_guard<std::mutex> lk(c->mu);
+  size_t si = 0;
+  RC_TRY(shard_of_input(c, "oprf", d_seeds, &si));
+  shard& s = c->sh[si];
+  DeviceGuard g(s.device);
+  hipStream_t st = resolve_stream(stream, s.stream);
+  RC_TRY(ws_begin(s, st));
+  RC_TRY(oprf_device(c, s, d_seeds, rows, d_luts, d_post_adds, n_lut, d_idx, d_out, st));
+  return ws_end(s, st);
+}
+
+int tfhe_hip_oprf(tfhe_ctx* c, const uint64_t* seeds, size_t rows, const uint64_t* luts, const uint64_t* post_adds,
+                  size_t n_lut, const uint32_t* lut_index, uint64_t* lwe_out) {
+  RC_TRY(oprf_check(c, seeds, rows, luts, post_adds, n_lut, lwe_out));
+  if (rows == 0) return 0;
+  RC_TRY(host_lut_index_check("oprf", lut_index, rows, n_lut));
+  std::lock_guard<std::mutex> lk(c->mu);
+  const size_t out_dim = (size_t)io_dim(c->p) + 1;
+  return for_each_slice(c, rows, [&](size_t i, size_t lo, size_t hi) -> int {
+    const size_t b = hi - lo;
+    return staged_run(c->sh[i],
+                      {{seeds + 2 * lo, b * 16}, {luts, n_lut * c->p.N * 8}, {post_adds, n_lut * 8},
+                       {lut_index ? lut_index + lo : nullptr, lut_index ? b * 4 : 0}},
+                      b * out_dim * 8, {{lwe_out + lo * out_dim, 4, b * out_dim * 8}},
+                      [&](shard& s, std::vector<void*>& d) {
+                        return oprf_device(c, s, (const u64*)d[0], b, (const u64*)d[1], (const u64*)d[2], n_lut,
+                                           (const u32*)d[3], (u64*)d[4], s.stream);
+                      });
+  });
 }
 
 int tfhe_hip_blind_rotate(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,

@@ -117,4 +117,13 @@ hipError_t launch_unpack_extract(const u64* packed, size_t count, int k, int N, 
 // rows == 0 launches nothing
 hipError_t launch_expand_compact(const u64* list, size_t count, int lwe_dim, int rep, size_t rows, u64* out,
                                  hipStream_t s);
+// ---- csprng.hip: the seeded mask stream (seeded.cpp csprng_words) on the device.  Row r of `out` (at
+// out + r * row_stride) gets words first_word .. first_word + dim - 1 of the stream of seed (seeds[2r], seeds[2r+1]);
+// zero_body also sets word dim to 0.  first_word + dim <= 2^60, row_stride >= dim (+ 1 with zero_body) and
+// rows * ceil(dim / 1022) <= 0x7FFFFFFF (hipErrorInvalidValue otherwise); rows == 0 or dim == 0 launches nothing
+hipError_t launch_csprng_rows(const u64* seeds, size_t rows, u64 first_word, u32 dim, size_t row_stride,
+                              bool zero_body, u64* out, hipStream_t s);
+// body (last word) of row r of rows x row_len += post_add[idx ? idx[r] : 0]
+hipError_t launch_body_add(u64* lwes, size_t rows, size_t row_len, const u64* post_add, size_t n_lut, const u32* idx,
+                           hipStream_t s);
 }  // namespace tfhe

@@ -232,6 +232,30 @@ class Circuit:
             off += cnt
         return res
 
+    def oprf(self, row_seeds):
+        """Oblivious pseudo-random bits (tfhe-rs ``generate_oblivious_pseudo_random*`` on the gate encoding): (R, 2)
+        row seeds -> (R, dim) gate-encoded bits, true iff the seeded mask's phase falls in the first half of the
+        rotation (gate LUT, post-add 0).  One ``Engine.oprf`` launch (``oprf_device`` for a device-resident
+        circuit), in chunks of MAX_LAUNCH rows; the masks never exist on the host."""
+        seeds = np.ascontiguousarray(np.asarray(row_seeds, dtype=np.uint64)).reshape(-1, 2)
+        R = seeds.shape[0]
+        if self.device is not None:
+            import torch
+            d_seeds = torch.from_numpy(seeds.view(np.int64)).to(self.device)
+            d_post = torch.zeros(1, dtype=torch.int64, device=self.device)
+            outs = [self.engine.oprf_device(d_seeds[o:o + MAX_LAUNCH], self._lut_d, d_post)
+                    for o in range(0, R, MAX_LAUNCH)]
+            out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0) if outs else \
+                torch.zeros((0, self.dim), dtype=torch.int64, device=self.device)
+        else:
+            outs = [self.engine.oprf(seeds[o:o + MAX_LAUNCH], self.lut, [0]) for o in range(0, R, MAX_LAUNCH)]
+            out = outs[0] if len(outs) == 1 else np.concatenate(outs, axis=0) if outs else \
+                np.zeros((0, self.dim), np.uint64)
+        if R:
+            self.pbs_count += R
+            self.launches += 1
+        return out
+
     def run(self, op: Op):
         return self.run_many([op])[0]
 
@@ -548,6 +572,32 @@ class FheUint:
     @classmethod
     def trivial(cls, circuit: Circuit, values, width: int) -> "FheUint":
         return cls(circuit, circuit.trivial(cls._bits_of(values, width)))
+
+    @classmethod
+    def rand(cls, circuit: Circuit, seeds, width: int) -> "FheUint":
+        """fhEVM ``rand``: one uniform ``width``-bit value per (lo, hi) request seed of ``seeds`` (one pair or a (B, 2)
+        array), one OPRF row per bit."""
+        return cls.rand_bounded(circuit, seeds, width, 1 << width)
+
+    @classmethod
+    def rand_bounded(cls, circuit: Circuit, seeds, width: int, bound: int) -> "FheUint":
+        """fhEVM ``randBounded``: uniform in [0, bound) for bound = 2^t, 1 <= t <= width (anything else raises
+        ValueError: fhEVM requires a power of two): t random bits, the rest trivial false.  Request b draws the row
+        seed of bit j from its own seed as ``oprf_block_seeds`` states (words (2j, 2j + 1) of the seed's stream)."""
+        from . import oprf_block_seeds
+        b = int(bound)
+        if b < 2 or b & (b - 1):
+            raise ValueError(f"randBounded: the bound must be a power of two >= 2 (fhEVM), got {bound}")
+        t = b.bit_length() - 1
+        if width < 1 or t > width:
+            raise ValueError(f"randBounded: bound 2^{t} exceeds the type's 2^{width}")
+        parents = np.asarray(seeds, dtype=object).reshape(-1, 2)
+        B = parents.shape[0]
+        rows = np.concatenate([oprf_block_seeds((int(s[0]), int(s[1])), t) for s in parents], axis=0)
+        bits = circuit.oprf(rows).reshape(B, t, circuit.dim)
+        if t < width:
+            bits = _cat([bits, _zeros(circuit, B, width - t)], 1)
+        return cls(circuit, bits)
 
     def decrypt(self, ck: ClientKey) -> np.ndarray:
         return decrypt_bits(ck, self.bits)

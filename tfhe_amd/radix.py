@@ -27,6 +27,7 @@ import numpy as np
 MSG = 4                     # message modulus
 SPACE = 16                  # message x carry
 DELTA = (1 << 63) // SPACE  # one padding bit
+FULL_BITS = 5               # padding bit + carry + message: DELTA = 2^(64 - FULL_BITS)
 _M64 = 1 << 64
 
 
@@ -165,6 +166,35 @@ class RadixCircuit:
         luts = np.stack([self.lut(t) for t in tables])
         return self.engine.pbs(flat, luts, idx)
 
+    def oprf_lut(self, random_bits: int):
+        """(lut, post_add) of ``random_bits`` uniform bits in a block of this encoding (``lut_oprf``), cached."""
+        key = ("oprf", int(random_bits))
+        if key not in self._luts:
+            from . import lut_oprf
+            self._luts[key] = lut_oprf(self.N, int(random_bits), FULL_BITS)
+        return self._luts[key]
+
+    def oprf(self, row_seeds, random_bits) -> np.ndarray:
+        """Oblivious pseudo-random blocks (tfhe-rs ``generate_oblivious_pseudo_random*``): (R, 2) row seeds -> (R, dim)
+        clean blocks of ``random_bits`` uniform bits each (one number, or one per row).  One ``Engine.oprf`` launch
+        (in chunks of MAX_LAUNCH rows): the masks come from the seeds on the device, one blind rotation per row."""
+        seeds = np.ascontiguousarray(np.asarray(row_seeds, dtype=np.uint64)).reshape(-1, 2)
+        rb = np.broadcast_to(np.asarray(random_bits, dtype=np.int64), (seeds.shape[0],))
+        if seeds.shape[0] == 0:
+            return np.zeros((0, self.dim), dtype=np.uint64)
+        kinds = sorted({int(b) for b in rb})
+        idx = np.searchsorted(np.array(kinds), rb).astype(np.uint32)
+        outs = [self._oprf(seeds[o:o + MAX_LAUNCH], kinds, idx[o:o + MAX_LAUNCH])
+                for o in range(0, seeds.shape[0], MAX_LAUNCH)]
+        self.pbs_count += seeds.shape[0]
+        self.launches += 1
+        return outs[0] if len(outs) == 1 else np.concatenate(outs, axis=0)
+
+    def _oprf(self, seeds, bit_kinds, idx):
+        """(cnt, 2) -> (cnt, dim): row q gets ``bit_kinds[idx[q]]`` random bits."""
+        tabs = [self.oprf_lut(b) for b in bit_kinds]
+        return self.engine.oprf(seeds, np.stack([t[0] for t in tabs]), [t[1] for t in tabs], idx)
+
     def run(self, op):
         return self.run_many([op])[0]
 
@@ -274,6 +304,16 @@ class RadixUint:
             return RadixUint(self.c, self.blocks[:, :nb])
         pad = _const(self.c, (self.batch, nb - self.blocks.shape[1]), 0)
         return RadixUint(self.c, np.concatenate([self.blocks, pad], axis=1))
+
+    @classmethod
+    def rand(cls, c: RadixCircuit, seeds, w: int) -> "RadixUint":
+        """fhEVM ``rand``: one uniform w-bit value per (lo, hi) seed of ``seeds`` (``g_rand``)."""
+        return c.run(g_rand(c, seeds, w))
+
+    @classmethod
+    def rand_bounded(cls, c: RadixCircuit, seeds, w: int, bound: int) -> "RadixUint":
+        """fhEVM ``randBounded``: uniform in [0, bound), bound a power of two <= 2^w (``g_rand_bounded``)."""
+        return c.run(g_rand_bounded(c, seeds, w, bound))
 
 
 # --------------------------------------------------------------------------------------------
@@ -542,6 +582,75 @@ def g_div_rem_scalar(c, a, d: int):
     qd = yield from g_mul(c, q, d)
     r = yield from g_sub(c, a, qd)
     return q, r
+
+
+def _request_seeds(seeds) -> np.ndarray:
+    """One (lo, hi) seed, or a (B, 2) array of them -> (B, 2) uint64."""
+    s = np.asarray([[int(v) % _M64 for v in row] for row in np.asarray(seeds, dtype=object).reshape(-1, 2)],
+                   dtype=np.uint64)
+    return s.reshape(-1, 2)
+
+
+def _rand_bits(bound) -> int:
+    b = int(bound)
+    if b < 2 or b & (b - 1):
+        raise ValueError(f"randBounded: the bound must be a power of two >= 2 (fhEVM), got {bound}")
+    return b.bit_length() - 1
+
+
+def g_rand_bounded(c: RadixCircuit, seeds, w: int, bound: int):
+    """fhEVM ``randBounded``: per request seed one value uniform in [0, bound), bound = 2^t with 1 <= t <= w.  The
+    value is t // 2 two-bit blocks, a one-bit block if t is odd, then trivial zeros up to w / 2 blocks.  Request b
+    draws the row seeds of its random blocks, in block order, from its seed (``oprf_block_seeds``: words (2j, 2j + 1)
+    of the seed's stream).  No level of the lockstep executor: the blocks are one ``RadixCircuit.oprf`` launch."""
+    from . import oprf_block_seeds
+    yield from ()
+    t = _rand_bits(bound)
+    if w < 2 or w % 2:
+        raise ValueError(f"radix rand: width {w} is not a positive multiple of the 2-bit block (ebool: g_rand_bool)")
+    if t > w:
+        raise ValueError(f"randBounded: bound 2^{t} exceeds the type's 2^{w}")
+    parents = _request_seeds(seeds)
+    B, nb, nr = parents.shape[0], w // 2, (t + 1) // 2
+    bits = np.array([2] * (t // 2) + [1] * (t % 2), dtype=np.int64)
+    rows = np.concatenate([oprf_block_seeds(s, nr) for s in parents], axis=0)
+    rnd = c.oprf(rows, np.tile(bits, B)).reshape(B, nr, c.dim)
+    if nr == nb:
+        return RadixUint(c, rnd)
+    return RadixUint(c, np.concatenate([rnd, _const(c, (B, nb - nr), 0)], axis=1))
+
+
+def g_rand(c: RadixCircuit, seeds, w: int):
+    """fhEVM ``rand``: per request seed one uniform w-bit value (every block random)."""
+    return (yield from g_rand_bounded(c, seeds, w, 1 << w))
+
+
+def g_rand_bool(c: RadixCircuit, seeds):
+    """fhEVM ``rand`` on ebool: an encrypted bool block (B, dim) holding a uniform 0 / 1, from block seed 0 of each
+    request seed."""
+    from . import oprf_block_seeds
+    yield from ()
+    rows = np.concatenate([oprf_block_seeds(s, 1) for s in _request_seeds(seeds)], axis=0)
+    return c.oprf(rows, 1)
+
+
+RADIX_RAND_OPS = ("rand", "randBounded")
+
+
+def fhevm_rand(c: RadixCircuit, op: str, seeds, w: int, bound=None):
+    """The two random fhEVM operators (coroutine, as ``fhevm_op``): ``rand`` gives a RadixUint of width w, or for
+    w == 1 (ebool) an encrypted bool block; ``randBounded`` takes a power-of-two ``bound``."""
+    if op not in RADIX_RAND_OPS:
+        raise ValueError(f"radix random operator {op!r} not supported")
+    if op == "rand":
+        if bound is not None:
+            raise ValueError("rand takes no bound (randBounded does)")
+        if w == 1:
+            return (yield from g_rand_bool(c, seeds))
+        return (yield from g_rand(c, seeds, w))
+    if bound is None:
+        raise ValueError("randBounded needs a bound")
+    return (yield from g_rand_bounded(c, seeds, w, bound))
 
 
 RADIX_OPS = ("add", "sub", "mul", "div", "rem", "and", "or", "xor", "eq", "ne", "lt", "le", "gt", "ge", "min", "max",
