@@ -454,6 +454,40 @@ int tfhe_hip_oprf_async(tfhe_ctx* ctx, const uint64_t* d_seeds, size_t rows, con
                         const uint64_t* d_post_adds, size_t n_lut, const uint32_t* d_lut_index, uint64_t* d_lwe_out,
                         void* stream);
 
+/* ---- sparse linear combinations of LWE rows: the linear part of a radix circuit level -----------------------
+ * tfhe-rs lwe_ciphertext_add_assign / lwe_ciphertext_cleartext_mul_assign / lwe_ciphertext_plaintext_add_assign
+ * (what shortint's unchecked_add, unchecked_scalar_mul and the bivariate 4x + y of apply_bivariate_lookup_table
+ * reduce to; the reference's call site of a server-side operation is ml/extensions/rust/src/ml.rs:88), applied to
+ * a whole circuit level at once (tfhe_amd/csrc/lincomb.hip).  Output row r of `dim` words is, mod 2^64,
+ *   out[r][j] = sum over t in row_start[r] .. row_start[r + 1] - 1 of term_coef[t] * B_t[j],  j < dim
+ *   out[r][dim - 1] += bias[r]
+ * with B_t row term_row[t] of source buffer term_buf[t].  A row without terms is a trivial ciphertext (zero mask,
+ * body bias[r]); a source may repeat within a row and across rows; rows of any dim are 8-byte aligned only.
+ * row_start (rows + 1 entries), term_buf, term_row (u32), term_coef (u64) and bias (u64, null = none) are HOST
+ * arrays in every form: the library checks them, resolves each term to an address and stages the result through
+ * pinned memory of its own, so no kernel sees an address that was not checked.  Every check precedes device work:
+ * EINVAL for a null ctx or buffer, dim == 0, row_start[0] != 0, a decreasing row_start, term_buf[t] >= n_buf,
+ * term_row[t] >= buf_rows[term_buf[t]], rows > 0x7FFFFFFF (the term count is a u32 by construction), or an output
+ * range that overlaps a source buffer; rows == 0 returns OK and launches nothing.  Needs no key.  Timing: slot 3. */
+/* host form: one source buffer src of src_rows x dim words (the terms have no term_buf), out: rows x dim; shard 0 */
+int tfhe_hip_lwe_lincomb(tfhe_ctx* ctx, uint32_t dim, const uint64_t* src, size_t src_rows, const uint32_t* row_start,
+                         const uint32_t* term_row, const uint64_t* term_coef, const uint64_t* bias, size_t rows,
+                         uint64_t* out);
+/* _async: d_bufs is a HOST array of n_buf device base pointers, buffer b holding buf_rows[b] x dim words; d_out:
+ * rows x dim on the device, on the shard whose device holds it; enqueued on `stream` (stream rules of
+ * tfhe_hip_pbs_async; the staged description is a workspace of the shard and ordered as there). */
+int tfhe_hip_lwe_lincomb_async(tfhe_ctx* ctx, uint32_t dim, const uint64_t* const* d_bufs, const size_t* buf_rows,
+                               size_t n_buf, const uint32_t* row_start, const uint32_t* term_buf,
+                               const uint32_t* term_row, const uint64_t* term_coef, const uint64_t* bias, size_t rows,
+                               uint64_t* d_out, void* stream);
+/* The same map with dim = io_dim + 1 into a workspace of the ctx, then the PBS of tfhe_hip_pbs_async on the
+ * assembled rows, in one call: d_lwe_out: rows x (io_dim + 1).  Checks of both; ENOKEYS without keys.  d_lwe_out is
+ * written only after the assembly has read its sources. */
+int tfhe_hip_lincomb_pbs_async(tfhe_ctx* ctx, const uint64_t* const* d_bufs, const size_t* buf_rows, size_t n_buf,
+                               const uint32_t* row_start, const uint32_t* term_buf, const uint32_t* term_row,
+                               const uint64_t* term_coef, const uint64_t* bias, size_t rows, const uint64_t* d_luts,
+                               size_t n_lut, const uint32_t* d_lut_index, uint64_t* d_lwe_out, void* stream);
+
 /* ---- switch-and-squash: noise squashing to a 128-bit LWE ----------------------
  * fhEVM's sns-worker (coprocessor-docker-compose.yml:124-140) turns each 64-bit P-FHEVM ciphertext into
  * a Z_2^128 LWE with tiny noise for threshold decryption: keyswitch to the small key, modulus-switch

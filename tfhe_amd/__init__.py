@@ -123,6 +123,7 @@ ABI_SYMBOLS = (
     "tfhe_hip_sns_pks_pack_async", "tfhe_hip_sns_pks_pack_host", "tfhe_hip_sns_pks_packed_words",
     "tfhe_hip_sns_pks_compress", "tfhe_hip_sns_pks_extract", "tfhe_hip_glwe_phase128",
     "tfhe_hip_lut_oprf", "tfhe_hip_csprng_rows", "tfhe_hip_csprng_rows_async", "tfhe_hip_oprf", "tfhe_hip_oprf_async",
+    "tfhe_hip_lwe_lincomb", "tfhe_hip_lwe_lincomb_async", "tfhe_hip_lincomb_pbs_async",
 )
 
 # P-FHEVM modulus-switch noise reduction key (include/tfhe_hip.h TFHE_HIP_MS_FHEVM_*)
@@ -246,6 +247,14 @@ def lib():
         L.tfhe_hip_oprf_async.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p]
+        _terms = [_U32P, _U32P, _U32P, _U64P, _U64P, ctypes.c_size_t]  # row_start, term_buf, term_row, term_coef, bias, rows
+        _bufs = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_size_t]
+        L.tfhe_hip_lwe_lincomb.argtypes = [ctypes.c_void_p, ctypes.c_uint32, _U64P, ctypes.c_size_t, _U32P, _U32P, _U64P,
+                                           _U64P, ctypes.c_size_t, _U64P]
+        L.tfhe_hip_lwe_lincomb_async.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + _bufs + _terms + [
+            ctypes.c_void_p, ctypes.c_void_p]
+        L.tfhe_hip_lincomb_pbs_async.argtypes = [ctypes.c_void_p] + _bufs + _terms + [
+            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         _LIB = L
     return _LIB
 
@@ -811,6 +820,97 @@ class Engine:
         d_out = d_seeds.new_empty((d_seeds.shape[0], self.params.io_dim + 1))
         if d_seeds.shape[0]:
             self.oprf_async(d_seeds.contiguous(), d_luts, d_post_adds, d_out, d_lut_index)
+        return d_out
+
+    # -- sparse linear combinations of rows: the linear part of a radix level (radix.LinBlocks builds the terms) ----
+    @staticmethod
+    def _lincomb_terms(row_start, term_buf, term_row, term_coef, bias):
+        """The host term description -> (arrays to keep alive, the C arguments row_start .. rows).  Only what the C
+        checks cannot see is checked here: that the arrays are as long as ``row_start`` says."""
+        rs = np.ascontiguousarray(np.asarray(row_start, dtype=np.uint32)).reshape(-1)
+        tb = np.ascontiguousarray(np.asarray(term_buf, dtype=np.uint32)).reshape(-1)
+        tr = np.ascontiguousarray(np.asarray(term_row, dtype=np.uint32)).reshape(-1)
+        tc = _c_u64(term_coef).reshape(-1)
+        bs = None if bias is None else _c_u64(bias).reshape(-1)
+        rows = max(rs.shape[0] - 1, 0)
+        need = int(rs.max(initial=0))
+        if min(tb.shape[0], tr.shape[0], tc.shape[0]) < need:
+            raise ValueError("lincomb: row_start names more terms than the term arrays hold")
+        if bs is not None and bs.shape[0] != rows:
+            raise ValueError("lincomb: one bias per output row")
+        args = (rs.ctypes.data_as(_U32P), tb.ctypes.data_as(_U32P), tr.ctypes.data_as(_U32P), _u64(tc),
+                _u64(bs) if bs is not None else None, rows)
+        return (rs, tb, tr, tc, bs), args
+
+    @staticmethod
+    def _lincomb_bufs(d_bufs, dim: int):
+        """Device tensors -> (tensors to keep alive, the C arguments d_bufs, buf_rows, n_buf)."""
+        keep = [b if b.is_contiguous() else b.contiguous() for b in d_bufs]
+        ptrs = (ctypes.c_void_p * max(len(keep), 1))(*[b.data_ptr() for b in keep])
+        nrow = (ctypes.c_size_t * max(len(keep), 1))(*[b.numel() // dim for b in keep])
+        return keep, (ptrs, nrow, len(keep))
+
+    def lincomb(self, bufs, row_start, term_buf, term_row, term_coef, bias=None, dim: Optional[int] = None) -> np.ndarray:
+        """Sparse linear combinations of LWE rows over host arrays, mod 2^64 (``radix.lincomb_ref`` states the map):
+        output row r = the sum over its terms t of ``term_coef[t]`` times row ``term_row[t]`` of ``bufs[term_buf[t]]``,
+        plus ``bias[r]`` on the body; a row without terms is trivial.  ``bufs``: arrays of (rows_b, dim) words.  The
+        C host form takes one source buffer, so the buffers are joined here.  Needs no key."""
+        bufs = [_c_u64(b) for b in bufs]
+        dim = int(dim if dim is not None else (bufs[0].shape[-1] if bufs else self.params.io_dim + 1))
+        bufs = [b.reshape(-1, dim) for b in bufs]
+        base = np.concatenate([[0], np.cumsum([b.shape[0] for b in bufs])]).astype(np.int64)
+        src = np.concatenate(bufs, axis=0) if bufs else np.zeros((0, dim), dtype=np.uint64)
+        tb = np.asarray(term_buf, dtype=np.int64).reshape(-1)
+        tr = np.asarray(term_row, dtype=np.int64).reshape(-1)
+        if tb.size and (tb.min() < 0 or tb.max() >= len(bufs) or np.any(tr >= base[tb + 1] - base[tb])):
+            raise ValueError("lincomb: a term names a buffer or a row that does not exist")
+        keep, (rs, _, trp, tc, bs, rows) = self._lincomb_terms(row_start, np.zeros_like(tb), tr + base[tb], term_coef, bias)
+        out = np.zeros((rows, dim), dtype=np.uint64)
+        _check(lib().tfhe_hip_lwe_lincomb(self._h, dim, _u64(src), src.shape[0], rs, trp, tc, bs, rows, _u64(out)))
+        del keep
+        return out
+
+    def lincomb_async(self, d_bufs, row_start, term_buf, term_row, term_coef, bias, d_out, stream=None) -> None:
+        """Device-resident ``lincomb`` (``d_bufs``: torch tensors of (rows_b, dim) words on this device, d_out: (rows,
+        dim), overlapping none of them), enqueued on ``stream`` like ``pbs_async``.  The term arrays stay host
+        arrays: the library checks them and resolves the addresses itself."""
+        dim = int(d_out.shape[-1])
+        keep_b, bufs = self._lincomb_bufs(d_bufs, dim)
+        keep_t, terms = self._lincomb_terms(row_start, term_buf, term_row, term_coef, bias)
+        _check(lib().tfhe_hip_lwe_lincomb_async(self._h, dim, *bufs, *terms, ctypes.c_void_p(d_out.data_ptr()),
+                                                ctypes.c_void_p(_stream_handle(stream, self.device))))
+        del keep_b, keep_t
+
+    def _lincomb_out(self, d_bufs, rows: int, dim: int):
+        if d_bufs:
+            return d_bufs[0].new_empty((rows, dim))
+        import torch
+        return torch.empty((rows, dim), dtype=torch.int64, device=f"cuda:{self.device}")
+
+    def lincomb_device(self, d_bufs, row_start, term_buf, term_row, term_coef, bias=None, dim: Optional[int] = None):
+        """lincomb_async into a fresh (rows, dim) tensor on torch's current stream (no host synchronisation); ``dim``
+        defaults to the row length of the first buffer, or io_dim + 1 without buffers."""
+        dim = int(dim if dim is not None else (d_bufs[0].shape[-1] if d_bufs else self.params.io_dim + 1))
+        rows = max(len(row_start) - 1, 0)
+        d_out = self._lincomb_out(d_bufs, rows, dim)
+        if rows:
+            self.lincomb_async(d_bufs, row_start, term_buf, term_row, term_coef, bias, d_out)
+        return d_out
+
+    def lincomb_pbs_device(self, d_bufs, row_start, term_buf, term_row, term_coef, bias, d_luts, d_lut_index=None):
+        """``lincomb_device`` at dim = io_dim + 1 into a workspace of the engine, then ``pbs_device`` of the assembled
+        rows, in one call: a fresh (rows, io_dim + 1) tensor, queued on torch's current stream."""
+        dim = self.params.io_dim + 1
+        rows = max(len(row_start) - 1, 0)
+        d_out = self._lincomb_out(d_bufs, rows, dim)
+        if rows:
+            keep_b, bufs = self._lincomb_bufs(d_bufs, dim)
+            keep_t, terms = self._lincomb_terms(row_start, term_buf, term_row, term_coef, bias)
+            _check(lib().tfhe_hip_lincomb_pbs_async(
+                self._h, *bufs, *terms, ctypes.c_void_p(d_luts.data_ptr()), d_luts.numel() // self.params.N,
+                ctypes.c_void_p(d_lut_index.data_ptr()) if d_lut_index is not None else None,
+                ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(_stream_handle(None, self.device))))
+            del keep_b, keep_t
         return d_out
 
     def sample_extract_many(self, acc: np.ndarray, n_fn: int, stride: int) -> np.ndarray:

@@ -118,6 +118,17 @@ struct tfhe_shard {
   size_t expand_cap = 0;    // bytes
   u64* d_oprf = nullptr;  // seeded masks with body 0, the PBS input of tfhe_hip_oprf (rows x (n + 1))
   size_t oprf_cap = 0;    // bytes
+  u64* d_lin = nullptr;  // assembled rows, the PBS input of tfhe_hip_lincomb_pbs (rows x (io_dim + 1))
+  size_t lin_cap = 0;    // bytes
+  // term description of a lincomb launch (lincomb_stage): packed on the host into one of two pinned slots, copied
+  // into d_lin_meta; a slot is refilled only after the event recorded behind its previous copy
+  void* d_lin_meta = nullptr;
+  size_t lin_meta_cap = 0;  // bytes
+  void* h_lin_meta[2] = {nullptr, nullptr};
+  size_t h_lin_meta_cap[2] = {0, 0};  // bytes
+  hipEvent_t lin_meta_done[2] = {nullptr, nullptr};
+  bool lin_meta_used[2] = {false, false};
+  int lin_meta_next = 0;
   void* d_stage = nullptr;
   size_t stage_cap = 0;  // bytes
   void* d_ks_dig = nullptr;
@@ -548,6 +559,12 @@ void shard_free(shard& s) {
   (void)hipFree(s.d_acc);
   (void)hipFree(s.d_expand);
   (void)hipFree(s.d_oprf);
+  (void)hipFree(s.d_lin);
+  (void)hipFree(s.d_lin_meta);
+  for (int i = 0; i < 2; i++) {
+    if (s.h_lin_meta[i]) (void)hipHostFree(s.h_lin_meta[i]);
+    if (s.lin_meta_done[i]) (void)hipEventDestroy(s.lin_meta_done[i]);
+  }
   (void)hipFree(s.d_stage);
   if (s.ws_free) (void)hipEventDestroy(s.ws_free);
   if (s.stream) (void)hipStreamDestroy(s.stream);
@@ -791,6 +808,107 @@ int oprf_device(tfhe_ctx* c, shard& s, const u64* d_seeds, size_t rows, const u6
   if (c->p.order == 1) RC_TRY(bootstrap_device(c, s, s.d_oprf, rows, d_luts, n_lut, d_idx, d_out, st));
   else RC_TRY(pbs_device(c, s, s.d_oprf, rows, d_luts, n_lut, d_idx, nullptr, d_out, st));
   HIP_TRY(tfhe::launch_body_add(d_out, rows, (size_t)io_dim(c->p) + 1, d_post, n_lut, d_idx, st));
+  return 0;
+}
+
+// the term description of the tfhe_hip_lwe_lincomb* entry points: host arrays (include/tfhe_hip.h)
+struct lin_desc {
+  const u32* row_start;  // rows + 1 entries
+  const u32* term_buf;   // null: every term reads buffer 0 (the host form)
+  const u32* term_row;
+  const u64* term_coef;
+  const u64* bias;  // null: no bias
+};
+
+// tfhe_hip_lwe_lincomb*: every check of the description that precedes device work; rows == 0 passes.  After it each
+// term names an existing row of an existing buffer.
+int lincomb_check(const char* what, uint32_t dim, const size_t* buf_rows, size_t n_buf, const lin_desc& L, size_t rows) {
+  if (dim == 0) return fail(TFHE_HIP_EINVAL, "%s: dim == 0", what);
+  if (rows > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "%s: rows = %zu, too many rows for one call", what, rows);
+  if (rows == 0) return 0;
+  if (!L.row_start || (n_buf && !buf_rows)) return fail(TFHE_HIP_EINVAL, "%s: null buffer", what);
+  if (L.row_start[0] != 0) return fail(TFHE_HIP_EINVAL, "%s: row_start[0] = %u, must be 0", what, L.row_start[0]);
+  for (size_t r = 0; r < rows; r++)
+    if (L.row_start[r + 1] < L.row_start[r])
+      return fail(TFHE_HIP_EINVAL, "%s: row_start[%zu] = %u < row_start[%zu] = %u", what, r + 1, L.row_start[r + 1], r,
+                  L.row_start[r]);
+  const size_t T = L.row_start[rows];
+  if (T && (!L.term_row || !L.term_coef)) return fail(TFHE_HIP_EINVAL, "%s: null buffer", what);
+  for (size_t b = 0; b < n_buf; b++)
+    if (buf_rows[b] > (1ull << 60) / dim) return fail(TFHE_HIP_EINVAL, "%s: buf_rows[%zu] = %zu too large", what, b, buf_rows[b]);
+  for (size_t t = 0; t < T; t++) {
+    const size_t b = L.term_buf ? L.term_buf[t] : 0;
+    if (b >= n_buf) return fail(TFHE_HIP_EINVAL, "%s: term_buf[%zu] = %zu >= n_buf = %zu", what, t, b, n_buf);
+    if (L.term_row[t] >= buf_rows[b])
+      return fail(TFHE_HIP_EINVAL, "%s: term_row[%zu] = %u >= the %zu rows of buffer %zu", what, t, L.term_row[t],
+                  buf_rows[b], b);
+  }
+  return 0;
+}
+
+// device pointers of tfhe_hip_lwe_lincomb_async / tfhe_hip_lincomb_pbs_async: no null source, and (d_out given) no
+// source range that the output range rows x dim touches
+int lincomb_ptr_check(const char* what, uint32_t dim, const uint64_t* const* d_bufs, const size_t* buf_rows, size_t n_buf,
+                      size_t rows, const uint64_t* d_out) {
+  if (n_buf && !d_bufs) return fail(TFHE_HIP_EINVAL, "%s: null buffer", what);
+  const uintptr_t o_lo = (uintptr_t)d_out, o_hi = o_lo + rows * (size_t)dim * 8;
+  for (size_t b = 0; b < n_buf; b++) {
+    if (!buf_rows[b]) continue;
+    if (!d_bufs[b]) return fail(TFHE_HIP_EINVAL, "%s: source buffer %zu is null", what, b);
+    const uintptr_t lo = (uintptr_t)d_bufs[b], hi = lo + buf_rows[b] * (size_t)dim * 8;
+    if (d_out && o_lo < hi && lo < o_hi) return fail(TFHE_HIP_EINVAL, "%s: the output overlaps source buffer %zu", what, b);
+  }
+  return 0;
+}
+
+// Resolve a checked description into the kernel's arrays.  Terms (address, coefficient), row_start and bias are packed
+// into one pinned slot of the shard and go to d_lin_meta in one copy on `st`; the slot is refilled only after the
+// event behind that copy (the caller's ws_begin / ws_end order d_lin_meta itself across streams).
+int lincomb_stage(shard& s, uint32_t dim, const uint64_t* const* d_bufs, const lin_desc& L, size_t rows, hipStream_t st,
+                  const tfhe::lin_term** d_terms, const u32** d_row_start, const u64** d_bias) {
+  const size_t T = L.row_start[rows];
+  const size_t rs_off = T * sizeof(tfhe::lin_term);
+  const size_t bias_off = (rs_off + (rows + 1) * sizeof(u32) + 15) & ~(size_t)15;
+  const size_t total = bias_off + (L.bias ? rows * sizeof(u64) : 0);
+  RC_TRY(grow(s, &s.d_lin_meta, &s.lin_meta_cap, total));
+  const int k = s.lin_meta_next;
+  s.lin_meta_next ^= 1;
+  if (!s.lin_meta_done[k]) HIP_TRY(hipEventCreateWithFlags(&s.lin_meta_done[k], hipEventDisableTiming));
+  if (s.lin_meta_used[k]) HIP_TRY(hipEventSynchronize(s.lin_meta_done[k]));
+  if (s.h_lin_meta_cap[k] < total) {
+    if (s.h_lin_meta[k]) (void)hipHostFree(s.h_lin_meta[k]);
+    s.h_lin_meta[k] = nullptr;
+    s.h_lin_meta_cap[k] = 0;
+    HIP_TRY(hipHostMalloc(&s.h_lin_meta[k], total, hipHostMallocDefault));
+    s.h_lin_meta_cap[k] = total;
+  }
+  char* h = (char*)s.h_lin_meta[k];
+  tfhe::lin_term* ht = (tfhe::lin_term*)h;
+  for (size_t t = 0; t < T; t++) {
+    ht[t].src = d_bufs[L.term_buf ? L.term_buf[t] : 0] + (size_t)L.term_row[t] * dim;
+    ht[t].coef = L.term_coef[t];
+  }
+  memcpy(h + rs_off, L.row_start, (rows + 1) * sizeof(u32));
+  if (L.bias) memcpy(h + bias_off, L.bias, rows * sizeof(u64));
+  HIP_TRY(hipMemcpyAsync(s.d_lin_meta, h, total, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipEventRecord(s.lin_meta_done[k], st));
+  s.lin_meta_used[k] = true;
+  *d_terms = (const tfhe::lin_term*)s.d_lin_meta;
+  *d_row_start = (const u32*)((char*)s.d_lin_meta + rs_off);
+  *d_bias = L.bias ? (const u64*)((char*)s.d_lin_meta + bias_off) : nullptr;
+  return 0;
+}
+
+// The linear combinations on device buffers (caller as pbs_device, description and pointers checked), timed in slot 3.
+int lincomb_device(tfhe_ctx* c, shard& s, uint32_t dim, const uint64_t* const* d_bufs, const lin_desc& L, size_t rows,
+                   u64* d_out, hipStream_t st) {
+  const tfhe::lin_term* d_terms = nullptr;
+  const u32* d_row_start = nullptr;
+  const u64* d_bias = nullptr;
+  RC_TRY(lincomb_stage(s, dim, d_bufs, L, rows, st, &d_terms, &d_row_start, &d_bias));
+  timed_begin(c, s, 3, st);
+  HIP_TRY(tfhe::launch_lincomb(d_terms, d_row_start, d_bias, rows, dim, d_out, st));
+  timed_end(c, s, 3, st);
   return 0;
 }
 
@@ -1357,6 +1475,67 @@ int tfhe_hip_oprf(tfhe_ctx* c, const uint64_t* seeds, size_t rows, const uint64_
                                            (const u32*)d[3], (u64*)d[4], s.stream);
                       });
   });
+}
+
+int tfhe_hip_lwe_lincomb_async(tfhe_ctx* c, uint32_t dim, const uint64_t* const* d_bufs, const size_t* buf_rows,
+                               size_t n_buf, const uint32_t* row_start, const uint32_t* term_buf,
+                               const uint32_t* term_row, const uint64_t* term_coef, const uint64_t* bias, size_t rows,
+                               uint64_t* d_out, void* stream) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "lwe_lincomb: null ctx");
+  const lin_desc L{row_start, term_buf, term_row, term_coef, bias};
+  RC_TRY(lincomb_check("lwe_lincomb", dim, buf_rows, n_buf, L, rows));
+  if (rows == 0) return 0;
+  if (!d_out || (row_start[rows] && !term_buf)) return fail(TFHE_HIP_EINVAL, "lwe_lincomb: null buffer");
+  RC_TRY(lincomb_ptr_check("lwe_lincomb", dim, d_bufs, buf_rows, n_buf, rows, d_out));
+  std::lock_guard<std::mutex> lk(c->mu);
+  size_t si = 0;
+  RC_TRY(shard_of_input(c, "lwe_lincomb", d_out, &si));
+  shard& s = c->sh[si];
+  DeviceGuard g(s.device);
+  hipStream_t st = resolve_stream(stream, s.stream);
+  RC_TRY(ws_begin(s, st));
+  RC_TRY(lincomb_device(c, s, dim, d_bufs, L, rows, d_out, st));
+  return ws_end(s, st);
+}
+
+int tfhe_hip_lwe_lincomb(tfhe_ctx* c, uint32_t dim, const uint64_t* src, size_t src_rows, const uint32_t* row_start,
+                         const uint32_t* term_row, const uint64_t* term_coef, const uint64_t* bias, size_t rows,
+                         uint64_t* out) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "lwe_lincomb: null ctx");
+  const lin_desc L{row_start, nullptr, term_row, term_coef, bias};
+  RC_TRY(lincomb_check("lwe_lincomb", dim, &src_rows, 1, L, rows));
+  if (rows == 0) return 0;
+  if (!out || (src_rows && !src)) return fail(TFHE_HIP_EINVAL, "lwe_lincomb: null buffer");
+  const size_t out_bytes = rows * (size_t)dim * 8;
+  return staged_call(c, {{src, src_rows * (size_t)dim * 8}}, out_bytes, {{out, 1, out_bytes}},
+                     [&](shard& s, std::vector<void*>& d) {
+                       const uint64_t* bufs[1] = {(const u64*)d[0]};
+                       return lincomb_device(c, s, dim, bufs, L, rows, (u64*)d[1], s.stream);
+                     });
+}
+
+int tfhe_hip_lincomb_pbs_async(tfhe_ctx* c, const uint64_t* const* d_bufs, const size_t* buf_rows, size_t n_buf,
+                               const uint32_t* row_start, const uint32_t* term_buf, const uint32_t* term_row,
+                               const uint64_t* term_coef, const uint64_t* bias, size_t rows, const uint64_t* d_luts,
+                               size_t n_lut, const uint32_t* d_idx, uint64_t* d_out, void* stream) {
+  RC_TRY(pbs_check(c, "lincomb_pbs", d_out, rows, d_luts, n_lut, pbs_kind{}, d_out));
+  const uint32_t dim = io_dim(c->p) + 1;
+  const lin_desc L{row_start, term_buf, term_row, term_coef, bias};
+  RC_TRY(lincomb_check("lincomb_pbs", dim, buf_rows, n_buf, L, rows));
+  if (rows == 0) return 0;
+  if (row_start[rows] && !term_buf) return fail(TFHE_HIP_EINVAL, "lincomb_pbs: null buffer");
+  RC_TRY(lincomb_ptr_check("lincomb_pbs", dim, d_bufs, buf_rows, n_buf, rows, nullptr));
+  std::lock_guard<std::mutex> lk(c->mu);
+  size_t si = 0;
+  RC_TRY(shard_of_input(c, "lincomb_pbs", d_out, &si));
+  shard& s = c->sh[si];
+  DeviceGuard g(s.device);
+  hipStream_t st = resolve_stream(stream, s.stream);
+  RC_TRY(ws_begin(s, st));
+  RC_TRY(grow(s, (void**)&s.d_lin, &s.lin_cap, rows * (size_t)dim * sizeof(u64)));
+  RC_TRY(lincomb_device(c, s, dim, d_bufs, L, rows, s.d_lin, st));
+  RC_TRY(pbs_device(c, s, s.d_lin, rows, d_luts, n_lut, d_idx, nullptr, d_out, st));
+  return ws_end(s, st);
 }
 
 int tfhe_hip_blind_rotate(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,

@@ -126,4 +126,13 @@ hipError_t launch_csprng_rows(const u64* seeds, size_t rows, u64 first_word, u32
 // body (last word) of row r of rows x row_len += post_add[idx ? idx[r] : 0]
 hipError_t launch_body_add(u64* lwes, size_t rows, size_t row_len, const u64* post_add, size_t n_lut, const u32* idx,
                            hipStream_t s);
+// ---- lincomb.hip: out[r] = sum of terms[t].coef * terms[t].src[0 .. dim - 1] over t in row_start[r] ..
+// row_start[r + 1] - 1, body += bias[r] (bias may be null), mod 2^64.  Every terms[t].src is a device row of dim
+// words that the caller has checked and that `out` does not overlap; rows == 0 launches nothing
+struct lin_term {
+  const u64* src;
+  u64 coef;
+};
+hipError_t launch_lincomb(const lin_term* terms, const u32* row_start, const u64* bias, size_t rows, u32 dim, u64* out,
+                          hipStream_t s);
 }  // namespace tfhe

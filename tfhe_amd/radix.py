@@ -51,9 +51,18 @@ class RadixCircuit:
     request (tfhe-rs ``apply_many_lookup_table``): one blind rotation per ciphertext, n_fn results, and the
     caller guarantees every value of ``lin`` is < SPACE / n_fn.  ``many_lut=True`` lets the circuits that
     know such a bound (``g_propagate``) use it; the default keeps every circuit on one table per rotation.
-    ``pbs_count`` counts blind rotations, ``launches`` levels."""
+    ``pbs_count`` counts blind rotations, ``launches`` levels.
 
-    def __init__(self, engine, many_lut: bool = False):
+    ``device`` (a torch device of the engine's one shard, or "cpu") makes the circuit resident: every block array
+    is a ``LinBlocks`` (host-side terms over buffers that stay where they are), the linear work between two levels
+    is never executed on its own, and ``bootstrap`` turns a level into one term description that
+    ``Engine.lincomb_pbs_device`` assembles and bootstraps on torch's current stream; the outputs are new device
+    buffers and nothing synchronises before ``RadixUint.decrypt`` / ``to_host``.  ``device="cpu"`` is the same
+    executor over numpy buffers: it assembles with ``lincomb_ref`` and calls the overridable ``_pbs`` /
+    ``_pbs_many`` / ``_oprf``.  Both give the bits of the default host mode (the maps are exact mod 2^64).
+    ``max_terms`` records the most terms any assembled row had."""
+
+    def __init__(self, engine, many_lut: bool = False, device=None):
         self.engine = engine
         self.many_lut = bool(many_lut)
         p = engine.params
@@ -62,6 +71,88 @@ class RadixCircuit:
         self._luts: Dict[Tuple[int, ...], np.ndarray] = {}
         self.pbs_count = 0
         self.launches = 0
+        self.lazy = device is not None
+        self.device = None
+        self.max_terms = 0
+        if self.lazy and str(device) != "cpu":
+            import torch
+            if len(getattr(engine, "devices", (0,))) > 1:
+                raise ValueError("a device-resident RadixCircuit takes an engine with one shard")
+            self.device = torch.device(device)
+            self._d_cache: Dict = {}
+
+    # ---- the resident executor (device is not None) -----------------------------------------------------------
+    def _lincomb(self, bufs, row_start, term_buf, term_row, term_coef, bias, dim):
+        """The back end of ``LinBlocks.materialize``: a fresh (rows, dim) buffer where the circuit's buffers live."""
+        if self.device is None:
+            return lincomb_ref(bufs, row_start, term_buf, term_row, term_coef, bias, dim)
+        return self.engine.lincomb_device(bufs, row_start, term_buf, term_row, term_coef, bias, dim)
+
+    def wrap(self, buf) -> "LinBlocks":
+        """A (..., dim) buffer of ciphertext words (an int64 torch tensor on the circuit's device; a uint64 numpy
+        array for device="cpu") as a block array of this circuit.  The buffer is referenced, not copied."""
+        if not self.lazy:
+            raise ValueError("wrap: the circuit is not resident (RadixCircuit(engine, device=...))")
+        if isinstance(buf, np.ndarray) != (self.device is None):
+            raise TypeError("wrap: a numpy array for device=\"cpu\", a torch tensor on the device otherwise")
+        if tuple(buf.shape[-1:]) != (self.dim,):
+            raise ValueError(f"wrap: rows of {self.dim} words expected, got shape {tuple(buf.shape)}")
+        return LinBlocks.wrap(buf, self._lincomb)
+
+    def _ingest(self, host: np.ndarray):
+        """Host ciphertexts (..., dim) as a block array of this circuit: one upload in device mode."""
+        if not self.lazy:
+            return host
+        host = np.ascontiguousarray(host, dtype=np.uint64)
+        return self.wrap(host if self.device is None else self._upload(host.view(np.int64)))
+
+    def _upload(self, host: np.ndarray):
+        """numpy -> a tensor on the circuit's device through pinned memory, queued on the current stream."""
+        import torch
+        return torch.from_numpy(host).pin_memory().to(self.device, non_blocking=True)
+
+    def _d_luts(self, key, build):
+        """Device copy of a level's LUT stack, cached by its tables."""
+        if key not in self._d_cache:
+            self._d_cache[key] = self._upload(np.ascontiguousarray(build()).view(np.int64))
+        return self._d_cache[key]
+
+    def _lin_pbs(self, desc, tables, idx):
+        """A chunk of a level, resident: the rows of the term description ``desc`` (``LinBlocks.terms``) assembled
+        and bootstrapped, row q through tables[idx[q]] -> a (cnt, dim) buffer."""
+        if self.device is None:
+            return self._pbs(lincomb_ref(*desc, self.dim), tables, idx)
+        d_luts = self._d_luts(tuple(tables), lambda: np.stack([self.lut(t) for t in tables]))
+        return self.engine.lincomb_pbs_device(*desc, d_luts, self._upload(idx.view(np.int32)))
+
+    def _lin_pbs_many(self, desc, table_groups, idx, n_fn: int):
+        """As ``_lin_pbs`` for many-LUT entries -> a (cnt, n_fn, dim) buffer: the assembly is its own launch here
+        (``lincomb_device``), then ``pbs_many_device``."""
+        if self.device is None:
+            return self._pbs_many(lincomb_ref(*desc, self.dim), table_groups, idx, n_fn)
+        d_luts = self._d_luts(tuple(table_groups), lambda: np.stack([self.many_lut_of(g) for g in table_groups]))
+        lin = self.engine.lincomb_device(*desc, self.dim)
+        return self.engine.pbs_many_device(lin, d_luts, n_fn, self.N // n_fn, self._upload(idx.view(np.int32)))
+
+    @staticmethod
+    def _lazy_split(out: "LinBlocks", reqs) -> list:
+        """Per entry (its leading shape, its rows of the level's output)."""
+        res, off = [], 0
+        for a, _ in reqs:
+            cnt = a.bias.size
+            res.append((a.shape[:-1], out[off:off + cnt]))
+            off += cnt
+        return res
+
+    def _lazy_chunks(self, flat: "LinBlocks", idx: np.ndarray, step: int, run) -> "LinBlocks":
+        """run(term description, idx chunk) -> an output buffer, over chunks of ``step`` rows; the buffers wrapped
+        and joined."""
+        outs = []
+        for o in range(0, flat.shape[0], step):
+            desc = flat[o:o + step].terms()
+            self.max_terms = max(self.max_terms, int(np.diff(desc[1]).max(initial=0)))
+            outs.append(LinBlocks.wrap(run(desc, idx[o:o + step]), self._lincomb))
+        return outs[0] if len(outs) == 1 else np.concatenate(outs, axis=0)
 
     def lut(self, table: Tuple[int, ...]) -> np.ndarray:
         if table not in self._luts:
@@ -72,6 +163,8 @@ class RadixCircuit:
     # encodings
     def trivial(self, vals) -> np.ndarray:
         v = np.asarray(vals, dtype=np.uint64)
+        if self.lazy:
+            return LinBlocks.const((v % np.uint64(SPACE)) * np.uint64(DELTA), self.dim, self._lincomb)
         out = np.zeros(v.shape + (self.dim,), dtype=np.uint64)
         with np.errstate(over="ignore"):
             out[..., -1] = (v % np.uint64(SPACE)) * np.uint64(DELTA)
@@ -112,6 +205,11 @@ class RadixCircuit:
         flat = np.concatenate(flat_parts, axis=0)
         idx = np.concatenate(idx_parts)
         step = max(1, MAX_LAUNCH // n_fn)
+        if self.lazy:
+            out = self._lazy_chunks(flat, idx, step, lambda desc, i: self._lin_pbs_many(desc, groups, i, n_fn))
+            self.pbs_count += flat.shape[0]
+            return [tuple(part[:, f].reshape(s + (self.dim,)) for f in range(n_fn))
+                    for s, part in self._lazy_split(out, reqs)]
         outs = [self._pbs_many(flat[o:o + step], groups, idx[o:o + step], n_fn) for o in range(0, flat.shape[0], step)]
         out = outs[0] if len(outs) == 1 else np.concatenate(outs, axis=0)
         self.pbs_count += flat.shape[0]
@@ -149,6 +247,10 @@ class RadixCircuit:
             idx_parts.append(np.full(cnt, index[t], dtype=np.uint32))
         flat = np.concatenate(flat_parts, axis=0)
         idx = np.concatenate(idx_parts)
+        if self.lazy:
+            out = self._lazy_chunks(flat, idx, MAX_LAUNCH, lambda desc, i: self._lin_pbs(desc, tables, i))
+            self.pbs_count += flat.shape[0]
+            return [part.reshape(s + (self.dim,)) for s, part in self._lazy_split(out, reqs)]
         # one level = one launch; levels of wide operators (euint128 mul: ~10^5 PBS per operand pair) go in
         # chunks of MAX_LAUNCH ciphertexts so host and device staging stay bounded
         outs = [self._pbs(flat[o:o + MAX_LAUNCH], tables, idx[o:o + MAX_LAUNCH])
@@ -181,10 +283,11 @@ class RadixCircuit:
         seeds = np.ascontiguousarray(np.asarray(row_seeds, dtype=np.uint64)).reshape(-1, 2)
         rb = np.broadcast_to(np.asarray(random_bits, dtype=np.int64), (seeds.shape[0],))
         if seeds.shape[0] == 0:
-            return np.zeros((0, self.dim), dtype=np.uint64)
+            return self.trivial(np.zeros((0,), dtype=np.uint64))
         kinds = sorted({int(b) for b in rb})
         idx = np.searchsorted(np.array(kinds), rb).astype(np.uint32)
-        outs = [self._oprf(seeds[o:o + MAX_LAUNCH], kinds, idx[o:o + MAX_LAUNCH])
+        run = self._oprf_resident if self.lazy else self._oprf
+        outs = [run(seeds[o:o + MAX_LAUNCH], kinds, idx[o:o + MAX_LAUNCH])
                 for o in range(0, seeds.shape[0], MAX_LAUNCH)]
         self.pbs_count += seeds.shape[0]
         self.launches += 1
@@ -194,6 +297,17 @@ class RadixCircuit:
         """(cnt, 2) -> (cnt, dim): row q gets ``bit_kinds[idx[q]]`` random bits."""
         tabs = [self.oprf_lut(b) for b in bit_kinds]
         return self.engine.oprf(seeds, np.stack([t[0] for t in tabs]), [t[1] for t in tabs], idx)
+
+    def _oprf_resident(self, seeds, bit_kinds, idx) -> "LinBlocks":
+        """``_oprf`` of a resident circuit: the seeds go up (16 bytes a row), the blocks stay on the device."""
+        if self.device is None:
+            return self.wrap(np.ascontiguousarray(self._oprf(seeds, bit_kinds, idx), dtype=np.uint64))
+        tabs = [self.oprf_lut(b) for b in bit_kinds]
+        d_luts = self._d_luts(("oprf",) + tuple(bit_kinds), lambda: np.stack([t[0] for t in tabs]))
+        d_post = self._d_luts(("oprf post",) + tuple(bit_kinds),
+                              lambda: np.array([int(t[1]) % _M64 for t in tabs], dtype=np.uint64))
+        out = self.engine.oprf_device(self._upload(seeds.view(np.int64)), d_luts, d_post, self._upload(idx.view(np.int32)))
+        return self.wrap(out)
 
     def run(self, op):
         return self.run_many([op])[0]
@@ -228,7 +342,267 @@ class RadixCircuit:
 # --------------------------------------------------------------------------------------------
 # linear operations on block arrays (mod 2^64, any leading shape)
 # --------------------------------------------------------------------------------------------
+def lincomb_ref(bufs, row_start, term_buf, term_row, term_coef, bias, dim: int) -> np.ndarray:
+    """The numpy statement of the lincomb map (tfhe_amd/csrc/lincomb.hip; ``Engine.lincomb*`` take the same
+    arguments), all arithmetic mod 2^64:
+
+        out[r] = sum over t in row_start[r] .. row_start[r + 1] - 1 of term_coef[t] * bufs[term_buf[t]][term_row[t]]
+        out[r][dim - 1] += bias[r]            (bias may be None)
+
+    ``bufs``: arrays of (rows_b, dim) words; a row without terms is a trivial ciphertext.  -> (rows, dim) uint64."""
+    rs = np.asarray(row_start, dtype=np.int64)
+    rows = rs.shape[0] - 1
+    T = int(rs[-1]) if rows >= 0 else 0
+    out = np.zeros((max(rows, 0), dim), dtype=np.uint64)
+    if T:
+        tb = np.asarray(term_buf, dtype=np.int64)[:T]
+        tr = np.asarray(term_row, dtype=np.int64)[:T]
+        src = np.empty((T, dim), dtype=np.uint64)
+        for b in np.unique(tb):
+            sel = tb == b
+            src[sel] = np.asarray(bufs[b], dtype=np.uint64).reshape(-1, dim)[tr[sel]]
+        src *= np.asarray(term_coef, dtype=np.uint64)[:T, None]
+        counts = np.diff(rs)
+        for k in range(int(counts.max())):  # term k of every row that has one
+            sel = np.nonzero(counts > k)[0]
+            out[sel] += src[rs[sel] + k]
+    if bias is not None and rows > 0:
+        out[:, -1] += np.asarray(bias, dtype=np.uint64)
+    return out
+
+
+_BUF_IDS = __import__("itertools").count()
+
+
+class LinBlocks:
+    """A lazy block array of a resident ``RadixCircuit``: host-side metadata only.  Element e of the leading shape
+    stands for the ciphertext  sum over its terms of coef * (row ``row`` of buffer ``buf``)  + bias[e] on the body,
+    mod 2^64.  The terms of an element are slots along the last axis of ``buf`` / ``row`` / ``coef`` (``buf`` < 0:
+    empty slot); ``bufs`` maps the ids the array names to the buffers themselves (torch tensors on the device, or
+    numpy arrays), which keeps them alive.  ``shape`` is leading + (dim,), as of the eager array it replaces, and
+    the array supports what the circuits do to block arrays: basic and strided slicing and ``None`` on leading axes
+    (a full slice on the last), ``copy``, ``reshape`` of the leading axes, item assignment of another LinBlocks,
+    ``np.concatenate`` / ``np.stack`` / ``np.roll`` / ``np.broadcast_to`` along leading axes, and the linear
+    helpers ``_add`` / ``_scale`` / ``_sub`` / ``_not``.  None of these touches ciphertext words: ``materialize``
+    does, in one call of ``apply`` (``Engine.lincomb_device`` or ``lincomb_ref``)."""
+
+    def __init__(self, buf, row, coef, bias, bufs, dim, apply):
+        # bufs may name more buffers than the terms still use (a slice keeps its parent's): every bootstrap output
+        # starts from its one buffer again, so the surplus lives no longer than the linear work between two levels
+        self.buf, self.row, self.coef, self.bias, self.bufs, self.dim, self.apply = buf, row, coef, bias, bufs, int(dim), apply
+
+    @classmethod
+    def wrap(cls, buffer, apply) -> "LinBlocks":
+        """Every row of a (..., dim) buffer as one term of coefficient 1."""
+        if isinstance(buffer, LinBlocks) or buffer.ndim < 1:
+            raise TypeError("LinBlocks.wrap takes a (..., dim) buffer of ciphertext words")
+        lead, dim = tuple(buffer.shape[:-1]), int(buffer.shape[-1])
+        if isinstance(buffer, np.ndarray):
+            buffer = np.ascontiguousarray(buffer, dtype=np.uint64)
+        elif not buffer.is_contiguous():
+            buffer = buffer.contiguous()
+        i = next(_BUF_IDS)
+        n = int(np.prod(lead, dtype=np.int64))
+        return cls(np.full(lead + (1,), i, dtype=np.int64), np.arange(n, dtype=np.int64).reshape(lead + (1,)),
+                   np.ones(lead + (1,), dtype=np.uint64), np.zeros(lead, dtype=np.uint64), {i: buffer.reshape(n, dim)},
+                   dim, apply)
+
+    @classmethod
+    def const(cls, bodies, dim, apply) -> "LinBlocks":
+        """Trivial ciphertexts: no terms, body ``bodies``."""
+        b = np.array(bodies, dtype=np.uint64)
+        z = b.shape + (0,)
+        return cls(np.zeros(z, dtype=np.int64), np.zeros(z, dtype=np.int64), np.zeros(z, dtype=np.uint64), b, {}, dim, apply)
+
+    # ---- shape ------------------------------------------------------------------------------------------------
+    @property
+    def shape(self):
+        return self.bias.shape + (self.dim,)
+
+    @property
+    def ndim(self):
+        return self.bias.ndim + 1
+
+    def __len__(self):
+        return self.shape[0]
+
+    def _like(self, buf, row, coef, bias, bufs=None) -> "LinBlocks":
+        return LinBlocks(buf, row, coef, bias, self.bufs if bufs is None else bufs, self.dim, self.apply)
+
+    def _lead_key(self, key):
+        """An index of the block array -> the index of its leading axes (the last axis takes a full slice only)."""
+        key = key if isinstance(key, tuple) else (key,)
+        if any(k is Ellipsis for k in key):
+            i = next(j for j, k in enumerate(key) if k is Ellipsis)
+            fill = self.ndim - sum(k is not None and k is not Ellipsis for k in key)
+            key = key[:i] + (slice(None),) * fill + key[i + 1:]
+        if not all(k is None or isinstance(k, (int, np.integer, slice)) for k in key):
+            raise IndexError("LinBlocks: basic indexing only (integers, slices, None)")
+        if sum(k is not None for k in key) == self.ndim:
+            if key[-1] != slice(None):
+                raise IndexError("LinBlocks: the last axis (ciphertext words) takes a full slice only")
+            key = key[:-1]
+        return key
+
+    def __getitem__(self, key) -> "LinBlocks":
+        key = self._lead_key(key)
+        kk = key + (slice(None),)
+        return self._like(self.buf[kk], self.row[kk], self.coef[kk], self.bias[key])
+
+    def _slots(self, K: int):
+        """(buf, row, coef) padded with empty slots to K terms per element."""
+        pad = K - self.buf.shape[-1]
+        if pad == 0:
+            return self.buf, self.row, self.coef
+        tail = self.bias.shape + (pad,)
+        return (np.concatenate([self.buf, np.full(tail, -1, dtype=np.int64)], axis=-1),
+                np.concatenate([self.row, np.zeros(tail, dtype=np.int64)], axis=-1),
+                np.concatenate([self.coef, np.zeros(tail, dtype=np.uint64)], axis=-1))
+
+    def __setitem__(self, key, value: "LinBlocks") -> None:
+        if not isinstance(value, LinBlocks):
+            raise TypeError("LinBlocks: only another LinBlocks can be assigned")
+        key = self._lead_key(key)
+        K = max(self.buf.shape[-1], value.buf.shape[-1])
+        kk = key + (slice(None),)
+        mine, theirs = self._slots(K), value._slots(K)
+        for dst, src in zip(mine, theirs):
+            dst[kk] = src
+        self.bias[key] = value.bias
+        self.buf, self.row, self.coef = mine
+        self.bufs = {**self.bufs, **value.bufs}
+
+    def copy(self) -> "LinBlocks":
+        return self._like(self.buf.copy(), self.row.copy(), self.coef.copy(), self.bias.copy())
+
+    def reshape(self, *shape) -> "LinBlocks":
+        shape = tuple(shape[0]) if len(shape) == 1 and isinstance(shape[0], (tuple, list)) else tuple(shape)
+        if not shape or shape[-1] not in (-1, self.dim):
+            raise ValueError(f"LinBlocks.reshape: the last axis stays {self.dim} words")
+        bias = self.bias.reshape(shape[:-1])
+        K = (self.buf.shape[-1],)
+        return self._like(self.buf.reshape(bias.shape + K), self.row.reshape(bias.shape + K),
+                          self.coef.reshape(bias.shape + K), bias)
+
+    # ---- numpy functions along leading axes ---------------------------------------------------------------------
+    def _lead_axis(self, axis, ndim=None) -> int:
+        ndim = self.ndim if ndim is None else ndim
+        a = int(axis) % ndim
+        if a == ndim - 1:
+            raise ValueError("LinBlocks: the last axis (ciphertext words) cannot be moved or joined")
+        return a
+
+    @staticmethod
+    def _joined(fn, arrs, axis) -> "LinBlocks":
+        arrs = list(arrs)
+        if not arrs or not all(isinstance(a, LinBlocks) for a in arrs):
+            raise TypeError("LinBlocks joins with LinBlocks only")
+        K = max(a.buf.shape[-1] for a in arrs)
+        slots = [a._slots(K) for a in arrs]
+        bufs = {}
+        for a in arrs:
+            bufs.update(a.bufs)
+        return arrs[0]._like(*[fn([s[i] for s in slots], axis=axis) for i in range(3)],
+                             fn([a.bias for a in arrs], axis=axis), bufs)
+
+    def __array_function__(self, func, types, args, kwargs):
+        if func is np.concatenate:
+            arrs = args[0]
+            axis = args[1] if len(args) > 1 else kwargs.get("axis", 0)
+            return LinBlocks._joined(np.concatenate, arrs, arrs[0]._lead_axis(axis))
+        if func is np.stack:
+            arrs = args[0]
+            axis = args[1] if len(args) > 1 else kwargs.get("axis", 0)
+            return LinBlocks._joined(np.stack, arrs, arrs[0]._lead_axis(axis, arrs[0].ndim + 1))
+        if func is np.roll:
+            a, shift = args[0], args[1] if len(args) > 1 else kwargs["shift"]
+            axis = args[2] if len(args) > 2 else kwargs.get("axis")
+            if axis is None:
+                raise ValueError("LinBlocks: np.roll needs a leading axis")
+            ax = a._lead_axis(axis)
+            return a._like(np.roll(a.buf, shift, ax), np.roll(a.row, shift, ax), np.roll(a.coef, shift, ax),
+                           np.roll(a.bias, shift, ax))
+        if func is np.broadcast_to:
+            a, shape = args[0], tuple(args[1] if len(args) > 1 else kwargs["shape"])
+            if not shape or shape[-1] != a.dim:
+                raise ValueError(f"LinBlocks: broadcast keeps the last axis at {a.dim} words")
+            K = (a.buf.shape[-1],)
+            return a._like(np.broadcast_to(a.buf, shape[:-1] + K), np.broadcast_to(a.row, shape[:-1] + K),
+                           np.broadcast_to(a.coef, shape[:-1] + K), np.broadcast_to(a.bias, shape[:-1]))
+        return NotImplemented
+
+    # ---- linear maps -------------------------------------------------------------------------------------------
+    def scaled(self, k: int) -> "LinBlocks":
+        k = np.uint64(int(k) % _M64)
+        with np.errstate(over="ignore"):
+            return self._like(self.buf, self.row, self.coef * k, np.asarray(self.bias * k, dtype=np.uint64))
+
+    @staticmethod
+    def sum(xs) -> "LinBlocks":
+        """Elementwise sum (leading shapes broadcast): the operands' terms side by side, empty slots squeezed out."""
+        xs = list(xs)
+        lead = xs[0].bias.shape
+        if any(x.bias.shape != lead for x in xs):
+            lead = np.broadcast_shapes(*[x.bias.shape for x in xs])
+            xs = [x if x.bias.shape == lead else np.broadcast_to(x, lead + (x.dim,)) for x in xs]
+        buf, row, coef = [np.concatenate([getattr(x, f) for x in xs], axis=-1) for f in ("buf", "row", "coef")]
+        bias = np.zeros(lead, dtype=np.uint64)
+        bufs = {}
+        for x in xs:
+            with np.errstate(over="ignore"):
+                bias = np.asarray(bias + x.bias, dtype=np.uint64)
+            bufs.update(x.bufs)
+        valid = buf >= 0
+        if not valid.all():
+            order = np.argsort(~valid, axis=-1, kind="stable")
+            K = int(valid.sum(axis=-1).max(initial=0))
+            buf, row, coef = [np.take_along_axis(a, order, axis=-1)[..., :K] for a in (buf, row, coef)]
+        return xs[0]._like(buf, row, coef, bias, bufs)
+
+    # ---- ciphertext words ----------------------------------------------------------------------------------------
+    def terms(self):
+        """The term description of the flattened array, the arguments of ``lincomb_ref`` / ``Engine.lincomb*``:
+        (bufs, row_start, term_buf, term_row, term_coef, bias), one output row per element in C order."""
+        flat = (self.bias.size, self.buf.shape[-1])
+        buf = self.buf.reshape(flat)
+        valid = buf >= 0
+        row_start = np.zeros(flat[0] + 1, dtype=np.uint32)
+        row_start[1:] = np.cumsum(valid.sum(axis=1))
+        ids, term_buf = np.unique(buf[valid], return_inverse=True)
+        return ([self.bufs[int(i)] for i in ids], row_start, term_buf.astype(np.uint32).reshape(-1),
+                self.row.reshape(flat)[valid].astype(np.uint32), np.ascontiguousarray(self.coef.reshape(flat)[valid]),
+                np.ascontiguousarray(self.bias.reshape(-1)))
+
+    def materialize(self):
+        """The array's ciphertext words as one (leading..., dim) buffer where the buffers live: one ``apply`` call,
+        or no work at all for an untouched run of rows of one buffer."""
+        lead = self.bias.shape
+        bufs, row_start, term_buf, term_row, term_coef, bias = desc = self.terms()
+        n = row_start.shape[0] - 1
+        if (len(bufs) == 1 and term_row.shape[0] == n and self.buf.shape[-1] == 1 and n and not bias.any()
+                and np.all(term_coef == 1) and np.array_equal(term_row, term_row[0] + np.arange(n, dtype=np.uint32))):
+            return bufs[0][int(term_row[0]):int(term_row[0]) + n].reshape(lead + (self.dim,))
+        return self.apply(*desc, self.dim).reshape(lead + (self.dim,))
+
+    def to_host(self) -> np.ndarray:
+        """Materialised and downloaded: the eager uint64 array this one stands for."""
+        m = self.materialize()
+        if isinstance(m, np.ndarray):
+            return m
+        return m.cpu().numpy().view(np.uint64)
+
+    def __array__(self, dtype=None, copy=None):
+        h = self.to_host()
+        return h if dtype is None else h.astype(dtype, copy=False)
+
+
+def _host(blocks) -> np.ndarray:
+    return blocks.to_host() if isinstance(blocks, LinBlocks) else blocks
+
+
 def _add(*xs):
+    if isinstance(xs[0], LinBlocks):
+        return LinBlocks.sum(xs)
     with np.errstate(over="ignore"):
         out = xs[0].copy()
         for x in xs[1:]:
@@ -237,8 +611,17 @@ def _add(*xs):
 
 
 def _scale(x, k: int):
+    if isinstance(x, LinBlocks):
+        return x.scaled(k)
     with np.errstate(over="ignore"):
         return (x * np.uint64(k % _M64)).astype(np.uint64)
+
+
+def _sub(x, y):
+    if isinstance(x, LinBlocks):
+        return LinBlocks.sum([x, y.scaled(-1)])
+    with np.errstate(over="ignore"):
+        return (x - y).astype(np.uint64)
 
 
 def _const(c: "RadixCircuit", shape, v: int):
@@ -252,8 +635,7 @@ def _pack(x, y):
 
 def _not(c, a):
     """3 - a for clean blocks (bitwise NOT of the 2-bit message), no PBS."""
-    with np.errstate(over="ignore"):
-        return (_const(c, a.shape[:-1], MSG - 1) - a).astype(np.uint64)
+    return _sub(_const(c, a.shape[:-1], MSG - 1), a)
 
 
 class RadixUint:
@@ -283,15 +665,25 @@ class RadixUint:
     def encrypt(cls, c: RadixCircuit, ck, values, w: int, seed: Optional[int] = None, stream0: int = 0) -> "RadixUint":
         d = cls._digits(values, w)
         ct = ck.encrypt(d.reshape(-1), SPACE, seed, stream0).reshape(d.shape + (-1,))
-        return cls(c, ct)
+        return cls(c, c._ingest(ct))
 
     @classmethod
     def trivial(cls, c: RadixCircuit, values, w: int) -> "RadixUint":
         return cls(c, c.trivial(cls._digits(values, w)))
 
+    def tensor(self):
+        """The blocks as one (B, w/2, dim) buffer where the circuit keeps them: for a resident circuit the
+        materialised device tensor (int64, queued on torch's current stream, not synchronised; a numpy array for
+        device="cpu"), otherwise the host array itself."""
+        return self.blocks.materialize() if isinstance(self.blocks, LinBlocks) else self.blocks
+
+    def to_host(self) -> np.ndarray:
+        """The blocks as a host (B, w/2, dim) uint64 array (a resident circuit materialises and downloads)."""
+        return _host(self.blocks)
+
     def decrypt(self, ck) -> np.ndarray:
         B, nb = self.blocks.shape[:2]
-        d = ck.decrypt(self.blocks.reshape(B * nb, -1), SPACE).reshape(B, nb).astype(object)
+        d = ck.decrypt(self.to_host().reshape(B * nb, -1), SPACE).reshape(B, nb).astype(object)
         w = self.width
         vals = [sum(int(d[i, j]) << (2 * j) for j in range(nb)) % (1 << w) for i in range(B)]
         return np.array(vals, dtype=np.uint64 if w <= 64 else object)
@@ -706,8 +1098,7 @@ def fhevm_op(c: RadixCircuit, op: str, lhs, rhs=None):
         e = yield from g_eq(c, a, b)
         if op == "eq":
             return e
-        with np.errstate(over="ignore"):
-            return (_const(c, e.shape[:-1], 1) - e).astype(np.uint64)
+        return _sub(_const(c, e.shape[:-1], 1), e)
     if op in ("lt", "le", "gt", "ge"):
         return (yield from g_compare(c, op, a, b))
     return RadixUint(c, (yield from g_minmax(c, op, a, b)))
