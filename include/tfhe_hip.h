@@ -323,12 +323,18 @@ int tfhe_hip_pks_keygen_k(const tfhe_pks_params* pp, const tfhe_rng_key* rk, con
                           uint64_t* out_key, uint64_t* pksk /* nullable */);
 typedef struct tfhe_pks_ctx tfhe_pks_ctx;
 int tfhe_hip_pks_create(const tfhe_pks_params* pp, int device, tfhe_pks_ctx** out);
+/* Waits for every call still in flight on the ctx, on a caller's stream too, before it frees the ctx's buffers. */
 void tfhe_hip_pks_destroy(tfhe_pks_ctx* ctx);
+/* Waits for every call still in flight on the ctx before it rewrites the resident key. */
 int tfhe_hip_pks_load_key(tfhe_pks_ctx* ctx, const uint64_t* pksk, size_t len);
 /* count LWEs (count x (in_dim+1)) -> ceil(count / lwe_per_glwe) GLWEs ((k+1) x N each); GLWE g holds
  * LWEs g*lwe_per_glwe ... in coefficients 0, 1, ...  Host buffers, synchronous. */
 int tfhe_hip_pks_pack(tfhe_pks_ctx* ctx, const uint64_t* lwes, size_t count, uint64_t* glwes);
-/* Device buffers, enqueued on `stream` (NULL = the ctx stream, TFHE_HIP_NULL_STREAM = the null stream). */
+/* Device buffers, enqueued on `stream` (NULL = the ctx stream, TFHE_HIP_NULL_STREAM = the null stream).  The digit
+ * and T workspaces and the key are shared by every call on the ctx: calls on different streams, host calls included,
+ * are ordered on them by an event (a later call waits for the previous one's kernels on its own stream, and the host
+ * waits for them before it regrows a workspace), so a call may follow another at once, on any stream, without a
+ * synchronisation by the caller. */
 int tfhe_hip_pks_pack_async(tfhe_pks_ctx* ctx, const uint64_t* d_lwes, size_t count, uint64_t* d_glwes, void* stream);
 size_t tfhe_hip_pks_packed_words(const tfhe_pks_params* pp, uint32_t bodies);
 int tfhe_hip_pks_compress(const tfhe_pks_params* pp, const uint64_t* glwe, uint32_t bodies, uint64_t* packed);

@@ -6,7 +6,9 @@ pks_api.cpp), bit-exact against the oracle (or_pks_pack) with synthetic keys:
   many groups, and row counts across the 64-row VALU tile and the 256-row matrix-core tile;
 * both GEMMs against each other at the production shape;
 * the chunk loop of pack_device (a call whose T workspace exceeds PKS_T_BUDGET);
-* workspace regrowth on one context.
+* workspace regrowth on one context;
+* the call patterns that the header promises are ordered on a context's workspaces and key: calls on different
+  streams, a regrowth and a key load issued straight behind an async call.
 
 Key words and LWE words include the edges of the byte recoding and of the signed decomposition; the builders
 and their CPU-side checks (digit coverage, the two-chunk arithmetic) are also run without a GPU from
@@ -295,5 +297,107 @@ def test_workspace_regrowth(oracle_mod, name):
         for i, count in enumerate((5, 300, 5)):
             part = lwes[:count] if i < 2 else lwes[295:300]
             _assert_groups_equal_oracle(oracle_mod, pp, opp, key, part, packer.pack(part), None, f"{name} step {i}")
+    finally:
+        packer.close()
+
+
+# ---- 5. ordering across streams --------------------------------------------------------------------------
+# These pin the call patterns of the contract in include/tfhe_hip.h (tfhe_hip_pks_pack_async, tfhe_hip_pks_load_key).
+# They do not prove the ordering: launches this small may finish before the next call arrives.  The ordering itself
+# is the device slot's ws_begin / ws_end / ws_host_wait (host_common.h), shared with the other contexts.
+SENTINEL = 0x5E5E5E5E5E5E5E5E
+ORDER_CASES = ["mfma_k64_smallest", "valu_K48"]
+
+
+class _AsyncPack:
+    """Device input and a sentinel-filled output with two spare GLWEs for one pack_async call."""
+
+    def __init__(self, pp, lwes):
+        import torch
+        dev = torch.device("cuda", 0)
+        self.pp, self.lwes = pp, lwes
+        self.groups = -(-lwes.shape[0] // pp.lwe_per_glwe)
+        self.d_in = torch.from_numpy(np.ascontiguousarray(lwes).view(np.int64).copy()).to(dev)
+        self.d_out = torch.full((self.groups + 2, pp.glwe_len), SENTINEL, dtype=torch.int64, device=dev)
+
+    def issue(self, packer, stream):
+        packer.pack_async(self.d_in, self.lwes.shape[0], self.d_out, stream)
+
+    def check(self, oracle_mod, opp, key, tag):
+        out = self.d_out.cpu().numpy().view(np.uint64)
+        _assert_groups_equal_oracle(oracle_mod, self.pp, opp, key, self.lwes, out[:self.groups], None, tag)
+        assert (out[self.groups:] == SENTINEL).all(), tag
+        return out[:self.groups]
+
+
+@pytest.mark.parametrize("name", ORDER_CASES)
+def test_pack_stream_ordering(oracle_mod, name):
+    """An async pack of 257 LWEs on a side stream, then AT ONCE, without a synchronisation, a host pack of 65 others;
+    then the 257 and the 65 async on two side streams, back to back.  All four results equal the oracle."""
+    import torch
+    pp, opp, key, lwes = sweep_inputs(name)
+    X, Y = lwes[:257], synthetic_lwes(pp, 65, 556)
+    packer = _packer(pp, key)
+    try:
+        s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+        x1, x2, y2 = _AsyncPack(pp, X), _AsyncPack(pp, X), _AsyncPack(pp, Y)
+        torch.cuda.synchronize()                    # uploads and sentinel fills
+        x1.issue(packer, s1)
+        got_y = packer.pack(Y)
+        s1.synchronize()
+        _assert_groups_equal_oracle(oracle_mod, pp, opp, key, Y, got_y, None, f"{name}: host pack behind an async call")
+        x1.check(oracle_mod, opp, key, f"{name}: async pack with a host call behind it")
+        x2.issue(packer, s1)
+        y2.issue(packer, s2)
+        s1.synchronize()
+        s2.synchronize()
+        x2.check(oracle_mod, opp, key, f"{name}: async pack on s1")
+        y2.check(oracle_mod, opp, key, f"{name}: async pack on s2 behind s1")
+    finally:
+        packer.close()
+
+
+@pytest.mark.parametrize("name", ORDER_CASES)
+def test_regrow_behind_async_call(oracle_mod, name):
+    """A fresh context: 5 LWEs async on one stream, at once 300 async on another (the workspaces are freed and
+    reallocated behind the first call), then 5 on the first stream again.  All three equal the oracle."""
+    import torch
+    pp, opp, key, _ = sweep_inputs(name)
+    lwes = synthetic_lwes(pp, 300, 555)
+    packer = _packer(pp, key)
+    try:
+        s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+        calls = [(_AsyncPack(pp, lwes[:5]), s1), (_AsyncPack(pp, lwes), s2), (_AsyncPack(pp, lwes[295:300]), s1)]
+        torch.cuda.synchronize()
+        for call, st in calls:
+            call.issue(packer, st)
+        s1.synchronize()
+        s2.synchronize()
+        for i, (call, _) in enumerate(calls):
+            call.check(oracle_mod, opp, key, f"{name} step {i}")
+    finally:
+        packer.close()
+
+
+@pytest.mark.parametrize("name", ORDER_CASES)
+def test_load_key_behind_async_call(oracle_mod, name):
+    """An async pack of 257 LWEs under key A, at once load_key(B), then a host pack of the same LWEs: the async result
+    is the oracle's under A, the host result the oracle's under B, and the two differ."""
+    import torch
+    pp, opp, key_a, lwes = sweep_inputs(name)
+    key_b = synthetic_key(pp, 557)
+    X = lwes[:257]
+    packer = _packer(pp, key_a)
+    try:
+        s1 = torch.cuda.Stream()
+        xa = _AsyncPack(pp, X)
+        torch.cuda.synchronize()
+        xa.issue(packer, s1)
+        packer.load_key(key_b)
+        got_b = packer.pack(X)
+        s1.synchronize()
+        got_a = xa.check(oracle_mod, opp, key_a, f"{name}: async pack under key A")
+        _assert_groups_equal_oracle(oracle_mod, pp, opp, key_b, X, got_b, None, f"{name}: host pack under key B")
+        assert not np.array_equal(got_a, got_b)
     finally:
         packer.close()

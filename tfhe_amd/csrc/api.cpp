@@ -99,17 +99,15 @@ Rccl& rccl() {
 
 constexpr int TIMING_SLOTS = 4;
 
-// One device's slice of an engine.
-struct tfhe_shard {
-  int device = 0;
+// One device's slice of an engine: a device slot (host_common.h) plus keys, tables and workspaces.
+struct tfhe_shard : device_slot {
   int cus = 0;                  // compute units (queried once, shard_init)
-  hipStream_t stream = nullptr;
-  u64* d_bsk = nullptr;         // transform domain (NTT layout x N^-1, or Fourier)
+  u64* d_bsk = nullptr;        // transform domain (NTT layout x N^-1, or Fourier)
   u64* d_ksk = nullptr;         // standard KSK (VALU keyswitch; RCCL broadcast source / target)
   void* d_ks_planes = nullptr;  // KSK recoded into 8 signed byte planes (ks_mfma.hip)
   u64* d_tw = nullptr;          // twiddle tables of the device transform
   u64* d_ms_zeros = nullptr;    // modulus-switch noise reduction zeros (order 1)
-  // workspaces: every user waits for `ws_free` (the previous user's completion) on its own stream
+  // workspaces, ordered across streams by the slot's ws_begin / ws_end
   u64* d_big = nullptr;
   size_t big_cap = 0;  // bytes
   u64* d_acc = nullptr;  // blind-rotation accumulators of a many-LUT PBS
@@ -129,13 +127,8 @@ struct tfhe_shard {
   hipEvent_t lin_meta_done[2] = {nullptr, nullptr};
   bool lin_meta_used[2] = {false, false};
   int lin_meta_next = 0;
-  void* d_stage = nullptr;
-  size_t stage_cap = 0;  // bytes
   void* d_ks_dig = nullptr;
   size_t ks_dig_cap = 0;  // bytes
-  hipEvent_t ws_free = nullptr;
-  hipStream_t ws_last = nullptr;
-  bool ws_used = false;
   // timing: start/stop event pairs per slot (0 = blind rotate, 1 = keyswitch, 2 = MS noise reduction,
   // 3 = the ingest stage of a call: unpack / extract of a decompression, the expansion of a compact list, or the
   // seeded masks of tfhe_hip_oprf)
@@ -162,25 +155,6 @@ struct tfhe_ctx {
 namespace {
 
 using shard = tfhe_shard;
-
-int grow(shard& s, void** ptr, size_t* cap, size_t bytes) {
-  if (*cap >= bytes) return 0;
-  if (s.ws_used) HIP_TRY(hipEventSynchronize(s.ws_free));  // no launch may still read the old buffer
-  return grow_device_buffer(ptr, cap, bytes);
-}
-
-// Workspace ordering across streams (tfhe_hip_pbs_async may be called on any stream): the stream that
-// uses the shard's workspaces next waits for the event recorded after the previous use.
-int ws_begin(shard& s, hipStream_t st) {
-  if (s.ws_used && s.ws_last != st) HIP_TRY(hipStreamWaitEvent(st, s.ws_free, 0));
-  return 0;
-}
-int ws_end(shard& s, hipStream_t st) {
-  HIP_TRY(hipEventRecord(s.ws_free, st));
-  s.ws_last = st;
-  s.ws_used = true;
-  return 0;
-}
 
 hipEvent_t take_event(shard& s) {
   if (!s.ev_pool.empty()) {
@@ -243,7 +217,7 @@ int launch_ks(tfhe_ctx* c, shard& s, const u64* in_big, size_t B, u64* out, hipS
                                    (int)c->p.ks_level, out, st));
     return 0;
   }
-  RC_TRY(grow(s, &s.d_ks_dig, &s.ks_dig_cap, tfhe::ks_digits_bytes(B, big_dim, (int)c->p.ks_level)));
+  RC_TRY(ws_grow(s, &s.d_ks_dig, &s.ks_dig_cap, tfhe::ks_digits_bytes(B, big_dim, (int)c->p.ks_level)));
   HIP_TRY(tfhe::launch_keyswitch_mfma(in_big, B, big_dim, s.d_ks_planes, (int)c->p.n, (int)c->p.ks_base_log,
                                       (int)c->p.ks_level, s.d_ks_dig, out, st));
   return 0;
@@ -280,8 +254,8 @@ int pbs_device(tfhe_ctx* c, shard& s, const u64* d_in, size_t B, const u64* d_lu
                const many_args* m, u64* d_out, hipStream_t st) {
   const size_t big = (size_t)c->p.k * c->p.N + 1, small = (size_t)c->p.n + 1;
   const size_t rows = B * (m ? m->n_fn : 1);
-  RC_TRY(grow(s, (void**)&s.d_big, &s.big_cap, (c->p.order == 0 ? rows * big : B * small) * sizeof(u64)));
-  if (m) RC_TRY(grow(s, (void**)&s.d_acc, &s.acc_cap, B * (size_t)(c->p.k + 1) * c->p.N * sizeof(u64)));
+  RC_TRY(ws_grow(s, (void**)&s.d_big, &s.big_cap, (c->p.order == 0 ? rows * big : B * small) * sizeof(u64)));
+  if (m) RC_TRY(ws_grow(s, (void**)&s.d_acc, &s.acc_cap, B * (size_t)(c->p.k + 1) * c->p.N * sizeof(u64)));
   auto rotate = [&](const u64* in, u64* out) -> int {  // blind rotation + sample extraction, slot 0
     timed_begin(c, s, 0, st);
     if (m) {
@@ -323,53 +297,8 @@ int check_many(const tfhe_ctx* c, const char* what, size_t B, uint32_t n_fn, uin
   return 0;
 }
 
-using staged_in = std::initializer_list<std::pair<const void*, size_t>>;  // (host pointer or null, bytes)
-
-// Stage host buffers into the shard's staging allocation (on the shard stream).  Returns device pointers
-// in order, plus one for `extra_out_bytes` of output.
-int stage(shard& s, staged_in in, std::vector<void*>& dptr, size_t extra_out_bytes) {
-  size_t total = 0;
-  std::vector<size_t> off;
-  for (auto& x : in) {
-    off.push_back(total);
-    total += (x.second + 255) & ~(size_t)255;
-  }
-  const size_t out_off = total;
-  total += (extra_out_bytes + 255) & ~(size_t)255;
-  RC_TRY(grow(s, &s.d_stage, &s.stage_cap, total ? total : 256));
-  size_t i = 0;
-  dptr.clear();
-  for (auto& x : in) {
-    void* d = (char*)s.d_stage + off[i++];
-    if (x.first && x.second) HIP_TRY(hipMemcpyAsync(d, x.first, x.second, hipMemcpyHostToDevice, s.stream));
-    dptr.push_back(x.first ? d : nullptr);
-  }
-  dptr.push_back((char*)s.d_stage + out_off);
-  return 0;
-}
-
-struct copy_back {  // after the launch: host dst (skipped when null) <- staged pointer d[src], bytes
-  void* dst;
-  size_t src, bytes;
-};
-
-// One host-buffer call on a shard's own stream (caller holds c->mu and has set the shard's device): order the
-// workspaces after their previous user, stage `in` plus out_bytes of output, launch(s, d) on the staged pointers,
-// copy `back` to the host, mark the workspaces used and wait.
-template <class F>
-int staged_run(shard& s, staged_in in, size_t out_bytes, std::initializer_list<copy_back> back, F&& launch) {
-  RC_TRY(ws_begin(s, s.stream));
-  std::vector<void*> d;
-  RC_TRY(stage(s, in, d, out_bytes));
-  RC_TRY(launch(s, d));
-  for (auto& b : back)
-    if (b.dst) HIP_TRY(hipMemcpyAsync(b.dst, d[b.src], b.bytes, hipMemcpyDeviceToHost, s.stream));
-  RC_TRY(ws_end(s, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  return 0;
-}
-
-// The single-shard host entry points: staged_run on shard 0 under the engine lock.
+// The single-shard host entry points: staged_run (host_common.h) on shard 0 under the engine lock.  The *_async
+// entry points share async_call below.
 template <class F>
 int staged_call(tfhe_ctx* c, staged_in in, size_t out_bytes, std::initializer_list<copy_back> back, F&& launch) {
   std::lock_guard<std::mutex> lk(c->mu);
@@ -532,8 +461,7 @@ int convert_keys(tfhe_ctx* c, shard& s, const u64* std_bsk, size_t bsk_len, bool
 
 int shard_init(tfhe_ctx* c, shard& s) {
   DeviceGuard g(s.device);
-  HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreateWithFlags(&s.ws_free, hipEventDisableTiming));
+  RC_TRY(slot_streams(s));
   HIP_TRY(hipDeviceGetAttribute(&s.cus, hipDeviceAttributeMultiprocessorCount, s.device));
   std::vector<u64> tw(c->eng->table_words);  // the back end's twiddle / twist tables
   if (!c->eng->make_tables(tw.data()))
@@ -545,29 +473,15 @@ int shard_init(tfhe_ctx* c, shard& s) {
 
 void shard_free(shard& s) {
   DeviceGuard g(s.device);
-  if (s.stream) (void)hipStreamSynchronize(s.stream);
+  slot_close(s, {s.d_bsk, s.d_ksk, s.d_ks_planes, s.d_ks_dig, s.d_tw, s.d_ms_zeros, s.d_big, s.d_acc, s.d_expand, s.d_oprf,
+                 s.d_lin, s.d_lin_meta});
   for (int w = 0; w < TIMING_SLOTS; w++)
     for (auto e : s.ev[w]) (void)hipEventDestroy(e);
   for (auto e : s.ev_pool) (void)hipEventDestroy(e);
-  (void)hipFree(s.d_bsk);
-  (void)hipFree(s.d_ksk);
-  (void)hipFree(s.d_ks_planes);
-  (void)hipFree(s.d_ks_dig);
-  (void)hipFree(s.d_tw);
-  (void)hipFree(s.d_ms_zeros);
-  (void)hipFree(s.d_big);
-  (void)hipFree(s.d_acc);
-  (void)hipFree(s.d_expand);
-  (void)hipFree(s.d_oprf);
-  (void)hipFree(s.d_lin);
-  (void)hipFree(s.d_lin_meta);
   for (int i = 0; i < 2; i++) {
     if (s.h_lin_meta[i]) (void)hipHostFree(s.h_lin_meta[i]);
     if (s.lin_meta_done[i]) (void)hipEventDestroy(s.lin_meta_done[i]);
   }
-  (void)hipFree(s.d_stage);
-  if (s.ws_free) (void)hipEventDestroy(s.ws_free);
-  if (s.stream) (void)hipStreamDestroy(s.stream);
 }
 
 // Run fn(shard index, lo, hi) for contiguous slices of [0, B) on every shard concurrently (one host
@@ -628,6 +542,23 @@ int shard_of_input(tfhe_ctx* c, const char* what, const void* d_in, size_t* si) 
   return fail(TFHE_HIP_EINVAL, "%s_async: input on device %d, no shard there", what, a.device);
 }
 
+// The *_async entry points (device buffers, checked by the caller): under the engine lock, work(s, st) on the shard
+// whose device holds `d_anchor` and on the caller's stream.  uses_ws: the work touches the shard's workspaces or
+// keys, so it is ordered after their previous user and recorded as the latest; without it no event is taken.
+template <class F>
+int async_call(tfhe_ctx* c, const char* what, const void* d_anchor, void* stream, bool uses_ws, F&& work) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  size_t si = 0;
+  RC_TRY(shard_of_input(c, what, d_anchor, &si));
+  shard& s = c->sh[si];
+  DeviceGuard g(s.device);
+  hipStream_t st = resolve_stream(stream, s.stream);
+  if (!uses_ws) return work(s, st);
+  RC_TRY(ws_begin(s, st));
+  RC_TRY(work(s, st));
+  return ws_end(s, st);
+}
+
 int host_lut_index_check(const char* what, const u32* lut_index, size_t B, size_t n_lut) {
   if (lut_index)
     for (size_t q = 0; q < B; q++)
@@ -649,15 +580,9 @@ int pbs_async_call(tfhe_ctx* c, const char* what, const u64* d_in, size_t B, con
                    const u32* d_idx, const pbs_kind& kd, u64* d_out, void* stream) {
   RC_TRY(pbs_check(c, what, d_in, B, d_luts, n_lut, kd, d_out));
   if (B == 0) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  size_t si = 0;
-  RC_TRY(shard_of_input(c, what, d_in, &si));
-  shard& s = c->sh[si];
-  DeviceGuard g(s.device);
-  hipStream_t st = resolve_stream(stream, s.stream);
-  RC_TRY(ws_begin(s, st));
-  RC_TRY(pbs_kind_device(c, s, d_in, B, d_luts, n_lut, d_idx, kd, d_out, st));
-  return ws_end(s, st);
+  return async_call(c, what, d_in, stream, true, [&](shard& s, hipStream_t st) {
+    return pbs_kind_device(c, s, d_in, B, d_luts, n_lut, d_idx, kd, d_out, st);
+  });
 }
 
 // tfhe_hip_pbs / tfhe_hip_pbs_many / tfhe_hip_bootstrap: host buffers, sliced over the shards
@@ -701,7 +626,7 @@ int decompress_check(const tfhe_ctx* c, const tfhe_pks_params* pp, const void* p
 // (slot 3), then the rotation (slot 0).
 int decompress_device(tfhe_ctx* c, shard& s, const tfhe_pks_params& pp, const u64* d_packed, size_t count,
                       const u64* d_luts, size_t n_lut, const u32* d_idx, u64* d_out, hipStream_t st) {
-  RC_TRY(grow(s, (void**)&s.d_big, &s.big_cap, count * ((size_t)c->p.n + 1) * sizeof(u64)));
+  RC_TRY(ws_grow(s, (void**)&s.d_big, &s.big_cap, count * ((size_t)c->p.n + 1) * sizeof(u64)));
   timed_begin(c, s, 3, st);
   HIP_TRY(tfhe::launch_unpack_extract(d_packed, count, (int)pp.out_k, (int)pp.out_N, (int)pp.lwe_per_glwe,
                                       (int)pp.storage_log, s.d_big, st));
@@ -771,7 +696,7 @@ int expand_device(tfhe_ctx* c, shard& s, const u64* d_list, size_t count, uint32
 int expand_cast_device(tfhe_ctx* c, shard& s, const u64* d_list, size_t count, uint32_t rep, size_t rows,
                        const u64* d_luts, size_t n_lut, const u32* d_idx, u64* d_out, hipStream_t st) {
   const uint32_t dim = io_dim(c->p);
-  RC_TRY(grow(s, (void**)&s.d_expand, &s.expand_cap, rows * ((size_t)dim + 1) * sizeof(u64)));
+  RC_TRY(ws_grow(s, (void**)&s.d_expand, &s.expand_cap, rows * ((size_t)dim + 1) * sizeof(u64)));
   RC_TRY(expand_device(c, s, d_list, count, dim, rep, rows, s.d_expand, st));
   return pbs_device(c, s, s.d_expand, rows, d_luts, n_lut, d_idx, nullptr, d_out, st);
 }
@@ -803,7 +728,7 @@ int csprng_device(tfhe_ctx* c, shard& s, const u64* d_seeds, size_t rows, u64 fi
 int oprf_device(tfhe_ctx* c, shard& s, const u64* d_seeds, size_t rows, const u64* d_luts, const u64* d_post,
                 size_t n_lut, const u32* d_idx, u64* d_out, hipStream_t st) {
   const size_t small = (size_t)c->p.n + 1;
-  RC_TRY(grow(s, (void**)&s.d_oprf, &s.oprf_cap, rows * small * sizeof(u64)));
+  RC_TRY(ws_grow(s, (void**)&s.d_oprf, &s.oprf_cap, rows * small * sizeof(u64)));
   RC_TRY(csprng_device(c, s, d_seeds, rows, 0, c->p.n, small, true, s.d_oprf, st));
   if (c->p.order == 1) RC_TRY(bootstrap_device(c, s, s.d_oprf, rows, d_luts, n_lut, d_idx, d_out, st));
   else RC_TRY(pbs_device(c, s, s.d_oprf, rows, d_luts, n_lut, d_idx, nullptr, d_out, st));
@@ -870,7 +795,7 @@ int lincomb_stage(shard& s, uint32_t dim, const uint64_t* const* d_bufs, const l
   const size_t rs_off = T * sizeof(tfhe::lin_term);
   const size_t bias_off = (rs_off + (rows + 1) * sizeof(u32) + 15) & ~(size_t)15;
   const size_t total = bias_off + (L.bias ? rows * sizeof(u64) : 0);
-  RC_TRY(grow(s, &s.d_lin_meta, &s.lin_meta_cap, total));
+  RC_TRY(ws_grow(s, &s.d_lin_meta, &s.lin_meta_cap, total));
   const int k = s.lin_meta_next;
   s.lin_meta_next ^= 1;
   if (!s.lin_meta_done[k]) HIP_TRY(hipEventCreateWithFlags(&s.lin_meta_done[k], hipEventDisableTiming));
@@ -1095,11 +1020,7 @@ int tfhe_hip_create(const tfhe_params* p, const int* devices, int ndev, tfhe_ctx
                 "k=%u N=%u pbs %ux%u ks %ux%u order %u transform %u",
                 p->k, p->N, p->pbs_base_log, p->pbs_level, p->ks_base_log, p->ks_level, p->order, p->transform);
   if (!devices || ndev < 1 || ndev > 64) return fail(TFHE_HIP_EINVAL, "create: need 1..64 device ordinals, got %d", ndev);
-  int count = 0;
-  HIP_TRY(hipGetDeviceCount(&count));
-  for (int i = 0; i < ndev; i++)
-    if (devices[i] < 0 || devices[i] >= count)
-      return fail(TFHE_HIP_EINVAL, "create: device %d of %d (devices[%d])", devices[i], count, i);
+  for (int i = 0; i < ndev; i++) RC_TRY(device_ordinal_check("create", devices[i], i));
   std::unique_ptr<tfhe_ctx> c(new tfhe_ctx());
   c->p = *p;
   c->eng = tfhe::find_engine(p->transform == TFHE_HIP_TRANSFORM_FFT64, p->N);
@@ -1165,10 +1086,10 @@ static int load_keys_impl(tfhe_ctx* c, const char* what, const uint64_t* bsk, si
   // every shard: key buffers + a standard-domain BSK staging area (its d_stage)
   for (auto& s : c->sh) {
     DeviceGuard g(s.device);
-    if (s.ws_used) HIP_TRY(hipEventSynchronize(s.ws_free));
+    RC_TRY(ws_host_wait(s));
     if (!s.d_bsk) HIP_TRY(hipMalloc(&s.d_bsk, bsk_len * 8));
     if (with_ksk && !s.d_ksk) HIP_TRY(hipMalloc(&s.d_ksk, ksk_len * 8));
-    RC_TRY(grow(s, &s.d_stage, &s.stage_cap, bsk_len * 8));
+    RC_TRY(ws_grow(s, &s.d_stage, &s.stage_cap, bsk_len * 8));
   }
   shard& s0 = c->sh[0];
   const u64* bsk0 = (const u64*)bsk;  // standard BSK on shard 0's device
@@ -1245,7 +1166,7 @@ int tfhe_hip_load_ms_key(tfhe_ctx* c, const uint64_t* zeros, uint32_t count, dou
   for (auto& s : c->sh) {
     DeviceGuard g(s.device);
     HIP_TRY(hipStreamSynchronize(s.stream));
-    if (s.ws_used) HIP_TRY(hipEventSynchronize(s.ws_free));
+    RC_TRY(ws_host_wait(s));
     (void)hipFree(s.d_ms_zeros);
     s.d_ms_zeros = nullptr;
     if (!count) continue;
@@ -1310,15 +1231,9 @@ int tfhe_hip_decompress_async(tfhe_ctx* c, const tfhe_pks_params* pp, const uint
                               uint64_t* d_out, void* stream) {
   RC_TRY(decompress_check(c, pp, d_packed, packed_words, count, d_luts, n_lut, d_out));
   if (count == 0) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  size_t si = 0;
-  RC_TRY(shard_of_input(c, "decompress", d_packed, &si));
-  shard& s = c->sh[si];
-  DeviceGuard g(s.device);
-  hipStream_t st = resolve_stream(stream, s.stream);
-  RC_TRY(ws_begin(s, st));
-  RC_TRY(decompress_device(c, s, *pp, d_packed, count, d_luts, n_lut, d_idx, d_out, st));
-  return ws_end(s, st);
+  return async_call(c, "decompress", d_packed, stream, true, [&](shard& s, hipStream_t st) {
+    return decompress_device(c, s, *pp, d_packed, count, d_luts, n_lut, d_idx, d_out, st);
+  });
 }
 
 int tfhe_hip_decompress(tfhe_ctx* c, const tfhe_pks_params* pp, const uint64_t* packed, size_t packed_words,
@@ -1344,12 +1259,9 @@ int tfhe_hip_expand_compact_async(tfhe_ctx* c, const uint64_t* d_list, size_t li
                                   uint32_t rep, size_t rows, uint64_t* d_lwes_out, void* stream) {
   RC_TRY(expand_check(c, d_list, list_words, lwe_dim, count, rep, rows, d_lwes_out));
   if (rows == 0) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  size_t si = 0;
-  RC_TRY(shard_of_input(c, "expand_compact", d_list, &si));
-  shard& s = c->sh[si];
-  DeviceGuard g(s.device);
-  return expand_device(c, s, d_list, count, lwe_dim, rep, rows, d_lwes_out, resolve_stream(stream, s.stream));
+  return async_call(c, "expand_compact", d_list, stream, false, [&](shard& s, hipStream_t st) {  // no workspace
+    return expand_device(c, s, d_list, count, lwe_dim, rep, rows, d_lwes_out, st);
+  });
 }
 
 int tfhe_hip_expand_compact(tfhe_ctx* c, const uint64_t* list, size_t list_words, uint32_t lwe_dim, size_t count,
@@ -1368,15 +1280,9 @@ int tfhe_hip_expand_cast_async(tfhe_ctx* c, const uint64_t* d_list, size_t list_
                                uint64_t* d_out, void* stream) {
   RC_TRY(expand_cast_check(c, d_list, list_words, count, rep, rows, d_luts, n_lut, d_out));
   if (rows == 0) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  size_t si = 0;
-  RC_TRY(shard_of_input(c, "expand_cast", d_list, &si));
-  shard& s = c->sh[si];
-  DeviceGuard g(s.device);
-  hipStream_t st = resolve_stream(stream, s.stream);
-  RC_TRY(ws_begin(s, st));
-  RC_TRY(expand_cast_device(c, s, d_list, count, rep, rows, d_luts, n_lut, d_idx, d_out, st));
-  return ws_end(s, st);
+  return async_call(c, "expand_cast", d_list, stream, true, [&](shard& s, hipStream_t st) {
+    return expand_cast_device(c, s, d_list, count, rep, rows, d_luts, n_lut, d_idx, d_out, st);
+  });
 }
 
 int tfhe_hip_expand_cast(tfhe_ctx* c, const uint64_t* list, size_t list_words, size_t count, uint32_t rep, size_t rows,
@@ -1423,12 +1329,9 @@ int tfhe_hip_csprng_rows_async(tfhe_ctx* c, const uint64_t* d_seeds, size_t rows
                                size_t row_stride, uint64_t* d_out, void* stream) {
   RC_TRY(csprng_check(c, d_seeds, rows, first_word, dim, row_stride, d_out));
   if (rows == 0) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  size_t si = 0;
-  RC_TRY(shard_of_input(c, "csprng_rows", d_seeds, &si));
-  shard& s = c->sh[si];
-  DeviceGuard g(s.device);
-  return csprng_device(c, s, d_seeds, rows, first_word, dim, row_stride, false, d_out, resolve_stream(stream, s.stream));
+  return async_call(c, "csprng_rows", d_seeds, stream, false, [&](shard& s, hipStream_t st) {  // no workspace
+    return csprng_device(c, s, d_seeds, rows, first_word, dim, row_stride, false, d_out, st);
+  });
 }
 
 int tfhe_hip_csprng_rows(tfhe_ctx* c, const uint64_t* seeds, size_t rows, uint64_t first_word, uint32_t dim,
@@ -1446,15 +1349,9 @@ int tfhe_hip_oprf_async(tfhe_ctx* c, const uint64_t* d_seeds, size_t rows, const
                         void* stream) {
   RC_TRY(oprf_check(c, d_seeds, rows, d_luts, d_post_adds, n_lut, d_out));
   if (rows == 0) return 0;
-  std::lock_guard<std::mutex> lk(c->mu);
-  size_t si = 0;
-  RC_TRY(shard_of_input(c, "oprf", d_seeds, &si));
-  shard& s = c->sh[si];
-  DeviceGuard g(s.device);
-  hipStream_t st = resolve_stream(stream, s.stream);
-  RC_TRY(ws_begin(s, st));
-  RC_TRY(oprf_device(c, s, d_seeds, rows, d_luts, d_post_adds, n_lut, d_idx, d_out, st));
-  return ws_end(s, st);
+  return async_call(c, "oprf", d_seeds, stream, true, [&](shard& s, hipStream_t st) {
+    return oprf_device(c, s, d_seeds, rows, d_luts, d_post_adds, n_lut, d_idx, d_out, st);
+  });
 }
 
 int tfhe_hip_oprf(tfhe_ctx* c, const uint64_t* seeds, size_t rows, const uint64_t* luts, const uint64_t* post_adds,
@@ -1487,15 +1384,9 @@ int tfhe_hip_lwe_lincomb_async(tfhe_ctx* c, uint32_t dim, const uint64_t* const*
   if (rows == 0) return 0;
   if (!d_out || (row_start[rows] && !term_buf)) return fail(TFHE_HIP_EINVAL, "lwe_lincomb: null buffer");
   RC_TRY(lincomb_ptr_check("lwe_lincomb", dim, d_bufs, buf_rows, n_buf, rows, d_out));
-  std::lock_guard<std::mutex> lk(c->mu);
-  size_t si = 0;
-  RC_TRY(shard_of_input(c, "lwe_lincomb", d_out, &si));
-  shard& s = c->sh[si];
-  DeviceGuard g(s.device);
-  hipStream_t st = resolve_stream(stream, s.stream);
-  RC_TRY(ws_begin(s, st));
-  RC_TRY(lincomb_device(c, s, dim, d_bufs, L, rows, d_out, st));
-  return ws_end(s, st);
+  return async_call(c, "lwe_lincomb", d_out, stream, true, [&](shard& s, hipStream_t st) {
+    return lincomb_device(c, s, dim, d_bufs, L, rows, d_out, st);
+  });
 }
 
 int tfhe_hip_lwe_lincomb(tfhe_ctx* c, uint32_t dim, const uint64_t* src, size_t src_rows, const uint32_t* row_start,
@@ -1525,17 +1416,11 @@ int tfhe_hip_lincomb_pbs_async(tfhe_ctx* c, const uint64_t* const* d_bufs, const
   if (rows == 0) return 0;
   if (row_start[rows] && !term_buf) return fail(TFHE_HIP_EINVAL, "lincomb_pbs: null buffer");
   RC_TRY(lincomb_ptr_check("lincomb_pbs", dim, d_bufs, buf_rows, n_buf, rows, nullptr));
-  std::lock_guard<std::mutex> lk(c->mu);
-  size_t si = 0;
-  RC_TRY(shard_of_input(c, "lincomb_pbs", d_out, &si));
-  shard& s = c->sh[si];
-  DeviceGuard g(s.device);
-  hipStream_t st = resolve_stream(stream, s.stream);
-  RC_TRY(ws_begin(s, st));
-  RC_TRY(grow(s, (void**)&s.d_lin, &s.lin_cap, rows * (size_t)dim * sizeof(u64)));
-  RC_TRY(lincomb_device(c, s, dim, d_bufs, L, rows, s.d_lin, st));
-  RC_TRY(pbs_device(c, s, s.d_lin, rows, d_luts, n_lut, d_idx, nullptr, d_out, st));
-  return ws_end(s, st);
+  return async_call(c, "lincomb_pbs", d_out, stream, true, [&](shard& s, hipStream_t st) -> int {
+    RC_TRY(ws_grow(s, (void**)&s.d_lin, &s.lin_cap, rows * (size_t)dim * sizeof(u64)));
+    RC_TRY(lincomb_device(c, s, dim, d_bufs, L, rows, s.d_lin, st));
+    return pbs_device(c, s, s.d_lin, rows, d_luts, n_lut, d_idx, nullptr, d_out, st);
+  });
 }
 
 int tfhe_hip_blind_rotate(tfhe_ctx* c, const uint64_t* lwe_in, size_t B, const uint64_t* luts, size_t n_lut,
@@ -1660,7 +1545,7 @@ int tfhe_hip_sync(tfhe_ctx* c) {
   for (auto& s : c->sh) {
     DeviceGuard g(s.device);
     HIP_TRY(hipStreamSynchronize(s.stream));
-    if (s.ws_used) HIP_TRY(hipEventSynchronize(s.ws_free));
+    RC_TRY(ws_host_wait(s));
   }
   return 0;
 }

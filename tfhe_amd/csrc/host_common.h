@@ -1,10 +1,15 @@
 // host_common.h — plumbing shared by the C ABI translation units (api.cpp, pks_api.cpp, sns_api.cpp, sns_pks_api.cpp):
-// error reporting, HIP call checking, the device guard, stream resolution, buffer growth.  Host code only.
+// error reporting, HIP call checking, the device guard, stream resolution, buffer growth, and the device slot:
+// the stream, the cross-stream workspace ordering and the host-call staging of every device context.  Host code only.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+
+#include <initializer_list>
+#include <utility>
+#include <vector>
 
 #include "../../include/tfhe_hip.h"
 
@@ -14,6 +19,20 @@ int tfhe_hip_set_error(int code, const char* msg);
 // invalid parameters, count > 0x7FFFFFFF or packed_words != the words of ceil(count / lwe_per_glwe) groups,
 // EUNSUPPORTED for out_N above the unpack kernel's 4096.  `what` prefixes the message.
 int tfhe_hip_pks_list_check(const tfhe_pks_params* pp, size_t packed_words, size_t count, const char* what);
+
+// What every device context (an engine shard, tfhe_pks_ctx, tfhe_sns_ctx, tfhe_sns_pks_ctx) derives from: one device
+// ordinal, its own stream, the ordering state of the workspaces that all its calls share, and the staging buffer of
+// its host-buffer calls.
+struct device_slot {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  // workspaces and resident keys: every user waits for `ws_free` (the previous user's completion) on its own stream
+  hipEvent_t ws_free = nullptr;
+  hipStream_t ws_last = nullptr;
+  bool ws_used = false;
+  void* d_stage = nullptr;
+  size_t stage_cap = 0;  // bytes
+};
 
 namespace {
 
@@ -66,6 +85,114 @@ int grow_device_buffer(void** p, size_t* cap, size_t bytes) {
   *cap = 0;
   HIP_TRY(hipMalloc(p, bytes));
   *cap = bytes;
+  return 0;
+}
+
+// EINVAL unless `device` is an ordinal of this process (`list_index` >= 0: the entry of the caller's list it came from)
+int device_ordinal_check(const char* what, int device, int list_index = -1) {
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device >= 0 && device < ndev) return 0;
+  if (list_index < 0) return fail(TFHE_HIP_EINVAL, "%s: device %d of %d", what, device, ndev);
+  return fail(TFHE_HIP_EINVAL, "%s: device %d of %d (devices[%d])", what, device, ndev, list_index);
+}
+
+// the slot's non-blocking stream and its ordering event (s.device is set and current)
+int slot_streams(device_slot& s) {
+  HIP_TRY(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+  HIP_TRY(hipEventCreateWithFlags(&s.ws_free, hipEventDisableTiming));
+  return 0;
+}
+
+// Open a side context's slot: the ordinal check under the caller's `what`, then stream and event (EDEVICE,
+// "<what>: <setup_failed>").  After a failure slot_close still applies.
+int slot_open(device_slot& s, int device, const char* what, const char* setup_failed) {
+  RC_TRY(device_ordinal_check(what, device));
+  s.device = device;
+  DeviceGuard g(device);
+  if (slot_streams(s)) return fail(TFHE_HIP_EDEVICE, "%s: %s", what, setup_failed);
+  return 0;
+}
+
+// Close a slot, half-opened ones included: wait for its stream and for the last user of the workspaces (a caller's
+// stream may still run on them), then free `bufs` and the staging buffer and destroy event and stream.
+void slot_close(device_slot& s, std::initializer_list<void*> bufs) {
+  DeviceGuard g(s.device);
+  if (s.stream) (void)hipStreamSynchronize(s.stream);
+  if (s.ws_used) (void)hipEventSynchronize(s.ws_free);
+  for (void* p : bufs) (void)hipFree(p);
+  (void)hipFree(s.d_stage);
+  if (s.ws_free) (void)hipEventDestroy(s.ws_free);
+  if (s.stream) (void)hipStreamDestroy(s.stream);
+}
+
+// Workspace ordering across streams (the *_async calls may be given any stream): the stream that uses a slot's
+// workspaces or resident keys next waits for the event recorded after the previous use; the host waits for it before
+// it frees or rewrites a buffer that enqueued kernels may still read.  The entry points order: ws_begin before the
+// *_device worker, ws_end after it; the workers only call ws_grow / ws_host_wait where they regrow or rewrite.
+int ws_begin(device_slot& s, hipStream_t st) {
+  if (s.ws_used && s.ws_last != st) HIP_TRY(hipStreamWaitEvent(st, s.ws_free, 0));
+  return 0;
+}
+int ws_end(device_slot& s, hipStream_t st) {
+  HIP_TRY(hipEventRecord(s.ws_free, st));
+  s.ws_last = st;
+  s.ws_used = true;
+  return 0;
+}
+int ws_host_wait(device_slot& s) {
+  if (s.ws_used) HIP_TRY(hipEventSynchronize(s.ws_free));
+  return 0;
+}
+int ws_grow(device_slot& s, void** ptr, size_t* cap, size_t bytes) {
+  if (*cap >= bytes) return 0;
+  RC_TRY(ws_host_wait(s));  // no launch may still read the old buffer
+  return grow_device_buffer(ptr, cap, bytes);
+}
+
+using staged_in = std::initializer_list<std::pair<const void*, size_t>>;  // (host pointer or null, bytes)
+
+// Stage host buffers into the slot's staging allocation (on the slot's stream).  Returns device pointers
+// in order, plus one for `extra_out_bytes` of output.
+int stage(device_slot& s, staged_in in, std::vector<void*>& dptr, size_t extra_out_bytes) {
+  size_t total = 0;
+  std::vector<size_t> off;
+  for (auto& x : in) {
+    off.push_back(total);
+    total += (x.second + 255) & ~(size_t)255;
+  }
+  const size_t out_off = total;
+  total += (extra_out_bytes + 255) & ~(size_t)255;
+  RC_TRY(ws_grow(s, &s.d_stage, &s.stage_cap, total ? total : 256));
+  size_t i = 0;
+  dptr.clear();
+  for (auto& x : in) {
+    void* d = (char*)s.d_stage + off[i++];
+    if (x.first && x.second) HIP_TRY(hipMemcpyAsync(d, x.first, x.second, hipMemcpyHostToDevice, s.stream));
+    dptr.push_back(x.first ? d : nullptr);
+  }
+  dptr.push_back((char*)s.d_stage + out_off);
+  return 0;
+}
+
+struct copy_back {  // after the launch: host dst (skipped when null) <- staged pointer d[src], bytes
+  void* dst;
+  size_t src, bytes;
+};
+
+// One host-buffer call on a slot's own stream (caller holds the context's lock and has set the slot's device): order
+// the workspaces after their previous user, stage `in` plus out_bytes of output, launch(s, d) on the staged pointers,
+// copy `back` to the host, mark the workspaces used and wait.  S: the context type that derives from device_slot.
+template <class S, class F>
+int staged_run(S& s, staged_in in, size_t out_bytes, std::initializer_list<copy_back> back, F&& launch) {
+  RC_TRY(ws_begin(s, s.stream));
+  std::vector<void*> d;
+  RC_TRY(stage(s, in, d, out_bytes));
+  RC_TRY(launch(s, d));
+  for (auto& b : back)
+    if (b.dst) HIP_TRY(hipMemcpyAsync(b.dst, d[b.src], b.bytes, hipMemcpyDeviceToHost, s.stream));
+  RC_TRY(ws_end(s, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
   return 0;
 }
 

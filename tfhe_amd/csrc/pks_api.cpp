@@ -45,10 +45,9 @@ int tfhe_hip_pks_list_check(const tfhe_pks_params* pp, size_t packed_words, size
   return 0;
 }
 
-struct tfhe_pks_ctx {
+// d_A / d_A0 / d_A1 / d_T and the key are shared by every call: ordered across streams by the slot's ws_begin / ws_end
+struct tfhe_pks_ctx : device_slot {
   tfhe_pks_params pp{};
-  int device = 0;
-  hipStream_t stream = nullptr;
   u64* d_pksk = nullptr;
   u64* d_corr = nullptr;
   bool key = false;
@@ -61,8 +60,6 @@ struct tfhe_pks_ctx {
   void* d_planes = nullptr;
   void* d_A0 = nullptr;
   void* d_A1 = nullptr;
-  u64* d_io = nullptr;
-  size_t io_cap = 0;  // bytes
   std::mutex mu;
 };
 
@@ -70,6 +67,7 @@ namespace {
 
 int ensure_rows(tfhe_pks_ctx* c, size_t rows) {
   if (c->rows_cap >= rows) return 0;
+  RC_TRY(ws_host_wait(*c));  // no launch may still use the old buffers
   for (void* p : {(void*)c->d_A, (void*)c->d_T, c->d_A0, c->d_A1}) (void)hipFree(p);
   c->d_A = nullptr;
   c->d_T = nullptr;
@@ -88,6 +86,7 @@ int ensure_rows(tfhe_pks_ctx* c, size_t rows) {
   return 0;
 }
 
+// chunks of whole groups under the T budget (the caller orders the workspaces: ws_begin / ws_end)
 int pack_device(tfhe_pks_ctx* c, const u64* d_lwes, size_t count, u64* d_out, hipStream_t s) {
   const tfhe_pks_params& p = c->pp;
   const size_t Nc = (size_t)(p.out_k + 1) * p.out_N, lpg = p.lwe_per_glwe;
@@ -139,22 +138,18 @@ int tfhe_hip_pks_create(const tfhe_pks_params* pp, int device, tfhe_pks_ctx** ou
   if (!out) return fail(TFHE_HIP_EINVAL, "pks_create: null out");
   *out = nullptr;
   if (!pks_valid(pp)) return fail(TFHE_HIP_EINVAL, "pks_create: invalid parameters");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(TFHE_HIP_EINVAL, "pks_create: device %d of %d", device, ndev);
-  DeviceGuard g(device);
   tfhe_pks_ctx* c = new tfhe_pks_ctx();
   c->pp = *pp;
-  c->device = device;
   {
     const char* e = getenv("TFHE_HIP_PKS_VALU");
     // the matrix-core GEMM needs two int8 bytes per digit (base <= 2^15: a balanced digit reaches +2^(B-1), and
     // +2^15 would need a high byte of +128), the key planes' level limit (<= 8) and 64-deep k steps
     c->valu = (e && e[0] == '1') || pp->base_log > 15 || pp->level > 8 || (pp->in_dim * pp->level) % 64 != 0;
   }
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete c;
-    return fail(TFHE_HIP_EDEVICE, "pks_create: hipStreamCreate failed");
+  const int rc = slot_open(*c, device, "pks_create", "hipStreamCreate failed");
+  if (rc) {
+    tfhe_hip_pks_destroy(c);
+    return rc;
   }
   *out = c;
   return 0;
@@ -162,19 +157,7 @@ int tfhe_hip_pks_create(const tfhe_pks_params* pp, int device, tfhe_pks_ctx** ou
 
 void tfhe_hip_pks_destroy(tfhe_pks_ctx* c) {
   if (!c) return;
-  {
-    DeviceGuard g(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->d_pksk);
-    (void)hipFree(c->d_corr);
-    (void)hipFree(c->d_A);
-    (void)hipFree(c->d_T);
-    (void)hipFree(c->d_io);
-    (void)hipFree(c->d_planes);
-    (void)hipFree(c->d_A0);
-    (void)hipFree(c->d_A1);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-  }
+  slot_close(*c, {c->d_pksk, c->d_corr, c->d_A, c->d_T, c->d_planes, c->d_A0, c->d_A1});
   delete c;
 }
 
@@ -184,6 +167,7 @@ int tfhe_hip_pks_load_key(tfhe_pks_ctx* c, const uint64_t* pksk, size_t len) {
     return fail(TFHE_HIP_EINVAL, "pks_load_key: length %zu, expected %zu", len, tfhe::client::pksk_len(c->pp));
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
+  RC_TRY(ws_host_wait(*c));  // a call in flight on a caller's stream still reads the resident key
   c->key = false;
   const size_t Nc = (size_t)(c->pp.out_k + 1) * c->pp.out_N;
   if (!c->d_pksk) HIP_TRY(hipMalloc(&c->d_pksk, len * 8));
@@ -208,7 +192,10 @@ int tfhe_hip_pks_pack_async(tfhe_pks_ctx* c, const uint64_t* d_lwes, size_t coun
   if (!d_lwes || !d_glwes) return fail(TFHE_HIP_EINVAL, "pks_pack: null buffer");
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  return pack_device(c, d_lwes, count, d_glwes, resolve_stream(stream, c->stream));
+  hipStream_t st = resolve_stream(stream, c->stream);
+  RC_TRY(ws_begin(*c, st));
+  RC_TRY(pack_device(c, d_lwes, count, d_glwes, st));
+  return ws_end(*c, st);
 }
 
 int tfhe_hip_pks_pack(tfhe_pks_ctx* c, const uint64_t* lwes, size_t count, uint64_t* glwes) {
@@ -221,15 +208,11 @@ int tfhe_hip_pks_pack(tfhe_pks_ctx* c, const uint64_t* lwes, size_t count, uint6
   DeviceGuard g(c->device);
   const tfhe_pks_params& p = c->pp;
   const size_t in_bytes = count * (p.in_dim + 1) * 8, groups = (count + p.lwe_per_glwe - 1) / p.lwe_per_glwe;
-  const size_t out_bytes = groups * (p.out_k + 1) * p.out_N * 8, in_off = (out_bytes + 255) & ~(size_t)255;
-  RC_TRY(grow_device_buffer((void**)&c->d_io, &c->io_cap, in_off + in_bytes));
-  u64* d_out = c->d_io;
-  u64* d_in = (u64*)((char*)c->d_io + in_off);
-  HIP_TRY(hipMemcpyAsync(d_in, lwes, in_bytes, hipMemcpyHostToDevice, c->stream));
-  RC_TRY(pack_device(c, d_in, count, d_out, c->stream));
-  HIP_TRY(hipMemcpyAsync(glwes, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  const size_t out_bytes = groups * (p.out_k + 1) * p.out_N * 8;
+  return staged_run(*c, {{lwes, in_bytes}}, out_bytes, {{glwes, 1, out_bytes}},
+                    [&](tfhe_pks_ctx& s, std::vector<void*>& d) {
+                      return pack_device(&s, (const u64*)d[0], count, (u64*)d[1], s.stream);
+                    });
 }
 
 size_t tfhe_hip_pks_packed_words(const tfhe_pks_params* pp, uint32_t bodies) {
@@ -275,14 +258,11 @@ int tfhe_hip_pks_unpack_extract(tfhe_pks_ctx* c, const uint64_t* packed, size_t 
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
   const size_t out_bytes = count * ((size_t)c->pp.out_k * c->pp.out_N + 1) * 8;
-  const size_t in_off = (out_bytes + 255) & ~(size_t)255;
-  RC_TRY(grow_device_buffer((void**)&c->d_io, &c->io_cap, in_off + packed_words * 8));
-  u64* d_in = (u64*)((char*)c->d_io + in_off);
-  HIP_TRY(hipMemcpyAsync(d_in, packed, packed_words * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(unpack_extract_device(c->pp, d_in, count, c->d_io, c->stream));
-  HIP_TRY(hipMemcpyAsync(lwes_out, c->d_io, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return staged_run(*c, {{packed, packed_words * 8}}, out_bytes, {{lwes_out, 1, out_bytes}},
+                    [&](tfhe_pks_ctx& s, std::vector<void*>& d) -> int {
+                      HIP_TRY(unpack_extract_device(s.pp, (const u64*)d[0], count, (u64*)d[1], s.stream));
+                      return 0;
+                    });
 }
 
 int tfhe_hip_glwe_phase(uint32_t k, uint32_t N, const uint64_t* key, const uint64_t* glwe, uint64_t* out) {

@@ -38,10 +38,9 @@ size_t sns_chunk() {
 
 }  // namespace
 
-struct tfhe_sns_ctx {
+// d_acc, d_D, d_O, d_lut and the key are shared by every call: ordered across streams by the slot's ws_begin / ws_end
+struct tfhe_sns_ctx : device_slot {
   tfhe_sns_params sp{};
-  int device = 0;
-  hipStream_t stream = nullptr;
   void* d_fconst = nullptr;
   void* d_bskf = nullptr;  // key limb spectra (n x 9 x 3 x 5 x 1024 complex f64)
   bool key = false;
@@ -51,39 +50,14 @@ struct tfhe_sns_ctx {
   u64* d_lut = nullptr;
   uint32_t lut_mm = 0;
   size_t ws_cap = 0;
-  // d_acc, d_D, d_O, d_lut and the key are shared by every call: each user waits for `ws_free` (the previous
-  // user's completion) on its own stream, as the engine shards do (api.cpp ws_begin / ws_end)
-  hipEvent_t ws_free = nullptr;
-  hipStream_t ws_last = nullptr;
-  bool ws_used = false;
-  u64* d_io = nullptr;
-  size_t io_cap = 0;
   std::mutex mu;
 };
 
 namespace {
 
-// Workspace ordering across streams (tfhe_hip_sns_squash_async may be called on any stream): the stream that uses
-// the workspaces next waits for the event recorded after the previous use; the host waits for it before it frees
-// or rewrites a buffer that enqueued kernels may still read.
-int ws_begin(tfhe_sns_ctx* c, hipStream_t st) {
-  if (c->ws_used && c->ws_last != st) HIP_TRY(hipStreamWaitEvent(st, c->ws_free, 0));
-  return 0;
-}
-int ws_end(tfhe_sns_ctx* c, hipStream_t st) {
-  HIP_TRY(hipEventRecord(c->ws_free, st));
-  c->ws_last = st;
-  c->ws_used = true;
-  return 0;
-}
-int ws_host_wait(tfhe_sns_ctx* c) {
-  if (c->ws_used) HIP_TRY(hipEventSynchronize(c->ws_free));
-  return 0;
-}
-
 int ensure_ws(tfhe_sns_ctx* c, size_t B) {
   if (c->ws_cap >= B) return 0;
-  RC_TRY(ws_host_wait(c));  // no launch may still use the old buffers
+  RC_TRY(ws_host_wait(*c));  // no launch may still use the old buffers
   (void)hipFree(c->d_acc);
   (void)hipFree(c->d_D);
   (void)hipFree(c->d_O);
@@ -102,18 +76,18 @@ int ensure_lut(tfhe_sns_ctx* c, uint32_t mm) {
   if (c->d_lut && c->lut_mm == mm) return 0;
   std::vector<u64> lut(2 * (size_t)c->sp.N);
   tfhe::client::sns_lut_identity(c->sp, mm, lut.data());
-  RC_TRY(ws_host_wait(c));  // a call in flight on another stream still reads the previous modulus' LUT
+  RC_TRY(ws_host_wait(*c));  // a call in flight on another stream still reads the previous modulus' LUT
   if (!c->d_lut) HIP_TRY(hipMalloc(&c->d_lut, lut.size() * 8));
   HIP_TRY(hipMemcpy(c->d_lut, lut.data(), lut.size() * 8, hipMemcpyHostToDevice));
   c->lut_mm = mm;
   return 0;
 }
 
-// squash (out != null) or blind rotate only (acc_out != null) of B device ciphertexts
+// squash (out != null) or blind rotate only (acc_out != null) of B device ciphertexts (the caller orders the
+// workspaces: ws_begin / ws_end)
 int run_device(tfhe_sns_ctx* c, const u64* d_in, size_t B, u64* d_out, u64* d_acc_out, hipStream_t s) {
   const size_t chunk = std::min(B, sns_chunk());
   RC_TRY(ensure_ws(c, chunk));
-  RC_TRY(ws_begin(c, s));
   const size_t in_dim = c->sp.n + 1, out_dim = 2 * ((size_t)c->sp.k * c->sp.N + 1);
   const size_t acc_len = (size_t)(c->sp.k + 1) * 2 * c->sp.N;
   for (size_t f = 0; f < B; f += chunk) {
@@ -124,7 +98,7 @@ int run_device(tfhe_sns_ctx* c, const u64* d_in, size_t B, u64* d_out, u64* d_ac
     if (d_acc_out)
       HIP_TRY(hipMemcpyAsync(d_acc_out + f * acc_len, c->d_acc, nb * acc_len * 8, hipMemcpyDeviceToDevice, s));
   }
-  return ws_end(c, s);
+  return 0;
 }
 
 int host_call(tfhe_sns_ctx* c, const u64* in, size_t B, uint32_t mm, u64* out, bool acc_only) {
@@ -137,15 +111,10 @@ int host_call(tfhe_sns_ctx* c, const u64* in, size_t B, uint32_t mm, u64* out, b
   RC_TRY(ensure_lut(c, mm));
   const size_t in_bytes = B * (c->sp.n + 1) * 8;
   const size_t out_bytes = acc_only ? B * (c->sp.k + 1) * 2 * c->sp.N * 8 : B * 2 * ((size_t)c->sp.k * c->sp.N + 1) * 8;
-  const size_t off = (out_bytes + 255) & ~(size_t)255;
-  RC_TRY(grow_device_buffer((void**)&c->d_io, &c->io_cap, off + in_bytes));
-  u64* d_out = c->d_io;
-  u64* d_in = (u64*)((char*)c->d_io + off);
-  HIP_TRY(hipMemcpyAsync(d_in, in, in_bytes, hipMemcpyHostToDevice, c->stream));
-  RC_TRY(run_device(c, d_in, B, acc_only ? nullptr : d_out, acc_only ? d_out : nullptr, c->stream));
-  HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return staged_run(*c, {{in, in_bytes}}, out_bytes, {{out, 1, out_bytes}}, [&](tfhe_sns_ctx& s, std::vector<void*>& d) {
+    u64* d_out = (u64*)d[1];
+    return run_device(&s, (const u64*)d[0], B, acc_only ? nullptr : d_out, acc_only ? d_out : nullptr, s.stream);
+  });
 }
 
 }  // namespace
@@ -180,21 +149,20 @@ int tfhe_hip_sns_create(const tfhe_sns_params* sp, int device, tfhe_sns_ctx** ou
   *out = nullptr;
   if (!sns_valid(sp))
     return fail(TFHE_HIP_EUNSUPPORTED, "sns_create: the device kernels cover k = 2, N = 2048, 2^24 x 3");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(TFHE_HIP_EINVAL, "sns_create: device %d of %d", device, ndev);
-  DeviceGuard g(device);
   tfhe_sns_ctx* c = new tfhe_sns_ctx();
   c->sp = *sp;
-  c->device = device;
-  std::vector<unsigned char> F(tfhe::sns_fft_const_bytes());
-  tfhe::make_sns_fft_const(F.data());
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ws_free, hipEventDisableTiming) != hipSuccess ||
-      hipMalloc(&c->d_fconst, F.size()) != hipSuccess ||
-      hipMemcpy(c->d_fconst, F.data(), F.size(), hipMemcpyHostToDevice) != hipSuccess) {
+  int rc = slot_open(*c, device, "sns_create", "device setup failed");
+  if (!rc) {
+    DeviceGuard g(device);
+    std::vector<unsigned char> F(tfhe::sns_fft_const_bytes());
+    tfhe::make_sns_fft_const(F.data());
+    if (hipMalloc(&c->d_fconst, F.size()) != hipSuccess ||
+        hipMemcpy(c->d_fconst, F.data(), F.size(), hipMemcpyHostToDevice) != hipSuccess)
+      rc = fail(TFHE_HIP_EDEVICE, "sns_create: device setup failed");
+  }
+  if (rc) {
     tfhe_hip_sns_destroy(c);
-    return fail(TFHE_HIP_EDEVICE, "sns_create: device setup failed");
+    return rc;
   }
   *out = c;
   return 0;
@@ -202,15 +170,7 @@ int tfhe_hip_sns_create(const tfhe_sns_params* sp, int device, tfhe_sns_ctx** ou
 
 void tfhe_hip_sns_destroy(tfhe_sns_ctx* c) {
   if (!c) return;
-  {
-    DeviceGuard g(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->ws_used) (void)hipEventSynchronize(c->ws_free);  // a caller's stream may still run on the workspaces
-    for (void* p : {c->d_fconst, c->d_bskf, (void*)c->d_acc, c->d_D, c->d_O, (void*)c->d_lut, (void*)c->d_io})
-      (void)hipFree(p);
-    if (c->ws_free) (void)hipEventDestroy(c->ws_free);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-  }
+  slot_close(*c, {c->d_fconst, c->d_bskf, c->d_acc, c->d_D, c->d_O, c->d_lut});
   delete c;
 }
 
@@ -220,19 +180,19 @@ int tfhe_hip_sns_load_key(tfhe_sns_ctx* c, const uint64_t* bsk, size_t len) {
     return fail(TFHE_HIP_EINVAL, "sns_load_key: length %zu, expected %zu", len, tfhe::client::sns_bsk_len(c->sp));
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  RC_TRY(ws_host_wait(c));  // a call in flight on a caller's stream still reads the resident key
+  RC_TRY(ws_host_wait(*c));  // a call in flight on a caller's stream still reads the resident key
   c->key = false;
   if (!c->d_bskf) HIP_TRY(hipMalloc(&c->d_bskf, tfhe::sns_fft_key_len(c->sp.n) * 16));
-  // stage the key words in chunks of polynomials (lo, hi planes) through the io buffer, convert to limb spectra
+  // stage the key words in chunks of polynomials (lo, hi planes) through the staging buffer, convert to limb spectra
   const size_t poly_words = 2 * (size_t)c->sp.N, polys = len / poly_words, per = 2048;
   const size_t bytes = per * poly_words * 8;
-  RC_TRY(grow_device_buffer((void**)&c->d_io, &c->io_cap, bytes));
+  RC_TRY(ws_grow(*c, &c->d_stage, &c->stage_cap, bytes));
   for (size_t f = 0; f < polys; f += per) {
     const size_t np = std::min(per, polys - f);
-    HIP_TRY(hipMemcpyAsync(c->d_io, bsk + f * poly_words, np * poly_words * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(tfhe::launch_sns_bsk_to_fft(c->d_io, (char*)c->d_bskf + f * tfhe::SNS_FFT_POLY_BYTES, np, c->d_fconst,
-                                        c->stream));
-    // the io buffer is reused by the next chunk's copy: same stream, ordered
+    HIP_TRY(hipMemcpyAsync(c->d_stage, bsk + f * poly_words, np * poly_words * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(tfhe::launch_sns_bsk_to_fft((const u64*)c->d_stage, (char*)c->d_bskf + f * tfhe::SNS_FFT_POLY_BYTES, np,
+                                        c->d_fconst, c->stream));
+    // the staging buffer is reused by the next chunk's copy: same stream, ordered
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->key = true;
@@ -256,7 +216,10 @@ int tfhe_hip_sns_squash_async(tfhe_sns_ctx* c, const uint64_t* d_in, size_t B, u
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
   RC_TRY(ensure_lut(c, mm));
-  return run_device(c, d_in, B, d_out, nullptr, resolve_stream(stream, c->stream));
+  hipStream_t st = resolve_stream(stream, c->stream);
+  RC_TRY(ws_begin(*c, st));
+  RC_TRY(run_device(c, d_in, B, d_out, nullptr, st));
+  return ws_end(*c, st);
 }
 
 int tfhe_hip_sns_phase(const tfhe_sns_params* sp, const uint64_t* glwe_key, const uint64_t* cts, size_t count,

@@ -29,10 +29,9 @@ constexpr size_t SPK_MAX_ROWS = 65535ull * 64;   // the GEMM grid's row tiles (s
 
 }  // namespace
 
-struct tfhe_sns_pks_ctx {
+// d_A, d_T and the key are shared by every call: ordered across streams by the slot's ws_begin / ws_end
+struct tfhe_sns_pks_ctx : device_slot {
   tfhe_sns_pks_params pp{};
-  int device = 0;
-  hipStream_t stream = nullptr;
   size_t chunk_groups = 0;  // TFHE_HIP_SNS_PKS_CHUNK at create; 0: by the T budget
   u64* d_pksk = nullptr;
   u64* d_corr = nullptr;
@@ -40,36 +39,14 @@ struct tfhe_sns_pks_ctx {
   u64* d_A = nullptr;
   u64* d_T = nullptr;
   size_t rows_cap = 0;  // LWEs the A / T workspaces hold
-  // d_A, d_T and the key are shared by every call: each user waits for `ws_free` (the previous user's
-  // completion) on its own stream, as sns_api.cpp orders its workspaces
-  hipEvent_t ws_free = nullptr;
-  hipStream_t ws_last = nullptr;
-  bool ws_used = false;
-  u64* d_io = nullptr;
-  size_t io_cap = 0;  // bytes
   std::mutex mu;
 };
 
 namespace {
 
-int ws_begin(tfhe_sns_pks_ctx* c, hipStream_t st) {
-  if (c->ws_used && c->ws_last != st) HIP_TRY(hipStreamWaitEvent(st, c->ws_free, 0));
-  return 0;
-}
-int ws_end(tfhe_sns_pks_ctx* c, hipStream_t st) {
-  HIP_TRY(hipEventRecord(c->ws_free, st));
-  c->ws_last = st;
-  c->ws_used = true;
-  return 0;
-}
-int ws_host_wait(tfhe_sns_pks_ctx* c) {
-  if (c->ws_used) HIP_TRY(hipEventSynchronize(c->ws_free));
-  return 0;
-}
-
 int ensure_rows(tfhe_sns_pks_ctx* c, size_t rows) {
   if (c->rows_cap >= rows) return 0;
-  RC_TRY(ws_host_wait(c));  // no launch may still use the old buffers
+  RC_TRY(ws_host_wait(*c));  // no launch may still use the old buffers
   (void)hipFree(c->d_A);
   (void)hipFree(c->d_T);
   c->d_A = c->d_T = nullptr;
@@ -81,7 +58,8 @@ int ensure_rows(tfhe_sns_pks_ctx* c, size_t rows) {
   return 0;
 }
 
-// chunks of whole groups: the T workspace stays under its budget (or holds chunk_groups groups)
+// chunks of whole groups: the T workspace stays under its budget (or holds chunk_groups groups); the caller orders
+// the workspaces (ws_begin / ws_end)
 int pack_device(tfhe_sns_pks_ctx* c, const u64* d_lwes, size_t count, u64* d_out, hipStream_t s) {
   const tfhe_sns_pks_params& p = c->pp;
   const size_t Nc = (size_t)(p.out_k + 1) * p.out_N, lpg = p.lwe_per_glwe, ct_words = 2 * ((size_t)p.in_dim + 1);
@@ -89,14 +67,13 @@ int pack_device(tfhe_sns_pks_ctx* c, const u64* d_lwes, size_t count, u64* d_out
   groups = std::max<size_t>(1, std::min(groups, SPK_MAX_ROWS / lpg));
   const size_t rows = std::min(count, groups * lpg);
   RC_TRY(ensure_rows(c, rows));
-  RC_TRY(ws_begin(c, s));
   for (size_t first = 0; first < count; first += rows) {
     const size_t n = std::min(rows, count - first);
     HIP_TRY(tfhe::launch_sns_pks_pack(d_lwes + first * ct_words, n, (int)p.in_dim, (int)p.base_log, (int)p.level,
                                       (int)p.out_k, (int)p.out_N, (int)lpg, c->d_pksk, c->d_corr, c->d_A, c->d_T,
                                       d_out + (first / lpg) * 2 * Nc, s));
   }
-  return ws_end(c, s);
+  return 0;
 }
 
 int pack_checks(tfhe_sns_pks_ctx* c, const void* in, size_t count, const void* out) {
@@ -139,22 +116,17 @@ int tfhe_hip_sns_pks_create(const tfhe_sns_pks_params* pp, int device, tfhe_sns_
   if (!out) return fail(TFHE_HIP_EINVAL, "sns_pks_create: null out");
   *out = nullptr;
   if (!spk_valid(pp)) return fail(TFHE_HIP_EINVAL, "sns_pks_create: invalid parameters");
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(TFHE_HIP_EINVAL, "sns_pks_create: device %d of %d", device, ndev);
-  DeviceGuard g(device);
   tfhe_sns_pks_ctx* c = new tfhe_sns_pks_ctx();
   c->pp = *pp;
-  c->device = device;
   {
     const char* e = getenv("TFHE_HIP_SNS_PKS_CHUNK");
     const long x = e ? atol(e) : 0;
     c->chunk_groups = x > 0 ? (size_t)x : 0;
   }
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ws_free, hipEventDisableTiming) != hipSuccess) {
+  const int rc = slot_open(*c, device, "sns_pks_create", "device setup failed");
+  if (rc) {
     tfhe_hip_sns_pks_destroy(c);
-    return fail(TFHE_HIP_EDEVICE, "sns_pks_create: device setup failed");
+    return rc;
   }
   *out = c;
   return 0;
@@ -162,14 +134,7 @@ int tfhe_hip_sns_pks_create(const tfhe_sns_pks_params* pp, int device, tfhe_sns_
 
 void tfhe_hip_sns_pks_destroy(tfhe_sns_pks_ctx* c) {
   if (!c) return;
-  {
-    DeviceGuard g(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->ws_used) (void)hipEventSynchronize(c->ws_free);  // a caller's stream may still run on the workspaces
-    for (u64* p : {c->d_pksk, c->d_corr, c->d_A, c->d_T, c->d_io}) (void)hipFree(p);
-    if (c->ws_free) (void)hipEventDestroy(c->ws_free);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-  }
+  slot_close(*c, {c->d_pksk, c->d_corr, c->d_A, c->d_T});
   delete c;
 }
 
@@ -179,7 +144,7 @@ int tfhe_hip_sns_pks_load_key(tfhe_sns_pks_ctx* c, const uint64_t* pksk, size_t 
     return fail(TFHE_HIP_EINVAL, "sns_pks_load_key: length %zu, expected %zu", len, tfhe::client::sns_pksk_len(c->pp));
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  RC_TRY(ws_host_wait(c));  // a call in flight on a caller's stream still reads the resident key
+  RC_TRY(ws_host_wait(*c));  // a call in flight on a caller's stream still reads the resident key
   c->key = false;
   const size_t Nc = (size_t)(c->pp.out_k + 1) * c->pp.out_N;
   if (!c->d_pksk) HIP_TRY(hipMalloc(&c->d_pksk, len * 8));
@@ -198,7 +163,10 @@ int tfhe_hip_sns_pks_pack_async(tfhe_sns_pks_ctx* c, const uint64_t* d_lwes, siz
   if (count == 0) return 0;
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  return pack_device(c, d_lwes, count, d_glwes, resolve_stream(stream, c->stream));
+  hipStream_t st = resolve_stream(stream, c->stream);
+  RC_TRY(ws_begin(*c, st));
+  RC_TRY(pack_device(c, d_lwes, count, d_glwes, st));
+  return ws_end(*c, st);
 }
 
 int tfhe_hip_sns_pks_pack(tfhe_sns_pks_ctx* c, const uint64_t* lwes, size_t count, uint64_t* glwes) {
@@ -209,15 +177,11 @@ int tfhe_hip_sns_pks_pack(tfhe_sns_pks_ctx* c, const uint64_t* lwes, size_t coun
   const tfhe_sns_pks_params& p = c->pp;
   const size_t in_bytes = count * 2 * ((size_t)p.in_dim + 1) * 8;
   const size_t groups = (count + p.lwe_per_glwe - 1) / p.lwe_per_glwe;
-  const size_t out_bytes = groups * (p.out_k + 1) * 2 * p.out_N * 8, in_off = (out_bytes + 255) & ~(size_t)255;
-  RC_TRY(grow_device_buffer((void**)&c->d_io, &c->io_cap, in_off + in_bytes));
-  u64* d_out = c->d_io;
-  u64* d_in = (u64*)((char*)c->d_io + in_off);
-  HIP_TRY(hipMemcpyAsync(d_in, lwes, in_bytes, hipMemcpyHostToDevice, c->stream));
-  RC_TRY(pack_device(c, d_in, count, d_out, c->stream));
-  HIP_TRY(hipMemcpyAsync(glwes, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  const size_t out_bytes = groups * (p.out_k + 1) * 2 * p.out_N * 8;
+  return staged_run(*c, {{lwes, in_bytes}}, out_bytes, {{glwes, 1, out_bytes}},
+                    [&](tfhe_sns_pks_ctx& s, std::vector<void*>& d) {
+                      return pack_device(&s, (const u64*)d[0], count, (u64*)d[1], s.stream);
+                    });
 }
 
 int tfhe_hip_sns_pks_pack_host(const tfhe_sns_pks_params* pp, const uint64_t* pksk, const uint64_t* lwes, size_t count,
