@@ -303,6 +303,22 @@ def _c_u64(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.uint64))
 
 
+def _dptr(t):
+    """The C argument of an optional device tensor: its address, or a null pointer for None."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _lut_index(lut_index, rows: int, noun: str):
+    """The C argument of the optional ``lut_index`` of a host entry point: contiguous uint32, one entry per row (each
+    ``noun`` of the call), or a null pointer for None.  The pointer keeps its array alive."""
+    if lut_index is None:
+        return None
+    li = np.ascontiguousarray(np.asarray(lut_index, dtype=np.uint32))
+    if li.shape[0] != rows:
+        raise ValueError(f"lut_index must have one entry per {noun}")
+    return li.ctypes.data_as(_U32P)
+
+
 def encode_bool(b) -> np.ndarray:
     b = np.asarray(b, dtype=bool)
     return np.where(b, np.uint64(MU), np.uint64((1 << 64) - MU)).astype(np.uint64)
@@ -582,8 +598,7 @@ class Engine:
     def load_keys_device(self, d_bsk, d_ksk) -> "Engine":
         """Keys already in HBM on this device (torch tensors of dtype int64/uint64, e.g. after an
         RCCL broadcast)."""
-        _check(lib().tfhe_hip_load_keys_device(self._h, ctypes.c_void_p(d_bsk.data_ptr()), d_bsk.numel(),
-                                               ctypes.c_void_p(d_ksk.data_ptr()), d_ksk.numel()))
+        _check(lib().tfhe_hip_load_keys_device(self._h, _dptr(d_bsk), d_bsk.numel(), _dptr(d_ksk), d_ksk.numel()))
         return self
 
     # -- LUTs -------------------------------------------------------------------------------
@@ -603,20 +618,13 @@ class Engine:
         up to ``lut_index``)."""
         cts = _c_u64(cts).reshape(-1, row_len)
         luts = _c_u64(luts).reshape(-1, self.params.N)
-        li = None
-        if lut_index is not None:
-            li = np.ascontiguousarray(np.asarray(lut_index, dtype=np.uint32))
-            if li.shape[0] != cts.shape[0]:
-                raise ValueError("lut_index must have one entry per ciphertext")
         return cts, (self._h, _u64(cts), cts.shape[0], _u64(luts), luts.shape[0],
-                     li.ctypes.data_as(_U32P) if li is not None else None)
+                     _lut_index(lut_index, cts.shape[0], "ciphertext"))
 
     def _pbs_async_args(self, d_in, d_luts, d_lut_index, d_out, stream):
         """Device tensors of pbs_async / pbs_many_async -> the C arguments (up to ``d_idx``, from ``d_out`` on)."""
-        head = (self._h, ctypes.c_void_p(d_in.data_ptr()), d_in.shape[0], ctypes.c_void_p(d_luts.data_ptr()),
-                d_luts.numel() // self.params.N,
-                ctypes.c_void_p(d_lut_index.data_ptr()) if d_lut_index is not None else None)
-        return head, (ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(_stream_handle(stream, self.device)))
+        head = (self._h, _dptr(d_in), d_in.shape[0], _dptr(d_luts), d_luts.numel() // self.params.N, _dptr(d_lut_index))
+        return head, (_dptr(d_out), ctypes.c_void_p(_stream_handle(stream, self.device)))
 
     def pbs(self, cts: np.ndarray, luts: np.ndarray, lut_index=None) -> np.ndarray:
         """Batched keyswitch_programmable_bootstrap over host arrays: (B, dim+1) -> (B, dim+1)."""
@@ -713,9 +721,8 @@ class Engine:
         """Device-resident ``expand_compact`` (torch tensors on this device; d_out: (rows, lwe_dim + 1)), enqueued on
         ``stream`` like ``pbs_async``."""
         _check(lib().tfhe_hip_expand_compact_async(
-            self._h, ctypes.c_void_p(d_words.data_ptr()), d_words.numel(), int(lwe_dim), int(count), int(rep),
-            self._rows(count, rep, rows), ctypes.c_void_p(d_out.data_ptr()),
-            ctypes.c_void_p(_stream_handle(stream, self.device))))
+            self._h, _dptr(d_words), d_words.numel(), int(lwe_dim), int(count), int(rep), self._rows(count, rep, rows),
+            _dptr(d_out), ctypes.c_void_p(_stream_handle(stream, self.device))))
 
     def expand_compact_device(self, d_words, lwe_dim: int, count: int, rep: int = 1, rows=None):
         """expand_compact_async into a fresh (rows, lwe_dim + 1) tensor on torch's current stream (no host
@@ -733,15 +740,10 @@ class Engine:
         w = _c_u64(words).reshape(-1)
         luts = _c_u64(luts).reshape(-1, self.params.N)
         rows = self._rows(count, rep, rows)
-        li = None
-        if lut_index is not None:
-            li = np.ascontiguousarray(np.asarray(lut_index, dtype=np.uint32))
-            if li.shape[0] != rows:
-                raise ValueError("lut_index must have one entry per output row")
+        li = _lut_index(lut_index, rows, "output row")
         out = np.zeros((max(rows, 0), self.params.io_dim + 1), dtype=np.uint64)
         _check(lib().tfhe_hip_expand_cast(self._h, _u64(w), w.size, int(count), int(rep), rows, _u64(luts),
-                                          luts.shape[0], li.ctypes.data_as(_U32P) if li is not None else None,
-                                          _u64(out)))
+                                          luts.shape[0], li, _u64(out)))
         return out
 
     def expand_cast_async(self, d_words, count: int, d_luts, d_out, rep: int = 1, rows=None, d_lut_index=None,
@@ -749,10 +751,9 @@ class Engine:
         """Device-resident ``expand_cast`` (torch tensors on this device; d_out: (rows, io_dim + 1)), enqueued on
         ``stream`` like ``pbs_async``."""
         _check(lib().tfhe_hip_expand_cast_async(
-            self._h, ctypes.c_void_p(d_words.data_ptr()), d_words.numel(), int(count), int(rep),
-            self._rows(count, rep, rows), ctypes.c_void_p(d_luts.data_ptr()), d_luts.numel() // self.params.N,
-            ctypes.c_void_p(d_lut_index.data_ptr()) if d_lut_index is not None else None,
-            ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(_stream_handle(stream, self.device))))
+            self._h, _dptr(d_words), d_words.numel(), int(count), int(rep), self._rows(count, rep, rows), _dptr(d_luts),
+            d_luts.numel() // self.params.N, _dptr(d_lut_index), _dptr(d_out),
+            ctypes.c_void_p(_stream_handle(stream, self.device))))
 
     def expand_cast_device(self, d_words, count: int, d_luts, rep: int = 1, rows=None, d_lut_index=None):
         """expand_cast_async into a fresh (rows, io_dim + 1) tensor on torch's current stream (no host
@@ -777,8 +778,8 @@ class Engine:
         """Device-resident ``csprng_rows`` (torch tensors on this device: d_seeds (rows, 2), d_out (rows, stride) with
         stride >= dim; words past ``dim`` of a row are left alone), enqueued on ``stream`` like ``pbs_async``."""
         _check(lib().tfhe_hip_csprng_rows_async(
-            self._h, ctypes.c_void_p(d_seeds.data_ptr()), d_seeds.shape[0], int(first_word), int(dim),
-            d_out.shape[1], ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(_stream_handle(stream, self.device))))
+            self._h, _dptr(d_seeds), d_seeds.shape[0], int(first_word), int(dim), d_out.shape[1], _dptr(d_out),
+            ctypes.c_void_p(_stream_handle(stream, self.device))))
 
     def _oprf_tables(self, luts, post_adds):
         luts = _c_u64(luts).reshape(-1, self.params.N)
@@ -795,24 +796,17 @@ class Engine:
         only."""
         s = _c_u64(seeds).reshape(-1, 2)
         luts, post = self._oprf_tables(luts, post_adds)
-        li = None
-        if lut_index is not None:
-            li = np.ascontiguousarray(np.asarray(lut_index, dtype=np.uint32))
-            if li.shape[0] != s.shape[0]:
-                raise ValueError("lut_index must have one entry per seed")
+        li = _lut_index(lut_index, s.shape[0], "seed")
         out = np.zeros((s.shape[0], self.params.io_dim + 1), dtype=np.uint64)
-        _check(lib().tfhe_hip_oprf(self._h, _u64(s), s.shape[0], _u64(luts), _u64(post), luts.shape[0],
-                                   li.ctypes.data_as(_U32P) if li is not None else None, _u64(out)))
+        _check(lib().tfhe_hip_oprf(self._h, _u64(s), s.shape[0], _u64(luts), _u64(post), luts.shape[0], li, _u64(out)))
         return out
 
     def oprf_async(self, d_seeds, d_luts, d_post_adds, d_out, d_lut_index=None, stream=None) -> None:
         """Device-resident ``oprf`` (torch tensors on this device: d_seeds (rows, 2), d_post_adds one word per LUT,
         d_out (rows, io_dim + 1)), enqueued on ``stream`` like ``pbs_async``."""
         _check(lib().tfhe_hip_oprf_async(
-            self._h, ctypes.c_void_p(d_seeds.data_ptr()), d_seeds.shape[0], ctypes.c_void_p(d_luts.data_ptr()),
-            ctypes.c_void_p(d_post_adds.data_ptr()), d_luts.numel() // self.params.N,
-            ctypes.c_void_p(d_lut_index.data_ptr()) if d_lut_index is not None else None,
-            ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(_stream_handle(stream, self.device))))
+            self._h, _dptr(d_seeds), d_seeds.shape[0], _dptr(d_luts), _dptr(d_post_adds), d_luts.numel() // self.params.N,
+            _dptr(d_lut_index), _dptr(d_out), ctypes.c_void_p(_stream_handle(stream, self.device))))
 
     def oprf_device(self, d_seeds, d_luts, d_post_adds, d_lut_index=None):
         """oprf_async into a fresh tensor: (rows, 2) seeds on this device -> (rows, io_dim + 1), queued on torch's
@@ -877,7 +871,7 @@ class Engine:
         dim = int(d_out.shape[-1])
         keep_b, bufs = self._lincomb_bufs(d_bufs, dim)
         keep_t, terms = self._lincomb_terms(row_start, term_buf, term_row, term_coef, bias)
-        _check(lib().tfhe_hip_lwe_lincomb_async(self._h, dim, *bufs, *terms, ctypes.c_void_p(d_out.data_ptr()),
+        _check(lib().tfhe_hip_lwe_lincomb_async(self._h, dim, *bufs, *terms, _dptr(d_out),
                                                 ctypes.c_void_p(_stream_handle(stream, self.device))))
         del keep_b, keep_t
 
@@ -907,9 +901,8 @@ class Engine:
             keep_b, bufs = self._lincomb_bufs(d_bufs, dim)
             keep_t, terms = self._lincomb_terms(row_start, term_buf, term_row, term_coef, bias)
             _check(lib().tfhe_hip_lincomb_pbs_async(
-                self._h, *bufs, *terms, ctypes.c_void_p(d_luts.data_ptr()), d_luts.numel() // self.params.N,
-                ctypes.c_void_p(d_lut_index.data_ptr()) if d_lut_index is not None else None,
-                ctypes.c_void_p(d_out.data_ptr()), ctypes.c_void_p(_stream_handle(None, self.device))))
+                self._h, *bufs, *terms, _dptr(d_luts), d_luts.numel() // self.params.N, _dptr(d_lut_index), _dptr(d_out),
+                ctypes.c_void_p(_stream_handle(None, self.device))))
             del keep_b, keep_t
         return d_out
 

@@ -33,6 +33,7 @@ from typing import Generator, List, Optional, Sequence, Union
 import numpy as np
 
 from . import MU, ClientKey, Engine
+from .lockstep import cat as _cat, chunks, is_torch as _is_t, run_many, split
 
 _M64 = 1 << 64
 MAX_LAUNCH = 1 << 19  # ciphertexts per engine call (P-GATE: 2 x 631 x 8 B x 512 Ki = 5.3 GB of I/O)
@@ -42,18 +43,6 @@ WIDTHS = (8, 16, 32, 64, 128, 160, 256)   # ebool / euint* / eaddress of fhEVM (
 # --------------------------------------------------------------------------------------------
 # arrays: host numpy uint64, or (a device-resident Circuit) torch int64 tensors holding the same bits
 # --------------------------------------------------------------------------------------------
-def _is_t(a) -> bool:
-    return type(a).__module__.startswith("torch")
-
-
-def _cat(seq, axis: int = 0):
-    seq = list(seq)
-    if seq and _is_t(seq[0]):
-        import torch
-        return torch.cat(seq, dim=axis)
-    return np.concatenate(seq, axis=axis)
-
-
 def _stack(seq, axis: int = 0):
     seq = list(seq)
     if seq and _is_t(seq[0]):
@@ -157,7 +146,10 @@ Op = Generator[Level, List[np.ndarray], object]
 
 
 class Circuit:
-    """Runs operator coroutines on an Engine: every yielded level is one batched PBS launch."""
+    """Runs operator coroutines on an Engine: every yielded level is one batched PBS launch.  The stepping, the cut
+    of a level into engine calls and the cut of its output into the entries' shapes are ``tfhe_amd.lockstep``'s,
+    shared with ``radix.RadixCircuit``; host arrays and device tensors take the same ``bootstrap`` and ``oprf``,
+    which differ only in the engine call (``pbs`` / ``oprf`` or ``pbs_device`` / ``oprf_device``)."""
 
     def __init__(self, engine: Engine, capacity: int = 2048, round_size: Optional[int] = None, device=None):
         self.engine = engine
@@ -193,44 +185,17 @@ class Circuit:
         return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(self.device)
 
     def bootstrap(self, lins: Sequence[np.ndarray]) -> List[np.ndarray]:
-        shapes = [tuple(l.shape[:-1]) for l in lins]
-        if self.device is not None:
-            return self._bootstrap_device(lins, shapes)
-        flat = np.concatenate([l.reshape(-1, self.dim) for l in lins], axis=0) if lins else \
-            np.zeros((0, self.dim), np.uint64)
+        """One level: the entries' rows joined, one launch in chunks of MAX_LAUNCH ciphertexts (none, and nothing
+        counted, for a level without rows), the output cut back into the entries' shapes."""
+        if not lins:
+            return []
+        pbs, lut = (self.engine.pbs, self.lut) if self.device is None else (self.engine.pbs_device, self._lut_d)
+        out = flat = _cat([l.reshape(-1, self.dim) for l in lins])
         if flat.shape[0]:
-            # one level = one launch, in chunks of MAX_LAUNCH ciphertexts (euint128 mul levels reach ~10^6)
-            outs = [self.engine.pbs(flat[o:o + MAX_LAUNCH], self.lut) for o in range(0, flat.shape[0], MAX_LAUNCH)]
-            out = outs[0] if len(outs) == 1 else np.concatenate(outs, axis=0)
+            out = chunks(flat.shape[0], MAX_LAUNCH, lambda o, e: pbs(flat[o:e], lut))
             self.pbs_count += flat.shape[0]
             self.launches += 1
-        else:
-            out = flat
-        res, off = [], 0
-        for s in shapes:
-            cnt = int(np.prod(s, dtype=np.int64))
-            res.append(out[off:off + cnt].reshape(s + (self.dim,)))
-            off += cnt
-        return res
-
-    def _bootstrap_device(self, lins, shapes):
-        import torch
-        flat = torch.cat([l.reshape(-1, self.dim) for l in lins], dim=0) if lins else \
-            torch.zeros((0, self.dim), dtype=torch.int64, device=self.device)
-        if flat.shape[0]:
-            outs = [self.engine.pbs_device(flat[o:o + MAX_LAUNCH], self._lut_d)
-                    for o in range(0, flat.shape[0], MAX_LAUNCH)]
-            out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
-            self.pbs_count += flat.shape[0]
-            self.launches += 1
-        else:
-            out = flat
-        res, off = [], 0
-        for sh in shapes:
-            cnt = int(np.prod(sh, dtype=np.int64))
-            res.append(out[off:off + cnt].reshape(sh + (self.dim,)))
-            off += cnt
-        return res
+        return [part.reshape(s + (self.dim,)) for s, part in split(out, [tuple(l.shape[:-1]) for l in lins])]
 
     def oprf(self, row_seeds):
         """Oblivious pseudo-random bits (tfhe-rs ``generate_oblivious_pseudo_random*`` on the gate encoding): (R, 2)
@@ -239,52 +204,24 @@ class Circuit:
         circuit), in chunks of MAX_LAUNCH rows; the masks never exist on the host."""
         seeds = np.ascontiguousarray(np.asarray(row_seeds, dtype=np.uint64)).reshape(-1, 2)
         R = seeds.shape[0]
-        if self.device is not None:
-            import torch
-            d_seeds = torch.from_numpy(seeds.view(np.int64)).to(self.device)
-            d_post = torch.zeros(1, dtype=torch.int64, device=self.device)
-            outs = [self.engine.oprf_device(d_seeds[o:o + MAX_LAUNCH], self._lut_d, d_post)
-                    for o in range(0, R, MAX_LAUNCH)]
-            out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0) if outs else \
-                torch.zeros((0, self.dim), dtype=torch.int64, device=self.device)
+        if not R:
+            return self.trivial(np.zeros((0,), dtype=bool))
+        if self.device is None:
+            oprf, tables = self.engine.oprf, (self.lut, [0])
         else:
-            outs = [self.engine.oprf(seeds[o:o + MAX_LAUNCH], self.lut, [0]) for o in range(0, R, MAX_LAUNCH)]
-            out = outs[0] if len(outs) == 1 else np.concatenate(outs, axis=0) if outs else \
-                np.zeros((0, self.dim), np.uint64)
-        if R:
-            self.pbs_count += R
-            self.launches += 1
+            import torch
+            seeds = torch.from_numpy(seeds.view(np.int64)).to(self.device)
+            oprf, tables = self.engine.oprf_device, (self._lut_d, torch.zeros(1, dtype=torch.int64, device=self.device))
+        out = chunks(R, MAX_LAUNCH, lambda o, e: oprf(seeds[o:e], *tables))
+        self.pbs_count += R
+        self.launches += 1
         return out
 
     def run(self, op: Op):
         return self.run_many([op])[0]
 
     def run_many(self, ops: Sequence[Op]) -> list:
-        results = [None] * len(ops)
-        pending = {}
-        for i, g in enumerate(ops):
-            try:
-                pending[i] = (g, next(g))
-            except StopIteration as e:
-                results[i] = e.value
-        while pending:
-            order = list(pending)
-            lins, counts = [], []
-            for i in order:
-                lvl = pending[i][1]
-                lins.extend(lvl)
-                counts.append(len(lvl))
-            outs = self.bootstrap(lins)
-            off = 0
-            for i, cnt in zip(order, counts):
-                g = pending[i][0]
-                try:
-                    pending[i] = (g, g.send(outs[off:off + cnt]))
-                except StopIteration as e:
-                    results[i] = e.value
-                    del pending[i]
-                off += cnt
-        return results
+        return run_many(self.bootstrap, ops)
 
     def prefer_prefix(self, batch: int, width: int) -> bool:
         """Latency-bound (the level's PBS fit in one launch wave) -> log-depth prefix adder."""

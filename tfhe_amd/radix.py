@@ -24,6 +24,8 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .lockstep import chunks, n_rows, run_many, split
+
 MSG = 4                     # message modulus
 SPACE = 16                  # message x carry
 DELTA = (1 << 63) // SPACE  # one padding bit
@@ -60,7 +62,13 @@ class RadixCircuit:
     buffers and nothing synchronises before ``RadixUint.decrypt`` / ``to_host``.  ``device="cpu"`` is the same
     executor over numpy buffers: it assembles with ``lincomb_ref`` and calls the overridable ``_pbs`` /
     ``_pbs_many`` / ``_oprf``.  Both give the bits of the default host mode (the maps are exact mod 2^64).
-    ``max_terms`` records the most terms any assembled row had."""
+    ``max_terms`` records the most terms any assembled row had.
+
+    All three modes run one level routine, ``_level`` (``oprf`` has the same shape): join the entries' rows, then
+    chunk by chunk  rows -> ``_assemble`` -> ``_run_pbs`` / ``_run_pbs_many`` / ``_run_oprf`` -> ``_wrapped``, and cut
+    the joined output back into the entries' shapes (``tfhe_amd.lockstep``, shared with ``integer.Circuit``).  The
+    constructor binds those steps, ``_const`` (``trivial``) and ``_from_host`` (``_ingest``) once; nothing else asks
+    which mode the circuit is in.  Host mode's steps are identities around the seams, on plain uint64 arrays."""
 
     def __init__(self, engine, many_lut: bool = False, device=None):
         self.engine = engine
@@ -74,19 +82,44 @@ class RadixCircuit:
         self.lazy = device is not None
         self.device = None
         self.max_terms = 0
-        if self.lazy and str(device) != "cpu":
-            import torch
-            if len(getattr(engine, "devices", (0,))) > 1:
-                raise ValueError("a device-resident RadixCircuit takes an engine with one shard")
-            self.device = torch.device(device)
-            self._d_cache: Dict = {}
+        # The mode is chosen here and nowhere else.  Every chunk of a level (and of an oprf call) takes one way,
+        #   rows -> _assemble -> _run_pbs / _run_pbs_many / _run_oprf -> _wrapped,
+        # and what enters a circuit comes from _const (trivial) or _from_host (_ingest).
+        self._run_pbs, self._run_pbs_many, self._run_oprf = self._pbs, self._pbs_many, self._oprf
+        if not self.lazy:
+            # host: block arrays are plain uint64 arrays, and the seams take a level's rows as they are
+            self._const, self._from_host, self._assemble, self._wrapped = self._host_const, _same, _same, _same
+            return
+        self._const = lambda bodies: LinBlocks.const(bodies, self.dim, self._lincomb)
+        self._from_host = lambda host: self.wrap(self._buffer(np.ascontiguousarray(host, dtype=np.uint64)))
+        if str(device) == "cpu":
+            # resident over numpy buffers: lincomb_ref assembles a chunk's rows, then the same seams
+            self._lincomb, self._buffer = lincomb_ref, _same
+            self._assemble = lambda chunk: lincomb_ref(*self._terms(chunk), self.dim)
+            self._wrapped = lambda out: LinBlocks.wrap(np.ascontiguousarray(out, dtype=np.uint64), lincomb_ref)
+            return
+        # resident in HBM: a chunk stays a term description, and the engine assembles and bootstraps it
+        import torch
+        if len(getattr(engine, "devices", (0,))) > 1:
+            raise ValueError("a device-resident RadixCircuit takes an engine with one shard")
+        self.device = torch.device(device)
+        self._d_cache: Dict = {}
+        self._lincomb = engine.lincomb_device
+        self._buffer = lambda host: self._upload(host.view(np.int64))
+        self._assemble = self._terms
+        self._wrapped = lambda out: LinBlocks.wrap(out, self._lincomb)
+        self._run_pbs, self._run_pbs_many, self._run_oprf = self._pbs_device, self._pbs_many_device, self._oprf_device
 
-    # ---- the resident executor (device is not None) -----------------------------------------------------------
-    def _lincomb(self, bufs, row_start, term_buf, term_row, term_coef, bias, dim):
-        """The back end of ``LinBlocks.materialize``: a fresh (rows, dim) buffer where the circuit's buffers live."""
-        if self.device is None:
-            return lincomb_ref(bufs, row_start, term_buf, term_row, term_coef, bias, dim)
-        return self.engine.lincomb_device(bufs, row_start, term_buf, term_row, term_coef, bias, dim)
+    def _host_const(self, bodies: np.ndarray) -> np.ndarray:
+        out = np.zeros(bodies.shape + (self.dim,), dtype=np.uint64)
+        out[..., -1] = bodies
+        return out
+
+    def _terms(self, chunk: "LinBlocks"):
+        """The term description of a chunk's rows (``LinBlocks.terms``); ``max_terms`` keeps the widest row."""
+        desc = chunk.terms()
+        self.max_terms = max(self.max_terms, int(np.diff(desc[1]).max(initial=0)))
+        return desc
 
     def wrap(self, buf) -> "LinBlocks":
         """A (..., dim) buffer of ciphertext words (an int64 torch tensor on the circuit's device; a uint64 numpy
@@ -101,11 +134,9 @@ class RadixCircuit:
 
     def _ingest(self, host: np.ndarray):
         """Host ciphertexts (..., dim) as a block array of this circuit: one upload in device mode."""
-        if not self.lazy:
-            return host
-        host = np.ascontiguousarray(host, dtype=np.uint64)
-        return self.wrap(host if self.device is None else self._upload(host.view(np.int64)))
+        return self._from_host(host)
 
+    # ---- a torch device: uploads, cached LUT stacks, and the level calls that take a term description ----------
     def _upload(self, host: np.ndarray):
         """numpy -> a tensor on the circuit's device through pinned memory, queued on the current stream."""
         import torch
@@ -117,42 +148,40 @@ class RadixCircuit:
             self._d_cache[key] = self._upload(np.ascontiguousarray(build()).view(np.int64))
         return self._d_cache[key]
 
-    def _lin_pbs(self, desc, tables, idx):
-        """A chunk of a level, resident: the rows of the term description ``desc`` (``LinBlocks.terms``) assembled
-        and bootstrapped, row q through tables[idx[q]] -> a (cnt, dim) buffer."""
-        if self.device is None:
-            return self._pbs(lincomb_ref(*desc, self.dim), tables, idx)
+    def _pbs_device(self, desc, tables, idx):
+        """``_pbs`` in HBM: the rows of the term description ``desc`` assembled and bootstrapped in one call."""
         d_luts = self._d_luts(tuple(tables), lambda: np.stack([self.lut(t) for t in tables]))
         return self.engine.lincomb_pbs_device(*desc, d_luts, self._upload(idx.view(np.int32)))
 
-    def _lin_pbs_many(self, desc, table_groups, idx, n_fn: int):
-        """As ``_lin_pbs`` for many-LUT entries -> a (cnt, n_fn, dim) buffer: the assembly is its own launch here
-        (``lincomb_device``), then ``pbs_many_device``."""
-        if self.device is None:
-            return self._pbs_many(lincomb_ref(*desc, self.dim), table_groups, idx, n_fn)
+    def _pbs_many_device(self, desc, table_groups, idx, n_fn: int):
+        """``_pbs_many`` in HBM: the assembly is its own launch here (``lincomb_device``), then ``pbs_many_device``."""
         d_luts = self._d_luts(tuple(table_groups), lambda: np.stack([self.many_lut_of(g) for g in table_groups]))
         lin = self.engine.lincomb_device(*desc, self.dim)
         return self.engine.pbs_many_device(lin, d_luts, n_fn, self.N // n_fn, self._upload(idx.view(np.int32)))
 
-    @staticmethod
-    def _lazy_split(out: "LinBlocks", reqs) -> list:
-        """Per entry (its leading shape, its rows of the level's output)."""
-        res, off = [], 0
-        for a, _ in reqs:
-            cnt = a.bias.size
-            res.append((a.shape[:-1], out[off:off + cnt]))
-            off += cnt
-        return res
+    def _oprf_device(self, seeds, bit_kinds, idx):
+        """``_oprf`` in HBM: the seeds go up (16 bytes a row), the blocks stay on the device."""
+        tabs = [self.oprf_lut(b) for b in bit_kinds]
+        d_luts = self._d_luts(("oprf",) + tuple(bit_kinds), lambda: np.stack([t[0] for t in tabs]))
+        d_post = self._d_luts(("oprf post",) + tuple(bit_kinds),
+                              lambda: np.array([int(t[1]) % _M64 for t in tabs], dtype=np.uint64))
+        return self.engine.oprf_device(self._upload(seeds.view(np.int64)), d_luts, d_post, self._upload(idx.view(np.int32)))
 
-    def _lazy_chunks(self, flat: "LinBlocks", idx: np.ndarray, step: int, run) -> "LinBlocks":
-        """run(term description, idx chunk) -> an output buffer, over chunks of ``step`` rows; the buffers wrapped
-        and joined."""
-        outs = []
-        for o in range(0, flat.shape[0], step):
-            desc = flat[o:o + step].terms()
-            self.max_terms = max(self.max_terms, int(np.diff(desc[1]).max(initial=0)))
-            outs.append(LinBlocks.wrap(run(desc, idx[o:o + step]), self._lincomb))
-        return outs[0] if len(outs) == 1 else np.concatenate(outs, axis=0)
+    # ---- the seams: how a level reaches the engine in host and device="cpu" mode (tests override them) ----------
+    def _pbs(self, flat, tables, idx):
+        """(cnt, dim) -> (cnt, dim): ciphertext q through tables[idx[q]]."""
+        luts = np.stack([self.lut(t) for t in tables])
+        return self.engine.pbs(flat, luts, idx)
+
+    def _pbs_many(self, flat, table_groups, idx, n_fn: int):
+        """(cnt, dim) -> (cnt, n_fn, dim): ciphertext q through the many-LUT of table_groups[idx[q]]."""
+        luts = np.stack([self.many_lut_of(g) for g in table_groups])
+        return self.engine.pbs_many(flat, luts, n_fn, self.N // n_fn, idx)
+
+    def _oprf(self, seeds, bit_kinds, idx):
+        """(cnt, 2) -> (cnt, dim): row q gets ``bit_kinds[idx[q]]`` random bits."""
+        tabs = [self.oprf_lut(b) for b in bit_kinds]
+        return self.engine.oprf(seeds, np.stack([t[0] for t in tabs]), [t[1] for t in tabs], idx)
 
     def lut(self, table: Tuple[int, ...]) -> np.ndarray:
         if table not in self._luts:
@@ -160,113 +189,11 @@ class RadixCircuit:
             self._luts[table] = lut_from_table(self.N, SPACE, list(table), DELTA)
         return self._luts[table]
 
-    # encodings
-    def trivial(self, vals) -> np.ndarray:
-        v = np.asarray(vals, dtype=np.uint64)
-        if self.lazy:
-            return LinBlocks.const((v % np.uint64(SPACE)) * np.uint64(DELTA), self.dim, self._lincomb)
-        out = np.zeros(v.shape + (self.dim,), dtype=np.uint64)
-        with np.errstate(over="ignore"):
-            out[..., -1] = (v % np.uint64(SPACE)) * np.uint64(DELTA)
-        return out
-
-    def bootstrap(self, reqs: Sequence[Tuple[np.ndarray, Tuple[int, ...]]]) -> list:
-        if not reqs:
-            return []
-        many = [i for i, (_, t) in enumerate(reqs) if isinstance(t[0], tuple)]
-        if not many:
-            res = self._bootstrap_single(reqs)
-        else:
-            res = [None] * len(reqs)
-            single = [i for i in range(len(reqs)) if i not in set(many)]
-            if single:
-                for i, r in zip(single, self._bootstrap_single([reqs[i] for i in single])):
-                    res[i] = r
-            for n_fn in sorted({len(reqs[i][1]) for i in many}):
-                grp = [i for i in many if len(reqs[i][1]) == n_fn]
-                for i, r in zip(grp, self._bootstrap_many([reqs[i] for i in grp], n_fn)):
-                    res[i] = r
-        self.launches += 1
-        return res
-
-    def _bootstrap_many(self, reqs, n_fn: int) -> List[Tuple[np.ndarray, ...]]:
-        """The many-LUT entries of one level with n_fn tables each: one `_pbs_many` call (in chunks of
-        MAX_LAUNCH outputs); a tuple of n_fn arrays per entry."""
-        groups, index, idx_parts, flat_parts = [], {}, [], []
-        for a, ts in reqs:
-            if any(len(t) * n_fn != SPACE for t in ts):
-                raise ValueError(f"a many-LUT entry of {n_fn} tables takes tables of {SPACE // n_fn} entries")
-            if ts not in index:
-                index[ts] = len(groups)
-                groups.append(ts)
-            cnt = int(np.prod(a.shape[:-1], dtype=np.int64))
-            flat_parts.append(a.reshape(cnt, self.dim))
-            idx_parts.append(np.full(cnt, index[ts], dtype=np.uint32))
-        flat = np.concatenate(flat_parts, axis=0)
-        idx = np.concatenate(idx_parts)
-        step = max(1, MAX_LAUNCH // n_fn)
-        if self.lazy:
-            out = self._lazy_chunks(flat, idx, step, lambda desc, i: self._lin_pbs_many(desc, groups, i, n_fn))
-            self.pbs_count += flat.shape[0]
-            return [tuple(part[:, f].reshape(s + (self.dim,)) for f in range(n_fn))
-                    for s, part in self._lazy_split(out, reqs)]
-        outs = [self._pbs_many(flat[o:o + step], groups, idx[o:o + step], n_fn) for o in range(0, flat.shape[0], step)]
-        out = outs[0] if len(outs) == 1 else np.concatenate(outs, axis=0)
-        self.pbs_count += flat.shape[0]
-        res, off = [], 0
-        for a, _ in reqs:
-            s = a.shape[:-1]
-            cnt = int(np.prod(s, dtype=np.int64))
-            res.append(tuple(out[off:off + cnt, f].reshape(s + (self.dim,)) for f in range(n_fn)))
-            off += cnt
-        return res
-
-    def _pbs_many(self, flat, table_groups, idx, n_fn: int):
-        """(cnt, dim) -> (cnt, n_fn, dim): ciphertext q through the many-LUT of table_groups[idx[q]]."""
-        luts = np.stack([self.many_lut_of(g) for g in table_groups])
-        return self.engine.pbs_many(flat, luts, n_fn, self.N // n_fn, idx)
-
     def many_lut_of(self, group: Tuple[Tuple[int, ...], ...]) -> np.ndarray:
         if group not in self._luts:
             from . import lut_many
             self._luts[group] = lut_many(self.N, SPACE, [list(t) for t in group], DELTA)[0]
         return self._luts[group]
-
-    def _bootstrap_single(self, reqs: Sequence[Tuple[np.ndarray, Tuple[int, ...]]]) -> List[np.ndarray]:
-        shapes = [a.shape[:-1] for a, _ in reqs]
-        tables = []
-        index = {}
-        idx_parts = []
-        flat_parts = []
-        for a, t in reqs:
-            if t not in index:
-                index[t] = len(tables)
-                tables.append(t)
-            cnt = int(np.prod(a.shape[:-1], dtype=np.int64))
-            flat_parts.append(a.reshape(cnt, self.dim))
-            idx_parts.append(np.full(cnt, index[t], dtype=np.uint32))
-        flat = np.concatenate(flat_parts, axis=0)
-        idx = np.concatenate(idx_parts)
-        if self.lazy:
-            out = self._lazy_chunks(flat, idx, MAX_LAUNCH, lambda desc, i: self._lin_pbs(desc, tables, i))
-            self.pbs_count += flat.shape[0]
-            return [part.reshape(s + (self.dim,)) for s, part in self._lazy_split(out, reqs)]
-        # one level = one launch; levels of wide operators (euint128 mul: ~10^5 PBS per operand pair) go in
-        # chunks of MAX_LAUNCH ciphertexts so host and device staging stay bounded
-        outs = [self._pbs(flat[o:o + MAX_LAUNCH], tables, idx[o:o + MAX_LAUNCH])
-                for o in range(0, flat.shape[0], MAX_LAUNCH)]
-        out = outs[0] if len(outs) == 1 else np.concatenate(outs, axis=0)
-        self.pbs_count += flat.shape[0]
-        res, off = [], 0
-        for s in shapes:
-            cnt = int(np.prod(s, dtype=np.int64))
-            res.append(out[off:off + cnt].reshape(s + (self.dim,)))
-            off += cnt
-        return res
-
-    def _pbs(self, flat, tables, idx):
-        luts = np.stack([self.lut(t) for t in tables])
-        return self.engine.pbs(flat, luts, idx)
 
     def oprf_lut(self, random_bits: int):
         """(lut, post_add) of ``random_bits`` uniform bits in a block of this encoding (``lut_oprf``), cached."""
@@ -275,6 +202,57 @@ class RadixCircuit:
             from . import lut_oprf
             self._luts[key] = lut_oprf(self.N, int(random_bits), FULL_BITS)
         return self._luts[key]
+
+    # encodings
+    def trivial(self, vals) -> np.ndarray:
+        v = np.asarray(vals, dtype=np.uint64)
+        return self._const((v % np.uint64(SPACE)) * np.uint64(DELTA))
+
+    # ---- levels ---------------------------------------------------------------------------------------------------
+    def bootstrap(self, reqs: Sequence[Tuple[np.ndarray, Tuple[int, ...]]]) -> list:
+        """One level: the ordinary entries first, then the many-LUT entries grouped by ascending n_fn, each group
+        one ``_level``; the results in request order."""
+        if not reqs:
+            return []
+        kinds = [len(t) if isinstance(t[0], tuple) else 0 for _, t in reqs]
+        if not any(kinds):
+            res = self._level(reqs)
+        else:
+            res = [None] * len(reqs)
+            for n_fn in sorted(set(kinds)):
+                grp = [i for i, k in enumerate(kinds) if k == n_fn]
+                for i, r in zip(grp, self._level([reqs[i] for i in grp], n_fn or None)):
+                    res[i] = r
+        self.launches += 1
+        return res
+
+    def _level(self, reqs, n_fn: Optional[int] = None) -> list:
+        """The entries of one level that take ``n_fn`` tables each (None: ordinary entries, one table each): every
+        distinct table (group) becomes one LUT and each row indexes its own, the rows go through ``_pbs`` in chunks
+        of MAX_LAUNCH (``_pbs_many`` in chunks of MAX_LAUNCH outputs), and every entry gets its leading shape back:
+        an array, or for a many-LUT entry a tuple of n_fn arrays."""
+        tables, index, idx_parts, flat_parts = [], {}, [], []
+        for a, t in reqs:
+            if n_fn and any(len(f) * n_fn != SPACE for f in t):
+                raise ValueError(f"a many-LUT entry of {n_fn} tables takes tables of {SPACE // n_fn} entries")
+            if t not in index:
+                index[t] = len(tables)
+                tables.append(t)
+            cnt = n_rows(a.shape[:-1])
+            flat_parts.append(a.reshape(cnt, self.dim))
+            idx_parts.append(np.full(cnt, index[t], dtype=np.uint32))
+        flat = np.concatenate(flat_parts, axis=0)
+        idx = np.concatenate(idx_parts)
+        if n_fn:
+            step, run = max(1, MAX_LAUNCH // n_fn), lambda lin, i: self._run_pbs_many(lin, tables, i, n_fn)
+        else:
+            step, run = MAX_LAUNCH, lambda lin, i: self._run_pbs(lin, tables, i)
+        out = chunks(flat.shape[0], step, lambda o, e: self._wrapped(run(self._assemble(flat[o:e]), idx[o:e])))
+        self.pbs_count += flat.shape[0]
+        parts = split(out, [a.shape[:-1] for a, _ in reqs])
+        if n_fn:
+            return [tuple(part[:, f].reshape(s + (self.dim,)) for f in range(n_fn)) for s, part in parts]
+        return [part.reshape(s + (self.dim,)) for s, part in parts]
 
     def oprf(self, row_seeds, random_bits) -> np.ndarray:
         """Oblivious pseudo-random blocks (tfhe-rs ``generate_oblivious_pseudo_random*``): (R, 2) row seeds -> (R, dim)
@@ -286,57 +264,20 @@ class RadixCircuit:
             return self.trivial(np.zeros((0,), dtype=np.uint64))
         kinds = sorted({int(b) for b in rb})
         idx = np.searchsorted(np.array(kinds), rb).astype(np.uint32)
-        run = self._oprf_resident if self.lazy else self._oprf
-        outs = [run(seeds[o:o + MAX_LAUNCH], kinds, idx[o:o + MAX_LAUNCH])
-                for o in range(0, seeds.shape[0], MAX_LAUNCH)]
+        out = chunks(seeds.shape[0], MAX_LAUNCH, lambda o, e: self._wrapped(self._run_oprf(seeds[o:e], kinds, idx[o:e])))
         self.pbs_count += seeds.shape[0]
         self.launches += 1
-        return outs[0] if len(outs) == 1 else np.concatenate(outs, axis=0)
-
-    def _oprf(self, seeds, bit_kinds, idx):
-        """(cnt, 2) -> (cnt, dim): row q gets ``bit_kinds[idx[q]]`` random bits."""
-        tabs = [self.oprf_lut(b) for b in bit_kinds]
-        return self.engine.oprf(seeds, np.stack([t[0] for t in tabs]), [t[1] for t in tabs], idx)
-
-    def _oprf_resident(self, seeds, bit_kinds, idx) -> "LinBlocks":
-        """``_oprf`` of a resident circuit: the seeds go up (16 bytes a row), the blocks stay on the device."""
-        if self.device is None:
-            return self.wrap(np.ascontiguousarray(self._oprf(seeds, bit_kinds, idx), dtype=np.uint64))
-        tabs = [self.oprf_lut(b) for b in bit_kinds]
-        d_luts = self._d_luts(("oprf",) + tuple(bit_kinds), lambda: np.stack([t[0] for t in tabs]))
-        d_post = self._d_luts(("oprf post",) + tuple(bit_kinds),
-                              lambda: np.array([int(t[1]) % _M64 for t in tabs], dtype=np.uint64))
-        out = self.engine.oprf_device(self._upload(seeds.view(np.int64)), d_luts, d_post, self._upload(idx.view(np.int32)))
-        return self.wrap(out)
+        return out
 
     def run(self, op):
         return self.run_many([op])[0]
 
     def run_many(self, ops) -> list:
-        results = [None] * len(ops)
-        pending = {}
-        for i, g in enumerate(ops):
-            try:
-                pending[i] = (g, next(g))
-            except StopIteration as e:
-                results[i] = e.value
-        while pending:
-            order = list(pending)
-            reqs, counts = [], []
-            for i in order:
-                reqs.extend(pending[i][1])
-                counts.append(len(pending[i][1]))
-            outs = self.bootstrap(reqs)
-            off = 0
-            for i, cnt in zip(order, counts):
-                g = pending[i][0]
-                try:
-                    pending[i] = (g, g.send(outs[off:off + cnt]))
-                except StopIteration as e:
-                    results[i] = e.value
-                    del pending[i]
-                off += cnt
-        return results
+        return run_many(self.bootstrap, ops)
+
+
+def _same(x):
+    return x
 
 
 # --------------------------------------------------------------------------------------------
