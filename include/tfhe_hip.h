@@ -612,6 +612,80 @@ int tfhe_hip_sns_pks_extract(const tfhe_sns_pks_params* pp, const uint64_t* pack
 /* client-side decryption of a 128-bit GLWE: body - sum_c mask_c * S_c -> [lo][N], [hi][N] */
 int tfhe_hip_glwe_phase128(uint32_t k, uint32_t N, const uint64_t* key, const uint64_t* glwe, uint64_t* out);
 
+/* ---- encrypted matrix x clear matrix (the front half of the compression path) ------------------
+ * Replaces the reference's GLWE x clear-matrix product (ml/extensions/rust/src: driver lib_python.rs:243-337
+ * cuda_matrix_multiplication, CPU twin :340-401; ml.rs:66-90 cuda_glwe_dot_product_with_clear_one_to_many and the
+ * LWE accumulate; rule computations.rs:80-132, encryption.rs:5-174, ml.rs:95-121).  All arithmetic is mod 2^64,
+ * GLWE dimension 1.  Kernels tfhe_amd/csrc/matmul.hip, host client code tfhe_amd/csrc/seeded.cpp.
+ *   encode   (encryption.rs:5-40)  plaintext = v * 2^(64 - bits_reserved), v a signed integer mod 2^64
+ *   encrypt  (ml.rs:131-189, encryption.rs:88-133, compression.rs:59-105)  a row of the matrix is cut into chunks of
+ *            N (the caller zero-pads the last); chunk g is one seeded GLWE: mask = words 0 .. N-1 of the AES-CTR
+ *            stream of seed g (tfhe_hip_csprng_words(seed, 0, N)), body = A*S + e + plaintext, then the body alone
+ *            is switched to in_storage_log bits, (((x >> (64-w-1)) + 1) >> 1) & (2^w - 1) (w = 64: unchanged), and
+ *            bit-packed LSB first; every GLWE's body starts on a word boundary and takes
+ *            tfhe_hip_matmul_body_words() words
+ *   expand   (compression.rs:110-128, ml.rs:191-205)  body value << (64 - in_storage_log), mask from the seed
+ *   dot      for row r, column c and K-blocks kb < Kb = ceil(K / N), w_kb[t] = W[kb N + t][c] (zero past K): the
+ *            reference accumulates glwe_{r,kb} * reverse(w_kb) (negacyclic) and sample-extracts coefficient N-1;
+ *            in closed form the output LWE (dimension N, under the GLWE key read as an LWE key) is
+ *              mask[i] = sum_kb sum_t w_kb[t] * a'_{r,kb}[t - i],  a'[d] = a[d] (d >= 0), -a[N + d] (d < 0)
+ *              body    = sum_kb sum_t w_kb[t] * b_{r,kb}[t]
+ *   decode   (encryption.rs:135-174)  closest representable of the phase at bits_reserved bits, / delta, mod 2^b;
+ *            values >= 2^(b-1) are negative
+ * The C LWEs of one encrypted row then go through tfhe_hip_pks_pack_async (pks in_dim = N) in groups of
+ * lwe_per_glwe that never straddle two rows, and tfhe_hip_pks_compress with `bodies` = the group's real count
+ * (compression.rs:263-289).  PARITY UNPINNED at the byte level, as every seeded path here (the reference mount
+ * holds no tfhe-rs). */
+typedef struct tfhe_matmul_params {
+  uint32_t N, bits_reserved, in_storage_log;
+  int32_t noise_log2;
+} tfhe_matmul_params;
+/* N 2048, 27 bits reserved, bodies stored on 39 bits, noise 2^-48 (fhext_classes.rs:99-112, the rounding of the
+ * reference's standard deviation that TFHE_HIP_PKS_PRESET_ML2048 uses) */
+#define TFHE_HIP_MATMUL_PRESET_ML2048 0
+int tfhe_hip_matmul_params_preset(int preset, tfhe_matmul_params* out);
+/* Valid: N a power of two in 64 .. 4096, 1 <= bits_reserved <= 63, 1 <= in_storage_log <= 64, -64 < noise_log2 < 0;
+ * every call below returns EINVAL otherwise, before any device work. */
+size_t tfhe_hip_matmul_body_words(const tfhe_matmul_params* mp); /* ceil(N * in_storage_log / 64); 0 if invalid */
+/* Host, no GPU.  keygen: N key bits from ChaCha stream 7 of the rng key.  encrypt: G GLWEs, values G x N (signed,
+ * padded by the caller), seeds G x 2, packed_out G x body_words; the noise of GLWE g comes from ChaCha stream
+ * stream0 + g.  expand_host: glwes_out G x 2 x N.  dot_host: the closed form above on the CPU, the layouts of
+ * tfhe_hip_matmul_dot.  decode: count phases -> signed values. */
+int tfhe_hip_matmul_keygen_k(const tfhe_matmul_params* mp, const tfhe_rng_key* rk, uint64_t* glwe_key);
+int tfhe_hip_matmul_encrypt_k(const tfhe_matmul_params* mp, const uint64_t* glwe_key, const tfhe_rng_key* rk,
+                              uint64_t stream0, const uint64_t* seeds, const int64_t* values, size_t G,
+                              uint64_t* packed_out);
+int tfhe_hip_matmul_expand_host(const tfhe_matmul_params* mp, const uint64_t* seeds, const uint64_t* packed, size_t G,
+                                uint64_t* glwes_out);
+int tfhe_hip_matmul_dot_host(const tfhe_matmul_params* mp, const int32_t* w, size_t K, size_t C, const uint64_t* glwes,
+                             size_t R, size_t col_stride, uint64_t* lwes_out);
+int tfhe_hip_matmul_decode(const tfhe_matmul_params* mp, const uint64_t* phases, size_t count, int64_t* out);
+typedef struct tfhe_matmul_ctx tfhe_matmul_ctx;
+typedef struct tfhe_matmul_matrix tfhe_matmul_matrix;
+int tfhe_hip_matmul_create(const tfhe_matmul_params* mp, int device, tfhe_matmul_ctx** out);
+/* Waits for every call still in flight on the ctx, on a caller's stream too.  Destroy the ctx's matrices first. */
+void tfhe_hip_matmul_destroy(tfhe_matmul_ctx* ctx);
+/* A clear matrix w (K x C, row-major, K >= 1, C >= 1) uploaded once and kept resident; a ctx may hold many.  destroy
+ * waits for the calls in flight on the ctx before it frees the matrix. */
+int tfhe_hip_matmul_matrix_create(tfhe_matmul_ctx* ctx, const int32_t* w, size_t K, size_t C, tfhe_matmul_matrix** out);
+void tfhe_hip_matmul_matrix_destroy(tfhe_matmul_matrix* m);
+/* Device buffers, enqueued on `stream` (NULL = the ctx stream, TFHE_HIP_NULL_STREAM = the null stream); calls on
+ * different streams are ordered by an event as tfhe_hip_pks_pack_async orders its own, so a call may follow another
+ * at once on any stream.  expand: d_seeds G x 2, d_packed G x body_words -> d_glwes G x 2 x N.  dot: d_glwes
+ * R x Kb x 2 x N (Kb = ceil(K / N) of the matrix) -> LWE c of row r at d_lwes_out + (r * col_stride + c) * (N + 1),
+ * col_stride >= C; the LWEs C .. col_stride - 1 of a row are not written (a caller that zero-fills them once can pack
+ * all R rows in one tfhe_hip_pks_pack_async with col_stride a multiple of lwe_per_glwe: a zero LWE adds nothing to
+ * its GLWE).  G == 0 / R == 0 return OK.  The forms without _async take host buffers and are synchronous; the host
+ * dot reads lwes_out first, so the unwritten LWEs keep the caller's words. */
+int tfhe_hip_matmul_expand_async(tfhe_matmul_ctx* ctx, const uint64_t* d_seeds, const uint64_t* d_packed, size_t G,
+                                 uint64_t* d_glwes, void* stream);
+int tfhe_hip_matmul_expand(tfhe_matmul_ctx* ctx, const uint64_t* seeds, const uint64_t* packed, size_t G,
+                           uint64_t* glwes_out);
+int tfhe_hip_matmul_dot_async(tfhe_matmul_ctx* ctx, const tfhe_matmul_matrix* m, const uint64_t* d_glwes, size_t R,
+                              size_t col_stride, uint64_t* d_lwes_out, void* stream);
+int tfhe_hip_matmul_dot(tfhe_matmul_ctx* ctx, const tfhe_matmul_matrix* m, const uint64_t* glwes, size_t R,
+                        size_t col_stride, uint64_t* lwes_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,10 @@ ABI_SYMBOLS = (
     "tfhe_hip_sns_pks_compress", "tfhe_hip_sns_pks_extract", "tfhe_hip_glwe_phase128",
     "tfhe_hip_lut_oprf", "tfhe_hip_csprng_rows", "tfhe_hip_csprng_rows_async", "tfhe_hip_oprf", "tfhe_hip_oprf_async",
     "tfhe_hip_lwe_lincomb", "tfhe_hip_lwe_lincomb_async", "tfhe_hip_lincomb_pbs_async",
+    "tfhe_hip_matmul_params_preset", "tfhe_hip_matmul_body_words", "tfhe_hip_matmul_keygen_k", "tfhe_hip_matmul_encrypt_k",
+    "tfhe_hip_matmul_expand_host", "tfhe_hip_matmul_dot_host", "tfhe_hip_matmul_decode", "tfhe_hip_matmul_create",
+    "tfhe_hip_matmul_destroy", "tfhe_hip_matmul_matrix_create", "tfhe_hip_matmul_matrix_destroy",
+    "tfhe_hip_matmul_expand_async", "tfhe_hip_matmul_expand", "tfhe_hip_matmul_dot_async", "tfhe_hip_matmul_dot",
 )
 
 # P-FHEVM modulus-switch noise reduction key (include/tfhe_hip.h TFHE_HIP_MS_FHEVM_*)

@@ -13,6 +13,9 @@ The return half (tfhe-rs CompressedCiphertextList::get / DecompressionKey::unpac
   DecompressionKey(compute_params, pks_params, post_packing_key, glwe_key, seed) -> a BSK, no KSK
   Decompressor(dk).decompress([CompressedGlwe]) -> LWEs under the compute GLWE key
 (unpack + sample extraction: tfhe_amd/csrc/decompress.hip; then a PBS without keyswitch on a BSK-only engine).
+
+The front half, which produces the LWEs that ``Packer`` consumes (the reference's encrypted matrix x clear matrix
+product), is ``tfhe_amd.matmul``.
 """
 from __future__ import annotations
 

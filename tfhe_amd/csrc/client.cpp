@@ -255,6 +255,11 @@ void noise_words(const tfhe_rng_key& rk, uint64_t stream, int32_t log2_sigma, si
   for (size_t i = 0; i < count; i++) out[i] = r.gauss(log2_sigma);
 }
 
+void binary_key(const tfhe_rng_key& rk, uint64_t stream, size_t count, uint64_t* out) {
+  ChaCha r(rk, stream);
+  for (size_t i = 0; i < count; i++) out[i] = r.next() & 1;
+}
+
 void lwe_encrypt(uint32_t dim, const uint64_t* key, int32_t noise_log2, const tfhe_rng_key& rk, uint64_t stream0,
                  const uint64_t* msgs, size_t count, uint64_t* out) {
   auto one = [&](int64_t q) {

@@ -45,6 +45,7 @@ size_t sns_pks_packed_words(const tfhe_sns_pks_params& pp, uint32_t bodies);
 void sns_pks_compress(const tfhe_sns_pks_params& pp, const uint64_t* glwe, uint32_t bodies, uint64_t* packed);
 void sns_pks_extract(const tfhe_sns_pks_params& pp, const uint64_t* packed, uint32_t bodies, uint64_t* glwe);
 void glwe_phase128(uint32_t k, uint32_t N, const uint64_t* key, const uint64_t* glwe, uint64_t* out);
+void binary_key(const tfhe_rng_key& rk, uint64_t stream, size_t count, uint64_t* out);  // count bits of one ChaCha stream
 }  // namespace client
 
 // compressed (seeded) server keys (seeded.cpp)
@@ -59,5 +60,13 @@ void seeded_lwe_list(uint32_t dim, uint32_t count, const uint64_t* key, int32_t 
 void decompress_bsk(const tfhe_params& p, const uint64_t seed[2], const uint64_t* bodies, uint64_t* bsk);
 void decompress_ksk(const tfhe_params& p, const uint64_t seed[2], const uint64_t* bodies, uint64_t* ksk);
 void decompress_lwe_list(uint32_t dim, uint32_t count, const uint64_t seed[2], const uint64_t* bodies, uint64_t* out);
+// encrypted matrix x clear matrix, client and CPU side (include/tfhe_hip.h tfhe_hip_matmul_*)
+size_t matmul_body_words(const tfhe_matmul_params& mp);
+void matmul_encrypt(const tfhe_matmul_params& mp, const uint64_t* glwe_key, const tfhe_rng_key& rk, uint64_t stream0,
+                    const uint64_t* seeds, const int64_t* values, size_t G, uint64_t* packed);
+void matmul_expand(const tfhe_matmul_params& mp, const uint64_t* seeds, const uint64_t* packed, size_t G, uint64_t* glwes);
+void matmul_dot(const tfhe_matmul_params& mp, const int32_t* w, size_t K, size_t C, const uint64_t* glwes, size_t R,
+                size_t col_stride, uint64_t* lwes);
+void matmul_decode(const tfhe_matmul_params& mp, const uint64_t* phases, size_t count, int64_t* out);
 }  // namespace seeded
 }  // namespace tfhe

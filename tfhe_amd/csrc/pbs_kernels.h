@@ -123,6 +123,13 @@ hipError_t launch_expand_compact(const u64* list, size_t count, int lwe_dim, int
 // rows * ceil(dim / 1022) <= 0x7FFFFFFF (hipErrorInvalidValue otherwise); rows == 0 or dim == 0 launches nothing
 hipError_t launch_csprng_rows(const u64* seeds, size_t rows, u64 first_word, u32 dim, size_t row_stride,
                               bool zero_body, u64* out, hipStream_t s);
+// ---- matmul.hip: encrypted matrix x clear matrix.  expand: G seeded GLWEs (seeds G x 2, packed G x ceil(N w / 64)
+// words of w-bit body values) -> glwes G x 2 x N.  dot: glwes R x Kb x 2 x N times the resident matrix W (Kb N x Cpad
+// u32, value + 2^31, zero = 2^31 past K and past C) -> LWE c < C of row r at out + (r * col_stride + c) * (N + 1).
+// N and Cpad multiples of 64, Cpad / 64 <= 65535, C <= Cpad, col_stride >= C (hipErrorInvalidValue otherwise)
+hipError_t launch_matmul_expand(const u64* seeds, const u64* packed, size_t G, int N, int w, u64* glwes, hipStream_t s);
+hipError_t launch_matmul_dot(const u64* glwes, const u32* W, size_t R, int N, int Kb, int Cpad, int C, size_t col_stride,
+                             u64* out, hipStream_t s);
 // body (last word) of row r of rows x row_len += post_add[idx ? idx[r] : 0]
 hipError_t launch_body_add(u64* lwes, size_t rows, size_t row_len, const u64* post_add, size_t n_lut, const u32* idx,
                            hipStream_t s);

@@ -289,5 +289,90 @@ void decompress_lwe_list(uint32_t dim, uint32_t count, const uint64_t seed[2], c
   });
 }
 
+// ------------------------------------------------- encrypted matrix x clear matrix: client and CPU side
+// The conventions of include/tfhe_hip.h (tfhe_hip_matmul_*), restated from the reference: encode encryption.rs:5-40,
+// seeded encryption ml.rs:131-189 / encryption.rs:88-133, storage switch and packing compression.rs:59-105, expansion
+// compression.rs:110-128, product and extraction computations.rs:80-132 / ml.rs:95-121, decode encryption.rs:135-174.
+// PARITY UNPINNED at the byte level, as the seeded keys above.
+size_t matmul_body_words(const tfhe_matmul_params& mp) { return ((size_t)mp.N * mp.in_storage_log + 63) / 64; }
+
+void matmul_encrypt(const tfhe_matmul_params& mp, const uint64_t* glwe_key, const tfhe_rng_key& rk, uint64_t stream0,
+                    const uint64_t* seeds, const int64_t* values, size_t G, uint64_t* packed) {
+  const uint32_t N = mp.N, w = mp.in_storage_log;
+  const size_t bw = matmul_body_words(mp);
+  const uint64_t vmask = (w == 64) ? ~0ull : ((1ull << w) - 1);
+  parallel_for((int64_t)G, [&](int64_t g) {
+    uint8_t kb[16];
+    key_bytes(seeds + 2 * g, kb);
+    const Aes128 aes(kb);
+    std::vector<uint64_t> mask(N), body(N);
+    std::vector<int64_t> e(N);
+    mask_words(aes, 0, N, mask.data());
+    client::noise_words(rk, stream0 + (uint64_t)g, mp.noise_log2, N, e.data());
+    for (uint32_t t = 0; t < N; t++)
+      body[t] = (uint64_t)e[t] + ((uint64_t)values[(size_t)g * N + t] << (64 - mp.bits_reserved));
+    add_product(N, mask.data(), glwe_key, body.data());
+    uint64_t* out = packed + (size_t)g * bw;
+    memset(out, 0, bw * 8);
+    for (uint32_t t = 0; t < N; t++) {
+      const uint64_t x = body[t];
+      const uint64_t ms = (w == 64) ? x : ((((x >> (64 - w - 1)) + 1) >> 1) & vmask);
+      const size_t bit = (size_t)t * w, word = bit >> 6, off = bit & 63;
+      out[word] |= ms << off;
+      if (off + w > 64) out[word + 1] |= ms >> (64 - off);
+    }
+  });
+}
+
+void matmul_expand(const tfhe_matmul_params& mp, const uint64_t* seeds, const uint64_t* packed, size_t G, uint64_t* glwes) {
+  const uint32_t N = mp.N, w = mp.in_storage_log;
+  const size_t bw = matmul_body_words(mp);
+  parallel_for((int64_t)G, [&](int64_t g) {
+    uint8_t kb[16];
+    key_bytes(seeds + 2 * g, kb);
+    const Aes128 aes(kb);
+    uint64_t* o = glwes + (size_t)g * 2 * N;
+    mask_words(aes, 0, N, o);
+    const uint64_t* p = packed + (size_t)g * bw;
+    for (uint32_t t = 0; t < N; t++) {
+      const size_t bit = (size_t)t * w, word = bit >> 6, off = bit & 63;
+      uint64_t v = p[word] >> off;
+      if (off + w > 64) v |= p[word + 1] << (64 - off);
+      o[N + t] = v << (64 - w);
+    }
+  });
+}
+
+// one (row, column) per task: mask[i] = sum_kb sum_t w[t] a'[t - i] as t loops over shifted copies of a
+void matmul_dot(const tfhe_matmul_params& mp, const int32_t* w, size_t K, size_t C, const uint64_t* glwes, size_t R,
+                size_t col_stride, uint64_t* lwes) {
+  const size_t N = mp.N, Kb = (K + N - 1) / N;
+  parallel_for((int64_t)(R * C), [&](int64_t rc) {
+    const size_t r = (size_t)rc / C, c = (size_t)rc % C;
+    uint64_t* o = lwes + (r * col_stride + c) * (N + 1);
+    memset(o, 0, (N + 1) * 8);
+    for (size_t kb = 0; kb < Kb; kb++) {
+      const uint64_t* a = glwes + (r * Kb + kb) * 2 * N;
+      const uint64_t* b = a + N;
+      for (size_t t = 0; t < N && kb * N + t < K; t++) {
+        const uint64_t wt = (uint64_t)(int64_t)w[(kb * N + t) * C + c];
+        if (!wt) continue;
+        for (size_t i = 0; i <= t; i++) o[i] += wt * a[t - i];
+        for (size_t i = t + 1; i < N; i++) o[i] -= wt * a[N + t - i];
+        o[N] += wt * b[t];
+      }
+    }
+  });
+}
+
+void matmul_decode(const tfhe_matmul_params& mp, const uint64_t* phases, size_t count, int64_t* out) {
+  const uint32_t b = mp.bits_reserved;
+  const uint64_t mod_mask = (1ull << b) - 1, half = 1ull << (b - 1);
+  for (size_t i = 0; i < count; i++) {
+    const uint64_t v = (((phases[i] >> (64 - b - 1)) + 1) >> 1) & mod_mask;
+    out[i] = (int64_t)(v >= half ? v - (1ull << b) : v);
+  }
+}
+
 }  // namespace seeded
 }  // namespace tfhe
