@@ -45,6 +45,7 @@ extern "C" {
 #define TFHE_HIP_PRESET_FHEVM 1  /* n=918 k=1 N=2048, PBS 23x1, KS 4x4 (PARAM_MESSAGE_2_CARRY_2_KS_PBS) */
 #define TFHE_HIP_PRESET_GATE_FFT 2 /* P-GATE on the FFT64 transform (native-torus BSK, f64 FFT) */
 #define TFHE_HIP_PRESET_FHEVM_FFT 3 /* P-FHEVM on the FFT64 transform (N = 2048 as two 512-point halves) */
+#define TFHE_HIP_PRESET_FHEVM_MB_FFT 4 /* preset 3 with n = 924 (divisible by 2, 3 and 4): multi-bit PBS keys */
 
 #define TFHE_HIP_TRANSFORM_NTT 0   /* GLWE/BSK over Z_p, Goldilocks NTT (exact integer arithmetic) */
 #define TFHE_HIP_TRANSFORM_FFT64 1 /* GLWE/BSK over Z_2^64, f64 FFT (tfhe-rs FFT64; oracle/fft_oracle.c) */
@@ -72,7 +73,8 @@ uint32_t tfhe_hip_io_dim(const tfhe_params* p);
 /* ---- client-side key material (host) ------------------------------------------------------
  * Replaces TfheClientKey.generate / ServerKey generation (sdk/relayer/src/tfhe.ts:20-28,
  * generateKeys.js:20-31).  All randomness is ChaCha20 keyed by a 192-bit rng key plus a stream index
- * (LWE key 1, GLWE key 2, BSK_i 0x1000+i, KSK_j 0x100000+j, MS zero z 0x200000+z, ciphertext q stream0+q).
+ * (LWE key 1, GLWE key 2, BSK_i 0x1000+i, KSK_j 0x100000+j, MS zero z 0x200000+z, multi-bit GGSW (q, sigma)
+ * 0x600000 + 16 q + sigma, ciphertext q stream0+q).
  *   - tfhe_hip_rng_key_entropy: 192 bits from the OS (getrandom) -- production keys and encryptions;
  *   - tfhe_hip_rng_key_from_seed: (seed, a public tag) -- REPRODUCIBLE streams for tests, golden vectors
  *     and the oracle.  A seeded key set is public knowledge: never use one for real data.
@@ -93,6 +95,25 @@ int tfhe_hip_server_keygen_k(const tfhe_params* p, const tfhe_rng_key* rk, const
                              const uint64_t* glwe_key, uint64_t* bsk /* nullable */, uint64_t* ksk /* nullable */);
 int tfhe_hip_server_keygen(const tfhe_params* p, uint64_t seed, const uint64_t* lwe_key, const uint64_t* glwe_key,
                            uint64_t* bsk /* nullable */, uint64_t* ksk /* nullable */);
+/* ---- multi-bit PBS keys (tfhe-rs LweMultiBitBootstrapKey; PARITY UNPINNED at the byte level) ------------------
+ * The grouping factor g in {2, 3, 4} belongs to the key, not to tfhe_params; n % g == 0.  Scope: the FFT64
+ * transform, k = 1, N = 2048, PBS gadget 2^23 x 1 (the shape of presets 3 and 4); every other shape returns
+ * EUNSUPPORTED, a wrong g or n % g != 0 EINVAL.
+ *   key     for group q (elements s_{gq} .. s_{gq+g-1}) and every sigma in 1 .. 2^g - 1 one GGSW of the indicator
+ *           [ s_{gq+i} == bit i of sigma for all i < g ], encrypted like a classic BSK row (same noise), on ChaCha
+ *           stream 0x600000 + 16 q + sigma; sigma = 0 is not stored.  Layout [q][sigma - 1][level][row c][col j][N].
+ *   switch  sum first, then switch: t_sigma = ms( sum_{i in sigma} a_{gq+i} mod 2^64 ), ms = the classic rounding
+ *           to 2N (NOT the sum of switched values)
+ *   step    acc <- acc + ExtProd( sum_sigma (X^{t_sigma} - 1) GGSW_{q,sigma}, acc ), the SignedDecomposer digits
+ *           taken from acc itself; exactly one indicator (sigma = 0 included) is 1, so this is
+ *           acc <- X^{<a, s>_group} acc.  Initial accumulator, sample extraction and LUT layout as the classic PBS.
+ * From one rng key the secret keys and the KSK are word for word those of tfhe_hip_keygen_k / server_keygen_k.
+ * tfhe_hip_mb_bsk_len: (n / g) (2^g - 1) (k+1) L (k+1) N words, 0 for invalid arguments. */
+size_t tfhe_hip_mb_bsk_len(const tfhe_params* p, uint32_t g);
+int tfhe_hip_mb_server_keygen_k(const tfhe_params* p, uint32_t g, const tfhe_rng_key* rk, const uint64_t* lwe_key,
+                                const uint64_t* glwe_key, uint64_t* bsk_mb, uint64_t* ksk /* nullable */);
+int tfhe_hip_mb_server_keygen(const tfhe_params* p, uint32_t g, uint64_t seed, const uint64_t* lwe_key,
+                              const uint64_t* glwe_key, uint64_t* bsk_mb, uint64_t* ksk /* nullable */);
 /* Modulus-switch noise reduction key of the P-FHEVM server key (the
  * reference's parameter block carries modulus_switch_zeros_count 1449, ms_bound 2^58,
  * ms_r_sigma_factor 13.179852282053789, ms_input_variance 2.63039184094559e-07 —
@@ -191,6 +212,18 @@ int tfhe_hip_load_keys_device(tfhe_ctx* ctx, const uint64_t* d_bsk, size_t bsk_l
  * TFHE_HIP_ENOKEYS until a tfhe_hip_load_keys makes the ctx complete.  _device: d_bsk on shard 0's device. */
 int tfhe_hip_load_bsk(tfhe_ctx* ctx, const uint64_t* bsk, size_t bsk_len);
 int tfhe_hip_load_bsk_device(tfhe_ctx* ctx, const uint64_t* d_bsk, size_t bsk_len);
+
+/* Multi-bit keys (tfhe_hip_mb_server_keygen*): upload, broadcast and convert like tfhe_hip_load_keys.  ksk == NULL
+ * loads a rotation-only ctx (as tfhe_hip_load_bsk).  Afterwards every entry point that blind-rotates (pbs*,
+ * pbs_many*, bootstrap*, blind_rotate, oprf*, expand_cast*, decompress*, lincomb_pbs_async) runs the multi-bit
+ * kernel on every shard and tfhe_hip_br_kernel reports its name; a later tfhe_hip_load_keys / load_bsk restores the
+ * classic path.  A loaded modulus-switch noise-reduction key is dropped: its pick is defined for the per-element
+ * switch, so tfhe_hip_load_ms_key and tfhe_hip_ms_reduce return EUNSUPPORTED on a multi-bit ctx.  EUNSUPPORTED for
+ * an NTT ctx or N = 1024; EINVAL for g outside {2, 3, 4}, n % g != 0 or a wrong length. */
+int tfhe_hip_load_keys_mb(tfhe_ctx* ctx, uint32_t g, const uint64_t* bsk_mb, size_t bsk_mb_len,
+                          const uint64_t* ksk /* nullable */, size_t ksk_len);
+/* Grouping factor of the resident bootstrapping key: 1 = classic keys (or none), 2..4 = multi-bit. */
+int tfhe_hip_grouping(const tfhe_ctx* ctx);
 
 /* Enable the modulus-switch noise reduction between keyswitch and blind rotation (order 1 only;
  * count = 0 disables).  Before each blind rotation the ciphertext gets the one zero whose

@@ -25,7 +25,7 @@ import numpy as np
 
 __all__ = [
     "Params", "TfheError", "lib", "ClientKey", "ServerKey", "gen_keys", "Engine", "FheBool", "FheUint8",
-    "PRESET_GATE", "PRESET_FHEVM", "PRESET_GATE_FFT", "PRESET_FHEVM_FFT", "TRANSFORM_NTT", "TRANSFORM_FFT64", "MU", "encode_bool",
+    "PRESET_GATE", "PRESET_FHEVM", "PRESET_GATE_FFT", "PRESET_FHEVM_FFT", "PRESET_FHEVM_MB_FFT", "TRANSFORM_NTT", "TRANSFORM_FFT64", "MU", "encode_bool",
     "decode_bool",
 ]
 
@@ -36,6 +36,8 @@ PRESET_GATE = 0
 PRESET_FHEVM = 1
 PRESET_GATE_FFT = 2  # P-GATE on the FFT64 transform (tfhe-rs's f64-FFT external product)
 PRESET_FHEVM_FFT = 3  # P-FHEVM on the FFT64 transform (N = 2048 as two 512-point halves)
+PRESET_FHEVM_MB_FFT = 4  # preset 3 with n = 924 (divisible by 2, 3 and 4): multi-bit PBS keys (gen_keys grouping=;
+                         # documented default grouping 3, the fastest at a batch of 32: DESIGN §4o)
 TRANSFORM_NTT = 0
 TRANSFORM_FFT64 = 1
 MU = 1 << 61  # gate encoding: true = +1/8, false = -1/8 of the 2^64 torus
@@ -128,6 +130,8 @@ ABI_SYMBOLS = (
     "tfhe_hip_matmul_expand_host", "tfhe_hip_matmul_dot_host", "tfhe_hip_matmul_decode", "tfhe_hip_matmul_create",
     "tfhe_hip_matmul_destroy", "tfhe_hip_matmul_matrix_create", "tfhe_hip_matmul_matrix_destroy",
     "tfhe_hip_matmul_expand_async", "tfhe_hip_matmul_expand", "tfhe_hip_matmul_dot_async", "tfhe_hip_matmul_dot",
+    "tfhe_hip_mb_bsk_len", "tfhe_hip_mb_server_keygen_k", "tfhe_hip_mb_server_keygen", "tfhe_hip_load_keys_mb",
+    "tfhe_hip_grouping",
 )
 
 # P-FHEVM modulus-switch noise reduction key (include/tfhe_hip.h TFHE_HIP_MS_FHEVM_*)
@@ -185,6 +189,14 @@ def lib():
         L.tfhe_hip_keygen_k.argtypes = [ctypes.c_void_p, _RKP, _U64P, _U64P, _U64P, _U64P]
         L.tfhe_hip_server_keygen_k.argtypes = [ctypes.c_void_p, _RKP, _U64P, _U64P, _U64P, _U64P]
         L.tfhe_hip_ms_zeros_keygen_k.argtypes = [ctypes.c_void_p, _RKP, _U64P, ctypes.c_uint32, _U64P]
+        L.tfhe_hip_mb_bsk_len.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+        L.tfhe_hip_mb_bsk_len.restype = ctypes.c_size_t
+        L.tfhe_hip_mb_server_keygen_k.argtypes = [ctypes.c_void_p, ctypes.c_uint32, _RKP, _U64P, _U64P, _U64P, _U64P]
+        L.tfhe_hip_mb_server_keygen.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, _U64P, _U64P, _U64P,
+                                                _U64P]
+        L.tfhe_hip_load_keys_mb.argtypes = [ctypes.c_void_p, ctypes.c_uint32, _U64P, ctypes.c_size_t, _U64P,
+                                            ctypes.c_size_t]
+        L.tfhe_hip_grouping.argtypes = [ctypes.c_void_p]
         L.tfhe_hip_aes128_block.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p]
         L.tfhe_hip_csprng_words.argtypes = [_U64P, ctypes.c_uint64, ctypes.c_size_t, _U64P]
         L.tfhe_hip_seeded_server_keygen_k.argtypes = [ctypes.c_void_p, _RKP, _U64P, _U64P, _U64P, _U64P, _U64P, _U64P]
@@ -390,10 +402,13 @@ class ClientKey:
 
 class ServerKey:
     """Public evaluation keys in the standard domain: BSK over Z_p and KSK over Z_2^64; for KS -> PBS
-    parameter sets (P-FHEVM) also the modulus-switch noise-reduction zeros (count x (n+1))."""
+    parameter sets (P-FHEVM) also the modulus-switch noise-reduction zeros (count x (n+1)).  ``grouping`` > 1: ``bsk``
+    is a multi-bit key of that grouping factor (include/tfhe_hip.h), ``ksk`` may be None (rotation-only) and there
+    are no zeros (the noise-reduction pick is defined for the per-element switch)."""
 
-    def __init__(self, params: Params, bsk: np.ndarray, ksk: np.ndarray, ms_zeros: Optional[np.ndarray] = None):
-        self.params, self.bsk, self.ksk, self.ms_zeros = params, bsk, ksk, ms_zeros
+    def __init__(self, params: Params, bsk: np.ndarray, ksk: np.ndarray, ms_zeros: Optional[np.ndarray] = None,
+                 grouping: int = 1):
+        self.params, self.bsk, self.ksk, self.ms_zeros, self.grouping = params, bsk, ksk, ms_zeros, int(grouping)
 
 
 def ms_zeros_keygen(params: Params, seed: Optional[int], lwe_key: np.ndarray,
@@ -407,17 +422,36 @@ def ms_zeros_keygen(params: Params, seed: Optional[int], lwe_key: np.ndarray,
     return z
 
 
-def gen_keys(params: Optional[Params] = None, seed: Optional[int] = None, with_server_key: bool = True):
+def _mb_server_key(p: Params, rk: RngKey, lwe: np.ndarray, glwe: np.ndarray, grouping: int) -> ServerKey:
+    L = lib()
+    g = int(grouping)
+    if not 0 <= g < 1 << 32:
+        raise ValueError(f"grouping = {grouping} must fit 32 bits")
+    bsk = np.zeros(max(L.tfhe_hip_mb_bsk_len(ctypes.byref(p), g), 1), dtype=np.uint64)
+    ksk = np.zeros(L.tfhe_hip_ksk_len(ctypes.byref(p)), dtype=np.uint64)
+    _check(L.tfhe_hip_mb_server_keygen_k(ctypes.byref(p), g, ctypes.byref(rk), _u64(lwe), _u64(glwe), _u64(bsk),
+                                         _u64(ksk)))
+    return ServerKey(p, bsk, ksk, None, grouping=g)
+
+
+def gen_keys(params: Optional[Params] = None, seed: Optional[int] = None, with_server_key: bool = True,
+             grouping: int = 1):
     """Key generation (tfhe-rs ``gen_keys`` analogue).  Returns (ClientKey, ServerKey).
 
     seed None (default): every key and the server-key randomness come from a fresh 192-bit OS-entropy
     ChaCha20 key.  An int seed gives the REPRODUCIBLE test key set (same streams as the oracle) --
-    anyone who knows the seed knows the secret key, so seeded keys are for tests and benchmarks only."""
+    anyone who knows the seed knows the secret key, so seeded keys are for tests and benchmarks only.
+
+    grouping 2, 3 or 4: a multi-bit server key of that grouping factor (the same secret keys and KSK as grouping 1)."""
     params = params or Params.preset(PRESET_GATE)
     L = lib()
     lwe = np.zeros(params.n, dtype=np.uint64)
     glwe = np.zeros(params.k * params.N, dtype=np.uint64)
     bsk = ksk = None
+    if with_server_key and grouping != 1:
+        rk = rng_key(seed)
+        _check(L.tfhe_hip_keygen_k(ctypes.byref(params), ctypes.byref(rk), _u64(lwe), _u64(glwe), None, None))
+        return ClientKey(params, seed, lwe, glwe), _mb_server_key(params, rk, lwe, glwe, grouping)
     if with_server_key:
         bsk = np.zeros(L.tfhe_hip_bsk_len(ctypes.byref(params)), dtype=np.uint64)
         ksk = np.zeros(L.tfhe_hip_ksk_len(ctypes.byref(params)), dtype=np.uint64)
@@ -435,12 +469,14 @@ def gen_keys(params: Optional[Params] = None, seed: Optional[int] = None, with_s
     return ck, ServerKey(params, bsk, ksk, zeros)
 
 
-def server_keygen(ck: "ClientKey", seed: Optional[int] = None) -> ServerKey:
+def server_keygen(ck: "ClientKey", seed: Optional[int] = None, grouping: int = 1) -> ServerKey:
     """BSK / KSK (+ MS zeros) for the secret keys of ``ck`` (e.g. a tfhe-rs ClientKey ingested by
     tfhe_amd.keyio).  seed None (default): fresh 192-bit OS entropy, so the published evaluation keys
-    reveal nothing reproducible; an int seed only for tests."""
+    reveal nothing reproducible; an int seed only for tests.  grouping 2, 3 or 4: a multi-bit key."""
     p = ck.params
     L = lib()
+    if grouping != 1:
+        return _mb_server_key(p, rng_key(seed), _c_u64(ck.lwe_key), _c_u64(ck.glwe_key), grouping)
     bsk = np.zeros(L.tfhe_hip_bsk_len(ctypes.byref(p)), dtype=np.uint64)
     ksk = np.zeros(L.tfhe_hip_ksk_len(ctypes.byref(p)), dtype=np.uint64)
     lwe, glwe = _c_u64(ck.lwe_key), _c_u64(ck.glwe_key)
@@ -544,6 +580,11 @@ class Engine:
         return per_wg * self.cus_per_device * len(self.devices)
 
     @property
+    def grouping(self) -> int:
+        """Grouping factor of the resident bootstrapping key: 1 = classic (or none), 2..4 = multi-bit."""
+        return int(lib().tfhe_hip_grouping(self._h))
+
+    @property
     def key_bcast_mode(self) -> str:
         return {0: "single", 1: "copy", 2: "rccl"}.get(lib().tfhe_hip_key_bcast_mode(self._h), "?")
 
@@ -566,6 +607,13 @@ class Engine:
 
     # -- keys -------------------------------------------------------------------------------
     def load_keys(self, sk: ServerKey) -> "Engine":
+        """Classic or multi-bit keys, by ``sk.grouping``."""
+        if getattr(sk, "grouping", 1) != 1:
+            bsk = _c_u64(sk.bsk)
+            ksk = _c_u64(sk.ksk) if sk.ksk is not None else None
+            _check(lib().tfhe_hip_load_keys_mb(self._h, int(sk.grouping), _u64(bsk), bsk.size,
+                                               _u64(ksk) if ksk is not None else None, ksk.size if ksk is not None else 0))
+            return self
         bsk, ksk = _c_u64(sk.bsk), _c_u64(sk.ksk)
         _check(lib().tfhe_hip_load_keys(self._h, _u64(bsk), bsk.size, _u64(ksk), ksk.size))
         if getattr(sk, "ms_zeros", None) is not None:

@@ -47,6 +47,8 @@ const struct {
     {TFHE_HIP_PRESET_FHEVM, {918, 1, 2048, 23, 1, 4, 4, -19, -47, 1, TFHE_HIP_TRANSFORM_NTT}},
     {TFHE_HIP_PRESET_GATE_FFT, {630, 1, 1024, 7, 3, 2, 8, -15, -25, 0, TFHE_HIP_TRANSFORM_FFT64}},
     {TFHE_HIP_PRESET_FHEVM_FFT, {918, 1, 2048, 23, 1, 4, 4, -19, -47, 1, TFHE_HIP_TRANSFORM_FFT64}},
+    // preset 3 with n divisible by 2, 3 and 4: the multi-bit keys' grouping factors (tfhe_hip_load_keys_mb)
+    {TFHE_HIP_PRESET_FHEVM_MB_FFT, {924, 1, 2048, 23, 1, 4, 4, -19, -47, 1, TFHE_HIP_TRANSFORM_FFT64}},
 };
 
 // a preset's shape: everything the kernels are specialised for (n and the noise parameters are free)
@@ -103,6 +105,8 @@ constexpr int TIMING_SLOTS = 4;
 struct tfhe_shard : device_slot {
   int cus = 0;                  // compute units (queried once, shard_init)
   u64* d_bsk = nullptr;        // transform domain (NTT layout x N^-1, or Fourier)
+  size_t bsk_cap = 0;          // bytes (a multi-bit key is larger than the classic one)
+  u64* d_tw_mb = nullptr;      // the multi-bit back end's own tables (first tfhe_hip_load_keys_mb)
   u64* d_ksk = nullptr;         // standard KSK (VALU keyswitch; RCCL broadcast source / target)
   void* d_ks_planes = nullptr;  // KSK recoded into 8 signed byte planes (ks_mfma.hip)
   u64* d_tw = nullptr;          // twiddle tables of the device transform
@@ -144,6 +148,8 @@ struct tfhe_ctx {
   bool ks_valu = false;  // TFHE_HIP_KS_VALU=1: the VALU keyswitch kernel instead (A/B runs)
   const tfhe::br_engine* eng = nullptr;  // the blind-rotation back end of (transform, N), set once in tfhe_hip_create
   size_t lat_max = 0;  // batches up to this size (per shard) run the latency kernel (default: eng->lat_max)
+  uint32_t grouping = 1;  // 2..4: multi-bit keys are resident and every blind rotation runs eng_mb
+  const tfhe::br_engine_mb* eng_mb = nullptr;  // the multi-bit back end on eng's ring, if any
   uint32_t ms_count = 0;
   double ms_bound = 0, ms_r_sigma = 0, ms_var128 = 0;
   int bcast_mode = 0;  // tfhe_hip_key_bcast_mode
@@ -195,6 +201,9 @@ bool latency_batch(const tfhe_ctx* c, size_t B) { return B <= c->lat_max; }
 
 hipError_t launch_br(tfhe_ctx* c, shard& s, const u64* in, size_t B, const u64* luts, const u32* idx, size_t n_lut,
                      u64* out_big, u64* out_acc, hipStream_t st) {
+  if (c->grouping > 1)
+    return c->eng_mb->blind_rotate(in, B, (int)c->p.n, (int)c->grouping, luts, idx, (int)n_lut, s.d_bsk, s.d_tw,
+                                   s.d_tw_mb, out_big, out_acc, st);
   return c->eng->blind_rotate(in, B, (int)c->p.n, luts, idx, (int)n_lut, s.d_bsk, s.d_tw, out_big, out_acc,
                               latency_batch(c, B), s.cus, st);
 }
@@ -473,7 +482,7 @@ int shard_init(tfhe_ctx* c, shard& s) {
 
 void shard_free(shard& s) {
   DeviceGuard g(s.device);
-  slot_close(s, {s.d_bsk, s.d_ksk, s.d_ks_planes, s.d_ks_dig, s.d_tw, s.d_ms_zeros, s.d_big, s.d_acc, s.d_expand, s.d_oprf,
+  slot_close(s, {s.d_bsk, s.d_tw_mb, s.d_ksk, s.d_ks_planes, s.d_ks_dig, s.d_tw, s.d_ms_zeros, s.d_big, s.d_acc, s.d_expand, s.d_oprf,
                  s.d_lin, s.d_lin_meta});
   for (int w = 0; w < TIMING_SLOTS; w++)
     for (auto e : s.ev[w]) (void)hipEventDestroy(e);
@@ -905,6 +914,38 @@ int tfhe_hip_server_keygen(const tfhe_params* p, uint64_t seed, const uint64_t* 
   return tfhe_hip_server_keygen_k(p, &rk, lwe_key, glwe_key, bsk, ksk);
 }
 
+// the multi-bit scope (include/tfhe_hip.h): FFT64, k = 1, N = 2048, PBS gadget 2^23 x 1
+static bool mb_scope(const tfhe_params* p) {
+  return p->transform == TFHE_HIP_TRANSFORM_FFT64 && p->k == 1 && p->N == 2048 && p->pbs_base_log == 23 &&
+         p->pbs_level == 1;
+}
+
+size_t tfhe_hip_mb_bsk_len(const tfhe_params* p, uint32_t g) {
+  return params_valid(p) && g >= 2 && g <= 4 && p->n % g == 0 ? tfhe::client::mb_bsk_len(*p, g) : 0;
+}
+
+int tfhe_hip_mb_server_keygen_k(const tfhe_params* p, uint32_t g, const tfhe_rng_key* rk, const uint64_t* lwe_key,
+                                const uint64_t* glwe_key, uint64_t* bsk_mb, uint64_t* ksk) {
+  if (!params_valid(p) || !rk || !lwe_key || !glwe_key || !bsk_mb)
+    return fail(TFHE_HIP_EINVAL, "mb_server_keygen: bad arguments");
+  if (g < 2 || g > 4) return fail(TFHE_HIP_EINVAL, "mb_server_keygen: grouping factor %u, expected 2, 3 or 4", g);
+  if (p->n % g) return fail(TFHE_HIP_EINVAL, "mb_server_keygen: n = %u is not divisible by the grouping factor %u", p->n, g);
+  if (!mb_scope(p))
+    return fail(TFHE_HIP_EUNSUPPORTED, "mb_server_keygen: multi-bit keys cover FFT64, k = 1, N = 2048, PBS 23x1; got "
+                                       "transform %u k=%u N=%u pbs %ux%u", p->transform, p->k, p->N, p->pbs_base_log,
+                p->pbs_level);
+  RC_TRY(check_binary(lwe_key, p->n, "mb_server_keygen: lwe_key"));
+  RC_TRY(check_binary(glwe_key, (size_t)p->k * p->N, "mb_server_keygen: glwe_key"));
+  tfhe::client::mb_server_keygen(*p, g, *rk, lwe_key, glwe_key, bsk_mb, ksk);
+  return 0;
+}
+
+int tfhe_hip_mb_server_keygen(const tfhe_params* p, uint32_t g, uint64_t seed, const uint64_t* lwe_key,
+                              const uint64_t* glwe_key, uint64_t* bsk_mb, uint64_t* ksk) {
+  const tfhe_rng_key rk = tfhe::client::rng_key_from_seed(seed);
+  return tfhe_hip_mb_server_keygen_k(p, g, &rk, lwe_key, glwe_key, bsk_mb, ksk);
+}
+
 int tfhe_hip_ms_zeros_keygen_k(const tfhe_params* p, const tfhe_rng_key* rk, const uint64_t* lwe_key, uint32_t count,
                                uint64_t* zeros) {
   if (!params_valid(p) || !rk || !lwe_key || (count && !zeros))
@@ -1027,6 +1068,7 @@ int tfhe_hip_create(const tfhe_params* p, const int* devices, int ndev, tfhe_ctx
   if (!c->eng)
     return fail(TFHE_HIP_EUNSUPPORTED, "create: no blind-rotation back end for transform %u, N = %u", p->transform,
                 p->N);
+  c->eng_mb = tfhe::find_engine_mb(c->eng);
   c->lat_max = c->eng->lat_max;  // the measured latency-kernel crossover (each engine row says how)
   {
     const char* e = getenv("TFHE_HIP_KS_VALU");
@@ -1071,23 +1113,48 @@ int tfhe_hip_bcast_plan(const int* devices, int ndev, const char* policy, int rc
   return n < 0 ? fail(n, "bcast_plan: %s", why.c_str()) : n;
 }
 
-// tfhe_hip_load_keys* (with_ksk) and tfhe_hip_load_bsk* (the BSK half alone; ksk / ksk_len unused)
+// the grouping factor of a multi-bit key: 2, 3 or 4 (include/tfhe_hip.h)
+static bool grouping_valid(uint32_t g) { return g >= 2 && g <= 4; }
+
+// tfhe_hip_load_keys* (with_ksk) and tfhe_hip_load_bsk* (the BSK half alone; ksk / ksk_len unused); g > 1: a
+// multi-bit key of that grouping factor (tfhe_hip_load_keys_mb), g == 1: a classic key
 static int load_keys_impl(tfhe_ctx* c, const char* what, const uint64_t* bsk, size_t bsk_len, const uint64_t* ksk,
-                          size_t ksk_len, bool with_ksk, bool from_host) {
+                          size_t ksk_len, bool with_ksk, bool from_host, uint32_t g = 1) {
   if (!c || !bsk || (with_ksk && !ksk)) return fail(TFHE_HIP_EINVAL, "%s: null argument", what);
   if (!with_ksk) ksk_len = tfhe::client::ksk_len(c->p);
-  if (bsk_len != tfhe::client::bsk_len(c->p) || ksk_len != tfhe::client::ksk_len(c->p))
-    return fail(TFHE_HIP_EINVAL, "%s: sizes %zu/%zu, expected %zu/%zu", what, bsk_len, ksk_len,
-                tfhe::client::bsk_len(c->p), tfhe::client::ksk_len(c->p));
+  const size_t want_bsk = g > 1 ? tfhe::client::mb_bsk_len(c->p, g) : tfhe::client::bsk_len(c->p);
+  if (bsk_len != want_bsk || ksk_len != tfhe::client::ksk_len(c->p))
+    return fail(TFHE_HIP_EINVAL, "%s: sizes %zu/%zu, expected %zu/%zu", what, bsk_len, ksk_len, want_bsk,
+                tfhe::client::ksk_len(c->p));
   std::lock_guard<std::mutex> lk(c->mu);
   c->keys = c->bsk = false;  // after a BSK-only load an earlier KSK belongs to another key set: rotation-only
+  c->grouping = 1;
   c->bcast_mode = 0;
+  if (g > 1) {
+    c->ms_count = 0;  // the noise-reduction pick is defined for the per-element switch
+    std::vector<u64> tw(c->eng_mb->table_words);
+    if (!c->eng_mb->make_tables(tw.data()))
+      return fail(TFHE_HIP_EUNSUPPORTED, "%s: the host root table's entry 0 is not exactly 1", what);
+    for (auto& s : c->sh) {
+      if (s.d_tw_mb) continue;
+      DeviceGuard gd(s.device);
+      HIP_TRY(hipMalloc(&s.d_tw_mb, tw.size() * 8));
+      HIP_TRY(hipMemcpy(s.d_tw_mb, tw.data(), tw.size() * 8, hipMemcpyHostToDevice));
+    }
+  }
   const size_t nd = c->sh.size();
   // every shard: key buffers + a standard-domain BSK staging area (its d_stage)
   for (auto& s : c->sh) {
     DeviceGuard g(s.device);
     RC_TRY(ws_host_wait(s));
-    if (!s.d_bsk) HIP_TRY(hipMalloc(&s.d_bsk, bsk_len * 8));
+    if (s.bsk_cap < bsk_len * 8) {
+      HIP_TRY(hipStreamSynchronize(s.stream));
+      (void)hipFree(s.d_bsk);
+      s.d_bsk = nullptr;
+      s.bsk_cap = 0;
+      HIP_TRY(hipMalloc(&s.d_bsk, bsk_len * 8));
+      s.bsk_cap = bsk_len * 8;
+    }
     if (with_ksk && !s.d_ksk) HIP_TRY(hipMalloc(&s.d_ksk, ksk_len * 8));
     RC_TRY(ws_grow(s, &s.d_stage, &s.stage_cap, bsk_len * 8));
   }
@@ -1117,6 +1184,7 @@ static int load_keys_impl(tfhe_ctx* c, const char* what, const uint64_t* bsk, si
     RC_TRY(convert_keys(c, c->sh[i], i == 0 ? bsk0 : (const u64*)c->sh[i].d_stage, bsk_len, with_ksk));
   c->bsk = true;
   c->keys = with_ksk;
+  c->grouping = g;
   return 0;
 }
 
@@ -1137,9 +1205,26 @@ int tfhe_hip_load_bsk_device(tfhe_ctx* c, const uint64_t* d_bsk, size_t bsk_len)
   return load_keys_impl(c, "load_bsk", d_bsk, bsk_len, nullptr, 0, false, false);
 }
 
+int tfhe_hip_load_keys_mb(tfhe_ctx* c, uint32_t g, const uint64_t* bsk_mb, size_t bsk_mb_len, const uint64_t* ksk,
+                          size_t ksk_len) {
+  if (!c || !bsk_mb) return fail(TFHE_HIP_EINVAL, "load_keys_mb: null argument");
+  if (!c->eng_mb)
+    return fail(TFHE_HIP_EUNSUPPORTED, "load_keys_mb: the multi-bit back end covers the FFT64 transform at N = 2048 "
+                                       "(PBS 23x1); this ctx runs transform %u, N = %u", c->p.transform, c->p.N);
+  if (!grouping_valid(g) || g < c->eng_mb->g_min || g > c->eng_mb->g_max)
+    return fail(TFHE_HIP_EINVAL, "load_keys_mb: grouping factor %u, expected 2, 3 or 4", g);
+  if (c->p.n % g) return fail(TFHE_HIP_EINVAL, "load_keys_mb: n = %u is not divisible by the grouping factor %u", c->p.n, g);
+  return load_keys_impl(c, "load_keys_mb", bsk_mb, bsk_mb_len, ksk, ksk_len, ksk != nullptr, true, g);
+}
+
+int tfhe_hip_grouping(const tfhe_ctx* c) { return c ? (int)c->grouping : 1; }
+
 int tfhe_hip_load_ms_key(tfhe_ctx* c, const uint64_t* zeros, uint32_t count, double bound, double r_sigma,
                          double input_variance) {
   if (!c || (count && !zeros)) return fail(TFHE_HIP_EINVAL, "load_ms_key: bad arguments");
+  if (c->grouping > 1)
+    return fail(TFHE_HIP_EUNSUPPORTED, "load_ms_key: multi-bit keys are loaded (grouping %u); the noise-reduction pick "
+                                       "is defined for the per-element modulus switch", c->grouping);
   if (c->p.order != 1 && count)
     return fail(TFHE_HIP_EUNSUPPORTED, "load_ms_key: the noise reduction runs between keyswitch and blind rotation "
                                        "(KS -> PBS parameter sets only)");
@@ -1184,6 +1269,9 @@ int tfhe_hip_load_ms_key(tfhe_ctx* c, const uint64_t* zeros, uint32_t count, dou
 int tfhe_hip_ms_reduce(tfhe_ctx* c, const uint64_t* in, size_t B, uint64_t* out, int32_t* picks) {
   if (!c || (B && (!in || !out))) return fail(TFHE_HIP_EINVAL, "ms_reduce: bad arguments");
   if (c->p.order != 1) return fail(TFHE_HIP_EUNSUPPORTED, "ms_reduce: KS -> PBS parameter sets only");
+  if (c->grouping > 1)
+    return fail(TFHE_HIP_EUNSUPPORTED, "ms_reduce: multi-bit keys are loaded (grouping %u); the noise-reduction pick is "
+                                       "defined for the per-element modulus switch", c->grouping);
   if (B == 0) return 0;
   if (B > 0x7FFFFFFF) return fail(TFHE_HIP_EINVAL, "ms_reduce: batch too large");
   const size_t bytes = B * ((size_t)c->p.n + 1) * 8;
@@ -1537,6 +1625,7 @@ int tfhe_hip_set_latency_batch(tfhe_ctx* c, size_t max_batch) {
 
 const char* tfhe_hip_br_kernel(const tfhe_ctx* c, size_t B) {
   if (!c) return nullptr;
+  if (c->grouping > 1) return c->eng_mb->kernel;
   return latency_batch(c, B) ? c->eng->lat_kernel : c->eng->batch_kernel;
 }
 

@@ -241,6 +241,33 @@ void server_keygen(const tfhe_params& p, const tfhe_rng_key& rk, const uint64_t*
   }
 }
 
+// multi-bit bootstrapping key: GGSW (q, sigma) of the indicator [s_{gq+i} == bit i of sigma, all i < g] on ChaCha
+// stream 0x600000 + 16 q + sigma (sigma = 1 .. 2^g - 1 <= 15), encrypted as the native-torus rows above
+size_t mb_bsk_len(const tfhe_params& p, uint32_t g) {
+  return (size_t)(p.n / g) * ((1u << g) - 1) * (p.k + 1) * p.pbs_level * (p.k + 1) * p.N;
+}
+
+void mb_server_keygen(const tfhe_params& p, uint32_t g, const tfhe_rng_key& rk, const uint64_t* lwe_key,
+                      const uint64_t* glwe_key, uint64_t* bsk_mb, uint64_t* ksk) {
+  if (bsk_mb) {
+    const uint32_t per_q = (1u << g) - 1;
+    const size_t row = (size_t)(p.k + 1) * p.N, per_ggsw = (size_t)(p.k + 1) * p.pbs_level * row;
+    parallel_for((int64_t)(p.n / g) * per_q, [&](int64_t idx) {
+      const uint32_t q = (uint32_t)(idx / per_q), sigma = (uint32_t)(idx % per_q) + 1;
+      bool ind = true;
+      for (uint32_t i = 0; i < g; i++) ind = ind && lwe_key[(size_t)g * q + i] == ((sigma >> i) & 1u);
+      ChaCha r(rk, 0x600000 + 16 * (uint64_t)q + sigma);
+      for (uint32_t l = 0; l < p.pbs_level; l++)
+        for (uint32_t c = 0; c <= p.k; c++) {
+          uint64_t* out = bsk_mb + per_ggsw * idx + row * (l * (p.k + 1) + c);
+          glwe_native(p.k, p.N, glwe_key, p.glwe_noise_log2, r, nullptr, out);
+          if (ind) out[(size_t)c * p.N] += 1ull << (64 - p.pbs_base_log * (l + 1));
+        }
+    });
+  }
+  if (ksk) server_keygen(p, rk, lwe_key, glwe_key, nullptr, ksk);
+}
+
 // modulus-switch zeros of the P-FHEVM server key: zero z on ChaCha stream 0x200000 + z
 void ms_zeros_keygen(const tfhe_params& p, const tfhe_rng_key& rk, const uint64_t* lwe_key, uint32_t count, uint64_t* zeros) {
   parallel_for((int64_t)count, [&](int64_t z) {

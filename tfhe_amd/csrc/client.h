@@ -15,6 +15,11 @@ void keygen(const tfhe_params& p, const tfhe_rng_key& rk, uint64_t* lwe_key, uin
 // BSK / KSK for given binary secret keys (e.g. an ingested tfhe-rs ClientKey); same streams as keygen
 void server_keygen(const tfhe_params& p, const tfhe_rng_key& rk, const uint64_t* lwe_key, const uint64_t* glwe_key,
                    uint64_t* bsk, uint64_t* ksk);
+// multi-bit keys (include/tfhe_hip.h): g in {2, 3, 4}, n % g == 0 and a native-torus p are the caller's checks;
+// bsk_mb [q][sigma - 1][level][row c][col j][N], the KSK that of server_keygen
+size_t mb_bsk_len(const tfhe_params& p, uint32_t g);
+void mb_server_keygen(const tfhe_params& p, uint32_t g, const tfhe_rng_key& rk, const uint64_t* lwe_key,
+                      const uint64_t* glwe_key, uint64_t* bsk_mb, uint64_t* ksk);
 // P-FHEVM modulus-switch zeros: count LWE encryptions of 0 under the small key, count x (n+1)
 void ms_zeros_keygen(const tfhe_params& p, const tfhe_rng_key& rk, const uint64_t* lwe_key, uint32_t count, uint64_t* zeros);
 void lwe_encrypt(uint32_t dim, const uint64_t* key, int32_t noise_log2, const tfhe_rng_key& rk, uint64_t stream0,

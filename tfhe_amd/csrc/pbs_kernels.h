@@ -42,6 +42,28 @@ inline const br_engine* find_engine(bool fft, unsigned N) {
   return nullptr;
 }
 
+// ---- the multi-bit back ends: pbs_fft2k_mb.hip ----------------------------------------------------------------------
+// A second lookup beside find_engine: a row serves the keys of grouping factor g_min .. g_max on the ring of `base`
+// (whose tables, convert_bsk and transforms it shares; the converted key is (n / g)(2^g - 1) GGSWs in base's layout).
+struct br_engine_mb {
+  const br_engine* base;
+  unsigned g_min, g_max;
+  const char* kernel;      // what tfhe_hip_br_kernel reports (one kernel shape for every batch size)
+  size_t table_words;      // the back end's own device tables, 8-byte words
+  bool (*make_tables)(u64* tw_mb);
+  // as br_engine::blind_rotate; n % g == 0, tw = base's tables, tw_mb = this row's
+  hipError_t (*blind_rotate)(const u64* lwe_in, size_t B, int n, int g, const u64* luts, const u32* lut_index,
+                             int n_lut, const u64* bsk, const u64* tw, const u64* tw_mb, u64* out_big, u64* out_acc,
+                             hipStream_t s);
+};
+extern const br_engine_mb ENGINE_FFT2K_MB;
+
+inline const br_engine_mb* find_engine_mb(const br_engine* base) {
+  for (const br_engine_mb* e : {&ENGINE_FFT2K_MB})
+    if (e->base == base) return e;
+  return nullptr;
+}
+
 // The output mode of a blind rotation as compile-time flags: f(WRITE_ACC, WRITE_BIG) launches the kernel
 // instantiated for `acc only` or `big only` (f's arguments are std::bool_constant values).
 template <class F>
