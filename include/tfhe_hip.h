@@ -74,7 +74,7 @@ uint32_t tfhe_hip_io_dim(const tfhe_params* p);
  * Replaces TfheClientKey.generate / ServerKey generation (sdk/relayer/src/tfhe.ts:20-28,
  * generateKeys.js:20-31).  All randomness is ChaCha20 keyed by a 192-bit rng key plus a stream index
  * (LWE key 1, GLWE key 2, BSK_i 0x1000+i, KSK_j 0x100000+j, MS zero z 0x200000+z, multi-bit GGSW (q, sigma)
- * 0x600000 + 16 q + sigma, ciphertext q stream0+q).
+ * 0x600000 + 16 q + sigma, seeded multi-bit GGSW (q, sigma) 0x700000 + 16 q + sigma, ciphertext q stream0+q).
  *   - tfhe_hip_rng_key_entropy: 192 bits from the OS (getrandom) -- production keys and encryptions;
  *   - tfhe_hip_rng_key_from_seed: (seed, a public tag) -- REPRODUCIBLE streams for tests, golden vectors
  *     and the oracle.  A seeded key set is public knowledge: never use one for real data.
@@ -153,6 +153,27 @@ int tfhe_hip_decompress_bsk(const tfhe_params* p, const uint64_t seed[2], const 
 int tfhe_hip_decompress_ksk(const tfhe_params* p, const uint64_t seed[2], const uint64_t* bodies, uint64_t* ksk);
 int tfhe_hip_decompress_lwe_list(uint32_t dim, uint32_t count, const uint64_t seed[2], const uint64_t* bodies,
                                  uint64_t* out /* count x (dim + 1) */);
+/* Seeded multi-bit bootstrapping keys (tfhe-rs SeededLweMultiBitBootstrapKey; restated, PARITY UNPINNED at the byte
+ * level like every seeded path).  Bodies [n/g][2^g][L][k+1][N]: group q holds 2^g GGSWs, sigma = 0 .. 2^g - 1 (tfhe-rs
+ * stores all 2^g, this engine keeps 2^g - 1); bit i of sigma belongs to key element g q + i (the convention of
+ * tfhe_hip_mb_server_keygen) and GGSW (q, sigma) encrypts the indicator [(s_{gq+i})_i = bits of sigma], its rows in
+ * tfhe-rs's form as tfhe_hip_seeded_server_keygen_k writes them (row c < k: -m g_l S_c, row k: m g_l).  Stream row
+ * rho = ((q 2^g + sigma) L + l)(k+1) + c owns mask words rho k N ... of the seed's stream; the noise of GGSW
+ * (q, sigma) comes from ChaCha stream 0x700000 + 16 q + sigma of the rng key.  The KSK of a multi-bit set is the
+ * classic seeded KSK (tfhe_hip_seeded_server_keygen_k with bsk_bodies NULL).
+ * tfhe_hip_decompress_bsk_mb is the host reference of the device route: it writes this engine's layout
+ * [q][sigma - 1][l][c][j][N] (level-major, unlike the classic [i][c L + l]) and SKIPS sigma = 0, whose bodies are
+ * ignored and whose mask words are stepped over in the stream.  Valid because sum_sigma indicator_sigma = 1, so
+ * tfhe-rs's sum_sigma X^{t_sigma} GGSW_sigma [.] acc equals this engine's acc + sum_{sigma >= 1} (X^{t_sigma} - 1)
+ * GGSW_sigma [.] acc up to noise.
+ * Both refuse what tfhe_hip_load_keys_mb refuses: EINVAL for g outside {2, 3, 4} or n % g != 0, EUNSUPPORTED outside
+ * FFT64, k = 1, N = 2048, PBS 23x1.  tfhe_hip_seeded_mb_bodies_len: (n / g) 2^g L (k+1) N, 0 for invalid arguments. */
+size_t tfhe_hip_seeded_mb_bodies_len(const tfhe_params* p, uint32_t g);
+int tfhe_hip_seeded_mb_server_keygen_k(const tfhe_params* p, uint32_t g, const tfhe_rng_key* rk,
+                                       const uint64_t bsk_seed[2], const uint64_t* lwe_key, const uint64_t* glwe_key,
+                                       uint64_t* bsk_bodies);
+int tfhe_hip_decompress_bsk_mb(const tfhe_params* p, uint32_t g, const uint64_t seed[2], const uint64_t* bodies,
+                               uint64_t* bsk_mb);
 /* Encrypt count torus messages; ciphertext q uses ChaCha stream (stream0 + q) of the rng key (a fresh
  * entropy key per call, or one key with non-overlapping stream ranges).
  * Replaces the encrypt path of packages/luxfhejs/src/index.ts:127-141 (server-side /encrypt). */
@@ -225,6 +246,40 @@ int tfhe_hip_load_keys_mb(tfhe_ctx* ctx, uint32_t g, const uint64_t* bsk_mb, siz
 /* Grouping factor of the resident bootstrapping key: 1 = classic keys (or none), 2..4 = multi-bit. */
 int tfhe_hip_grouping(const tfhe_ctx* ctx);
 
+/* Seeded (compressed) keys loaded without a host decompression (the CompressedServerKey::decompress step of the
+ * fhEVM coprocessor's tenant key cache, on the device): the HOST body buffers (layouts of the seeded section above)
+ * go through the pinned ring to shard 0 and by the key broadcast to the other shards -- bodies, not expanded keys:
+ * 1/(k+1) of the BSK words and 1/(n+1) of the KSK words -- and every shard regenerates the masks into its own
+ * standard-domain buffers (tfhe_amd/csrc/seeded_keys.hip: AES-128-CTR as tfhe_hip_csprng_words, the key schedule once
+ * per seed on the host), word for word what tfhe_hip_decompress_bsk / _bsk_mb / _ksk write; the conversion kernels of
+ * tfhe_hip_load_keys follow unchanged.  The device copy of the bodies is released before the call returns.  State
+ * transitions are those of the unseeded loaders: _seeded and _bsk_seeded restore the classic back end, _mb_seeded
+ * (ksk_bodies NULL = rotation-only, ksk_seed then unused) drops a resident noise-reduction key.  FFT64 ctx only
+ * (EUNSUPPORTED otherwise); EINVAL for a null argument, a wrong body count (bsk: n L (k+1) N or
+ * tfhe_hip_seeded_mb_bodies_len; ksk: k N ks_level), g outside {2, 3, 4} or n % g != 0; EUNSUPPORTED for a multi-bit
+ * load at N = 1024.  Every check precedes any change of the ctx: after a refused call the resident keys still work. */
+int tfhe_hip_load_keys_seeded(tfhe_ctx* ctx, const uint64_t bsk_seed[2], const uint64_t* bsk_bodies,
+                              size_t bsk_bodies_len, const uint64_t ksk_seed[2], const uint64_t* ksk_bodies,
+                              size_t ksk_bodies_len);
+int tfhe_hip_load_bsk_seeded(tfhe_ctx* ctx, const uint64_t seed[2], const uint64_t* bodies, size_t bodies_len);
+int tfhe_hip_load_keys_mb_seeded(tfhe_ctx* ctx, uint32_t g, const uint64_t bsk_seed[2], const uint64_t* bsk_bodies,
+                                 size_t bsk_bodies_len, const uint64_t ksk_seed[2] /* nullable with ksk_bodies */,
+                                 const uint64_t* ksk_bodies /* nullable */, size_t ksk_bodies_len);
+/* Device milliseconds of the last seeded key load on shard 0: upload of the bodies, expansion kernels, conversion
+ * (a measurement aid, tools/seeded_load_bench.py; any pointer may be null). */
+int tfhe_hip_seeded_load_stats(const tfhe_ctx* ctx, double* upload_ms, double* expand_ms, double* convert_ms);
+/* Stage-level (the parity tests): the expansion kernels alone, through the launchers the loaders use, on shard 0.
+ * out_host receives the standard-domain key (tfhe_hip_bsk_len / tfhe_hip_mb_bsk_len / tfhe_hip_ksk_len / count x
+ * (dim + 1) words) FOLLOWED BY TFHE_HIP_SEEDED_GUARD_WORDS words of the device buffer behind it, which were filled
+ * with 0xA5 bytes before the launch: a kernel that stays in bounds leaves them as they were.  _bsk: g = 1 classic
+ * bodies, g in 2..4 multi-bit bodies, shape and n of the ctx; errors as the loaders. */
+#define TFHE_HIP_SEEDED_GUARD_WORDS 64u
+int tfhe_hip_seeded_expand_bsk(tfhe_ctx* ctx, uint32_t g, const uint64_t seed[2], const uint64_t* bodies,
+                               uint64_t* out_host);
+int tfhe_hip_seeded_expand_ksk(tfhe_ctx* ctx, const uint64_t seed[2], const uint64_t* bodies, uint64_t* out_host);
+int tfhe_hip_seeded_expand_lwe_list(tfhe_ctx* ctx, uint32_t dim, uint32_t count, const uint64_t seed[2],
+                                    const uint64_t* bodies, uint64_t* out_host);
+
 /* Enable the modulus-switch noise reduction between keyswitch and blind rotation (order 1 only;
  * count = 0 disables).  Before each blind rotation the ciphertext gets the one zero whose
  * measure |E[err]| + r_sigma * sd(err) of the switch to 2N is best (tfhe-rs 1.x
@@ -232,6 +287,11 @@ int tfhe_hip_grouping(const tfhe_ctx* ctx);
  * EUNSUPPORTED for order 0 parameter sets. */
 int tfhe_hip_load_ms_key(tfhe_ctx* ctx, const uint64_t* zeros, uint32_t count, double bound, double r_sigma,
                          double input_variance);
+/* The same from the seeded form of the zeros (bodies [count], tfhe_hip_seeded_lwe_list_k at dim = n): the rows
+ * [count][n+1] are expanded and their element-major transpose is built on every shard's device.  Checks and refusals
+ * of tfhe_hip_load_ms_key (EUNSUPPORTED on a multi-bit ctx, the 2 GiB scan window), EUNSUPPORTED for an NTT ctx. */
+int tfhe_hip_load_ms_key_seeded(tfhe_ctx* ctx, const uint64_t seed[2], const uint64_t* bodies, uint32_t count,
+                                double bound, double r_sigma, double input_variance);
 /* Stage-level: the reduction alone on B small-key ciphertexts (B x (n+1)); picks (nullable, B
  * entries) receives the chosen zero index or -1. */
 int tfhe_hip_ms_reduce(tfhe_ctx* ctx, const uint64_t* lwe_small, size_t B, uint64_t* out, int32_t* picks);

@@ -131,7 +131,10 @@ ABI_SYMBOLS = (
     "tfhe_hip_matmul_destroy", "tfhe_hip_matmul_matrix_create", "tfhe_hip_matmul_matrix_destroy",
     "tfhe_hip_matmul_expand_async", "tfhe_hip_matmul_expand", "tfhe_hip_matmul_dot_async", "tfhe_hip_matmul_dot",
     "tfhe_hip_mb_bsk_len", "tfhe_hip_mb_server_keygen_k", "tfhe_hip_mb_server_keygen", "tfhe_hip_load_keys_mb",
-    "tfhe_hip_grouping",
+    "tfhe_hip_grouping", "tfhe_hip_seeded_mb_bodies_len", "tfhe_hip_seeded_mb_server_keygen_k",
+    "tfhe_hip_decompress_bsk_mb", "tfhe_hip_load_keys_seeded", "tfhe_hip_load_bsk_seeded",
+    "tfhe_hip_load_keys_mb_seeded", "tfhe_hip_load_ms_key_seeded", "tfhe_hip_seeded_load_stats",
+    "tfhe_hip_seeded_expand_bsk", "tfhe_hip_seeded_expand_ksk", "tfhe_hip_seeded_expand_lwe_list",
 )
 
 # P-FHEVM modulus-switch noise reduction key (include/tfhe_hip.h TFHE_HIP_MS_FHEVM_*)
@@ -197,6 +200,23 @@ def lib():
         L.tfhe_hip_load_keys_mb.argtypes = [ctypes.c_void_p, ctypes.c_uint32, _U64P, ctypes.c_size_t, _U64P,
                                             ctypes.c_size_t]
         L.tfhe_hip_grouping.argtypes = [ctypes.c_void_p]
+        L.tfhe_hip_seeded_mb_bodies_len.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+        L.tfhe_hip_seeded_mb_bodies_len.restype = ctypes.c_size_t
+        L.tfhe_hip_seeded_mb_server_keygen_k.argtypes = [ctypes.c_void_p, ctypes.c_uint32, _RKP, _U64P, _U64P, _U64P, _U64P]
+        L.tfhe_hip_decompress_bsk_mb.argtypes = [ctypes.c_void_p, ctypes.c_uint32, _U64P, _U64P, _U64P]
+        L.tfhe_hip_load_keys_seeded.argtypes = [ctypes.c_void_p, _U64P, _U64P, ctypes.c_size_t, _U64P, _U64P,
+                                                ctypes.c_size_t]
+        L.tfhe_hip_load_bsk_seeded.argtypes = [ctypes.c_void_p, _U64P, _U64P, ctypes.c_size_t]
+        L.tfhe_hip_load_keys_mb_seeded.argtypes = [ctypes.c_void_p, ctypes.c_uint32, _U64P, _U64P, ctypes.c_size_t, _U64P,
+                                                   _U64P, ctypes.c_size_t]
+        L.tfhe_hip_load_ms_key_seeded.argtypes = [ctypes.c_void_p, _U64P, _U64P, ctypes.c_uint32, ctypes.c_double,
+                                                  ctypes.c_double, ctypes.c_double]
+        _dp = ctypes.POINTER(ctypes.c_double)
+        L.tfhe_hip_seeded_load_stats.argtypes = [ctypes.c_void_p, _dp, _dp, _dp]
+        L.tfhe_hip_seeded_expand_bsk.argtypes = [ctypes.c_void_p, ctypes.c_uint32, _U64P, _U64P, _U64P]
+        L.tfhe_hip_seeded_expand_ksk.argtypes = [ctypes.c_void_p, _U64P, _U64P, _U64P]
+        L.tfhe_hip_seeded_expand_lwe_list.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, _U64P, _U64P,
+                                                      _U64P]
         L.tfhe_hip_aes128_block.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_void_p]
         L.tfhe_hip_csprng_words.argtypes = [_U64P, ctypes.c_uint64, ctypes.c_size_t, _U64P]
         L.tfhe_hip_seeded_server_keygen_k.argtypes = [ctypes.c_void_p, _RKP, _U64P, _U64P, _U64P, _U64P, _U64P, _U64P]
@@ -627,6 +647,43 @@ class Engine:
         b = _c_u64(bsk)
         _check(lib().tfhe_hip_load_bsk(self._h, _u64(b), b.size))
         return self
+
+    def load_compressed_keys(self, csk) -> "Engine":
+        """A whole ``keyio.CompressedServerKey`` through the seeded loaders: bodies and seeds go up, the masks are
+        generated into the key layouts on the device (tfhe_amd/csrc/seeded_keys.hip) and the usual conversion follows.
+        Multi-bit when ``csk.grouping > 1``; the modulus-switch zeros are loaded when the key carries them and is
+        classic.  Same resident keys as ``keyio.decompress_server_key`` + ``load_keys``, word for word."""
+        from . import keyio
+        L = lib()
+        g = int(getattr(csk, "grouping", 1))
+        bb, kb = _c_u64(csk.bsk_bodies).ravel(), _c_u64(csk.ksk_bodies).ravel()
+        bs, ks = keyio._seed2(csk.bsk_seed), keyio._seed2(csk.ksk_seed)
+        if g != 1:
+            if not 0 <= g < 1 << 32:
+                raise ValueError(f"grouping = {g} must fit 32 bits")
+            _check(L.tfhe_hip_load_keys_mb_seeded(self._h, g, _u64(bs), _u64(bb), bb.size, _u64(ks), _u64(kb), kb.size))
+            return self
+        _check(L.tfhe_hip_load_keys_seeded(self._h, _u64(bs), _u64(bb), bb.size, _u64(ks), _u64(kb), kb.size))
+        if csk.ms_bodies is not None and csk.ms_seed is not None:
+            mb = _c_u64(csk.ms_bodies).ravel()
+            ms = {**{k: MS_FHEVM[k] for k in ("bound", "r_sigma", "input_variance")}, **(csk.ms or {})}
+            _check(L.tfhe_hip_load_ms_key_seeded(self._h, _u64(keyio._seed2(csk.ms_seed)), _u64(mb), mb.size,
+                                                 ms["bound"], ms["r_sigma"], ms["input_variance"]))
+        return self
+
+    def load_compressed_bsk(self, seed: int, bodies: np.ndarray) -> "Engine":
+        """The rotation-only form of ``load_compressed_keys``: a seeded classic bootstrapping key alone (bodies
+        [n][L][k+1][N]), e.g. a decompression key.  The engine is then rotation-only as after ``load_bsk``."""
+        from . import keyio
+        b = _c_u64(bodies).ravel()
+        _check(lib().tfhe_hip_load_bsk_seeded(self._h, _u64(keyio._seed2(seed)), _u64(b), b.size))
+        return self
+
+    def seeded_load_stats(self) -> dict:
+        """Device milliseconds of the last seeded key load on shard 0: upload, expansion kernels, conversion."""
+        v = [ctypes.c_double() for _ in range(3)]
+        _check(lib().tfhe_hip_seeded_load_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return {"upload_ms": v[0].value, "expand_ms": v[1].value, "convert_ms": v[2].value}
 
     def load_ms_key(self, zeros: Optional[np.ndarray], bound: float = MS_FHEVM["bound"],
                     r_sigma: float = MS_FHEVM["r_sigma"], input_variance: float = MS_FHEVM["input_variance"]):

@@ -156,6 +156,7 @@ struct tfhe_ctx {
   std::vector<ncclComm_t> comms;
   std::mutex mu;
   bool timing = false;
+  double seeded_ms[3] = {0, 0, 0};  // the last seeded load on shard 0: upload, expansion, conversion (device ms)
 };
 
 namespace {
@@ -1010,6 +1011,43 @@ int tfhe_hip_decompress_lwe_list(uint32_t dim, uint32_t count, const uint64_t se
   return 0;
 }
 
+// the refusals shared by the two host calls of the seeded multi-bit key: those of tfhe_hip_load_keys_mb
+static int seeded_mb_check(const char* what, const tfhe_params* p, uint32_t g) {
+  if (g < 2 || g > 4) return fail(TFHE_HIP_EINVAL, "%s: grouping factor %u, expected 2, 3 or 4", what, g);
+  if (p->n % g) return fail(TFHE_HIP_EINVAL, "%s: n = %u is not divisible by the grouping factor %u", what, p->n, g);
+  if (!mb_scope(p))
+    return fail(TFHE_HIP_EUNSUPPORTED, "%s: multi-bit keys cover FFT64, k = 1, N = 2048, PBS 23x1; got transform %u "
+                                       "k=%u N=%u pbs %ux%u", what, p->transform, p->k, p->N, p->pbs_base_log,
+                p->pbs_level);
+  return 0;
+}
+
+size_t tfhe_hip_seeded_mb_bodies_len(const tfhe_params* p, uint32_t g) {
+  return params_valid(p) && g >= 2 && g <= 4 && p->n % g == 0
+             ? (size_t)(p->n / g) * (1u << g) * p->pbs_level * (p->k + 1) * p->N
+             : 0;
+}
+
+int tfhe_hip_seeded_mb_server_keygen_k(const tfhe_params* p, uint32_t g, const tfhe_rng_key* rk,
+                                       const uint64_t bsk_seed[2], const uint64_t* lwe_key, const uint64_t* glwe_key,
+                                       uint64_t* bsk_bodies) {
+  if (!params_valid(p) || !rk || !bsk_seed || !lwe_key || !glwe_key || !bsk_bodies)
+    return fail(TFHE_HIP_EINVAL, "seeded_mb_server_keygen: bad arguments");
+  RC_TRY(seeded_mb_check("seeded_mb_server_keygen", p, g));
+  RC_TRY(check_binary(lwe_key, p->n, "seeded_mb_server_keygen: lwe_key"));
+  RC_TRY(check_binary(glwe_key, (size_t)p->k * p->N, "seeded_mb_server_keygen: glwe_key"));
+  tfhe::seeded::seeded_mb_server_keygen(*p, g, *rk, bsk_seed, lwe_key, glwe_key, bsk_bodies);
+  return 0;
+}
+
+int tfhe_hip_decompress_bsk_mb(const tfhe_params* p, uint32_t g, const uint64_t seed[2], const uint64_t* bodies,
+                               uint64_t* bsk_mb) {
+  if (!params_valid(p) || !seed || !bodies || !bsk_mb) return fail(TFHE_HIP_EINVAL, "decompress_bsk_mb: bad arguments");
+  RC_TRY(seeded_mb_check("decompress_bsk_mb", p, g));
+  tfhe::seeded::decompress_bsk_mb(*p, g, seed, bodies, bsk_mb);
+  return 0;
+}
+
 int tfhe_hip_ms_zeros_keygen(const tfhe_params* p, uint64_t seed, const uint64_t* lwe_key, uint32_t count,
                              uint64_t* zeros) {
   const tfhe_rng_key rk = tfhe::client::rng_key_from_seed(seed);
@@ -1116,13 +1154,121 @@ int tfhe_hip_bcast_plan(const int* devices, int ndev, const char* policy, int rc
 // the grouping factor of a multi-bit key: 2, 3 or 4 (include/tfhe_hip.h)
 static bool grouping_valid(uint32_t g) { return g >= 2 && g <= 4; }
 
+// A seeded key source of load_keys_impl (tfhe_hip_load_*_seeded): seeds and HOST body buffers in the container's
+// layouts (include/tfhe_hip.h).  Only bodies and round keys travel; every shard expands into its own d_stage / d_ksk.
+struct seeded_src {
+  const uint64_t *bsk_seed, *bsk_bodies;
+  size_t bsk_bodies_len;
+  const uint64_t *ksk_seed, *ksk_bodies;  // unused without a KSK
+  size_t ksk_bodies_len;
+};
+
+static tfhe::seeded_shape seeded_shape_of(const tfhe_params& p, uint32_t g, uint32_t count = 0) {
+  return tfhe::seeded_shape{p.n, p.k, p.N, p.pbs_level, p.ks_level, g, count};
+}
+
+static tfhe::seeded_round_keys round_keys_of(const uint64_t seed[2]) {
+  tfhe::seeded_round_keys rk;
+  tfhe::seeded::aes_round_keys(seed, rk.w);
+  return rk;
+}
+
+static size_t seeded_bsk_bodies_len(const tfhe_params& p, uint32_t g) {
+  return (size_t)(g > 1 ? (p.n / g) * (1u << g) : p.n) * p.pbs_level * (p.k + 1) * p.N;
+}
+
+// device buffers that live for one call (the uploaded bodies of a seeded load): freed on every path out
+struct temp_buffers {
+  std::vector<std::pair<int, void*>> v;  // (device, pointer)
+  int alloc(int device, size_t bytes, void** out) {
+    DeviceGuard g(device);
+    *out = nullptr;
+    HIP_TRY(hipMalloc(out, bytes ? bytes : 8));
+    v.emplace_back(device, *out);
+    return 0;
+  }
+  ~temp_buffers() {
+    for (auto& x : v) {
+      DeviceGuard g(x.first);
+      (void)hipFree(x.second);
+    }
+  }
+};
+
+// The seeded half of load_keys_impl (caller holds c->mu, has sized every shard's d_bsk / d_ksk / d_stage and waited
+// for their previous users).  Shard 0's stream carries three timed phases (tfhe_hip_seeded_load_stats): the upload
+// of the bodies, the expansion kernels, the conversion.
+static int load_seeded(tfhe_ctx* c, const seeded_src& sd, size_t bsk_len, bool with_ksk, uint32_t g) {
+  const size_t nd = c->sh.size();
+  shard& s0 = c->sh[0];
+  temp_buffers tmp;
+  std::vector<u64*> tb(nd, nullptr), tk(nd, nullptr);
+  for (size_t i = 0; i < nd; i++) {
+    RC_TRY(tmp.alloc(c->sh[i].device, sd.bsk_bodies_len * 8, (void**)&tb[i]));
+    if (with_ksk) RC_TRY(tmp.alloc(c->sh[i].device, sd.ksk_bodies_len * 8, (void**)&tk[i]));
+  }
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  struct ev_guard {
+    hipEvent_t* e;
+    ~ev_guard() {
+      for (int i = 0; i < 5; i++)
+        if (e[i]) (void)hipEventDestroy(e[i]);
+    }
+  } eg{ev};
+  {
+    DeviceGuard gd(s0.device);
+    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(ev[0], s0.stream));
+    RC_TRY(upload_pinned(s0, tb[0], sd.bsk_bodies, sd.bsk_bodies_len * 8));
+    if (with_ksk) RC_TRY(upload_pinned(s0, tk[0], sd.ksk_bodies, sd.ksk_bodies_len * 8));
+    HIP_TRY(hipEventRecord(ev[1], s0.stream));
+  }
+  if (nd > 1 || getenv("TFHE_HIP_BCAST")) {  // bodies, not expanded keys: 1 / (k + 1) and 1 / (n + 1) of the words
+    RC_TRY(broadcast(c, tb[0], tb, sd.bsk_bodies_len));
+    if (with_ksk) RC_TRY(broadcast(c, tk[0], tk, sd.ksk_bodies_len));
+  }
+  const tfhe::seeded_round_keys rk_b = round_keys_of(sd.bsk_seed);
+  const tfhe::seeded_round_keys rk_k = with_ksk ? round_keys_of(sd.ksk_seed) : tfhe::seeded_round_keys{};
+  const tfhe::seeded_shape shp = seeded_shape_of(c->p, g);
+  for (size_t i = 0; i < nd; i++) {
+    shard& s = c->sh[i];
+    {
+      DeviceGuard gd(s.device);
+      if (i == 0) HIP_TRY(hipEventRecord(ev[2], s.stream));
+      HIP_TRY(tfhe::launch_seeded_rows(rk_b, g > 1 ? tfhe::SEEDED_BSK_MB : tfhe::SEEDED_BSK, shp, tb[i], (u64*)s.d_stage,
+                                       s.stream));
+      if (with_ksk) HIP_TRY(tfhe::launch_seeded_rows(rk_k, tfhe::SEEDED_KSK, shp, tk[i], s.d_ksk, s.stream));
+      if (i == 0) HIP_TRY(hipEventRecord(ev[3], s.stream));
+    }
+    RC_TRY(convert_keys(c, s, (const u64*)s.d_stage, bsk_len, with_ksk));  // waits for the shard's stream
+    if (i == 0) {
+      DeviceGuard gd(s.device);
+      HIP_TRY(hipEventRecord(ev[4], s.stream));
+      HIP_TRY(hipEventSynchronize(ev[4]));
+      float up = 0, ex = 0, cv = 0;
+      HIP_TRY(hipEventElapsedTime(&up, ev[0], ev[1]));
+      HIP_TRY(hipEventElapsedTime(&ex, ev[2], ev[3]));
+      HIP_TRY(hipEventElapsedTime(&cv, ev[3], ev[4]));
+      c->seeded_ms[0] = up, c->seeded_ms[1] = ex, c->seeded_ms[2] = cv;
+    }
+  }
+  c->bsk = true;
+  c->keys = with_ksk;
+  c->grouping = g;
+  return 0;
+}
+
 // tfhe_hip_load_keys* (with_ksk) and tfhe_hip_load_bsk* (the BSK half alone; ksk / ksk_len unused); g > 1: a
-// multi-bit key of that grouping factor (tfhe_hip_load_keys_mb), g == 1: a classic key
+// multi-bit key of that grouping factor (tfhe_hip_load_keys_mb), g == 1: a classic key.  sd: a seeded source
+// instead of bsk / ksk (its lengths already checked): bodies go up to shard 0 and on to the other shards, and every
+// shard expands them on its own stream into the buffers that the unseeded route fills by copy.
 static int load_keys_impl(tfhe_ctx* c, const char* what, const uint64_t* bsk, size_t bsk_len, const uint64_t* ksk,
-                          size_t ksk_len, bool with_ksk, bool from_host, uint32_t g = 1) {
-  if (!c || !bsk || (with_ksk && !ksk)) return fail(TFHE_HIP_EINVAL, "%s: null argument", what);
-  if (!with_ksk) ksk_len = tfhe::client::ksk_len(c->p);
+                          size_t ksk_len, bool with_ksk, bool from_host, uint32_t g = 1,
+                          const seeded_src* sd = nullptr) {
+  if (!c || (!sd && (!bsk || (with_ksk && !ksk)))) return fail(TFHE_HIP_EINVAL, "%s: null argument", what);
+  if (!with_ksk || sd) ksk_len = tfhe::client::ksk_len(c->p);
   const size_t want_bsk = g > 1 ? tfhe::client::mb_bsk_len(c->p, g) : tfhe::client::bsk_len(c->p);
+  if (sd) bsk_len = want_bsk;
   if (bsk_len != want_bsk || ksk_len != tfhe::client::ksk_len(c->p))
     return fail(TFHE_HIP_EINVAL, "%s: sizes %zu/%zu, expected %zu/%zu", what, bsk_len, ksk_len, want_bsk,
                 tfhe::client::ksk_len(c->p));
@@ -1159,6 +1305,7 @@ static int load_keys_impl(tfhe_ctx* c, const char* what, const uint64_t* bsk, si
     RC_TRY(ws_grow(s, &s.d_stage, &s.stage_cap, bsk_len * 8));
   }
   shard& s0 = c->sh[0];
+  if (sd) return load_seeded(c, *sd, bsk_len, with_ksk, g);
   const u64* bsk0 = (const u64*)bsk;  // standard BSK on shard 0's device
   {
     DeviceGuard g(s0.device);
@@ -1219,23 +1366,138 @@ int tfhe_hip_load_keys_mb(tfhe_ctx* c, uint32_t g, const uint64_t* bsk_mb, size_
 
 int tfhe_hip_grouping(const tfhe_ctx* c) { return c ? (int)c->grouping : 1; }
 
-int tfhe_hip_load_ms_key(tfhe_ctx* c, const uint64_t* zeros, uint32_t count, double bound, double r_sigma,
-                         double input_variance) {
-  if (!c || (count && !zeros)) return fail(TFHE_HIP_EINVAL, "load_ms_key: bad arguments");
+// ---- seeded loaders: every argument and length check precedes load_keys_impl, which touches the ctx
+static int seeded_load_check(const tfhe_ctx* c, const char* what, uint32_t g, const uint64_t* bsk_seed,
+                             const uint64_t* bsk_bodies, size_t bsk_bodies_len, bool with_ksk, const uint64_t* ksk_seed,
+                             const uint64_t* ksk_bodies, size_t ksk_bodies_len) {
+  if (!c || !bsk_seed || !bsk_bodies || (with_ksk && (!ksk_seed || !ksk_bodies)))
+    return fail(TFHE_HIP_EINVAL, "%s: null argument", what);
+  if (c->p.transform != TFHE_HIP_TRANSFORM_FFT64)
+    return fail(TFHE_HIP_EUNSUPPORTED, "%s: seeded keys exist for the native-torus (FFT64) presets only", what);
+  if (g > 1) {
+    if (!c->eng_mb)
+      return fail(TFHE_HIP_EUNSUPPORTED, "%s: the multi-bit back end covers the FFT64 transform at N = 2048 (PBS 23x1); "
+                                         "this ctx runs transform %u, N = %u", what, c->p.transform, c->p.N);
+    if (!grouping_valid(g) || g < c->eng_mb->g_min || g > c->eng_mb->g_max)
+      return fail(TFHE_HIP_EINVAL, "%s: grouping factor %u, expected 2, 3 or 4", what, g);
+    if (c->p.n % g) return fail(TFHE_HIP_EINVAL, "%s: n = %u is not divisible by the grouping factor %u", what, c->p.n, g);
+  }
+  const size_t want_b = seeded_bsk_bodies_len(c->p, g), want_k = (size_t)c->p.k * c->p.N * c->p.ks_level;
+  if (bsk_bodies_len != want_b || (with_ksk && ksk_bodies_len != want_k))
+    return fail(TFHE_HIP_EINVAL, "%s: body counts %zu/%zu, expected %zu/%zu", what, bsk_bodies_len,
+                with_ksk ? ksk_bodies_len : want_k, want_b, want_k);
+  return 0;
+}
+
+int tfhe_hip_load_keys_seeded(tfhe_ctx* c, const uint64_t bsk_seed[2], const uint64_t* bsk_bodies, size_t bsk_bodies_len,
+                              const uint64_t ksk_seed[2], const uint64_t* ksk_bodies, size_t ksk_bodies_len) {
+  RC_TRY(seeded_load_check(c, "load_keys_seeded", 1, bsk_seed, bsk_bodies, bsk_bodies_len, true, ksk_seed, ksk_bodies,
+                           ksk_bodies_len));
+  const seeded_src sd{bsk_seed, bsk_bodies, bsk_bodies_len, ksk_seed, ksk_bodies, ksk_bodies_len};
+  return load_keys_impl(c, "load_keys_seeded", nullptr, 0, nullptr, 0, true, true, 1, &sd);
+}
+
+int tfhe_hip_load_bsk_seeded(tfhe_ctx* c, const uint64_t seed[2], const uint64_t* bodies, size_t bodies_len) {
+  RC_TRY(seeded_load_check(c, "load_bsk_seeded", 1, seed, bodies, bodies_len, false, nullptr, nullptr, 0));
+  const seeded_src sd{seed, bodies, bodies_len, nullptr, nullptr, 0};
+  return load_keys_impl(c, "load_bsk_seeded", nullptr, 0, nullptr, 0, false, true, 1, &sd);
+}
+
+int tfhe_hip_load_keys_mb_seeded(tfhe_ctx* c, uint32_t g, const uint64_t bsk_seed[2], const uint64_t* bsk_bodies,
+                                 size_t bsk_bodies_len, const uint64_t ksk_seed[2], const uint64_t* ksk_bodies,
+                                 size_t ksk_bodies_len) {
+  if (c && g == 1) return fail(TFHE_HIP_EINVAL, "load_keys_mb_seeded: grouping factor 1, expected 2, 3 or 4");
+  const bool with_ksk = ksk_bodies != nullptr;
+  RC_TRY(seeded_load_check(c, "load_keys_mb_seeded", g, bsk_seed, bsk_bodies, bsk_bodies_len, with_ksk, ksk_seed,
+                           ksk_bodies, ksk_bodies_len));
+  const seeded_src sd{bsk_seed, bsk_bodies, bsk_bodies_len, ksk_seed, ksk_bodies, ksk_bodies_len};
+  return load_keys_impl(c, "load_keys_mb_seeded", nullptr, 0, nullptr, 0, with_ksk, true, g, &sd);
+}
+
+int tfhe_hip_seeded_load_stats(const tfhe_ctx* c, double* upload_ms, double* expand_ms, double* convert_ms) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "seeded_load_stats: null ctx");
+  if (upload_ms) *upload_ms = c->seeded_ms[0];
+  if (expand_ms) *expand_ms = c->seeded_ms[1];
+  if (convert_ms) *convert_ms = c->seeded_ms[2];
+  return 0;
+}
+
+// ---- the expansion kernels alone (test-facing): the launchers the loaders use, on shard 0, into a fresh device
+// buffer of out_len + TFHE_HIP_SEEDED_GUARD_WORDS words filled with 0xA5 bytes, all of which is copied back
+static int seeded_expand_call(tfhe_ctx* c, tfhe::seeded_kind kind, const tfhe::seeded_shape& shp,
+                              const uint64_t seed[2], const uint64_t* bodies, size_t bodies_len, size_t out_len,
+                              uint64_t* out_host) {
+  const tfhe::seeded_round_keys rk = round_keys_of(seed);
+  std::lock_guard<std::mutex> lk(c->mu);
+  shard& s = c->sh[0];
+  DeviceGuard gd(s.device);
+  temp_buffers tmp;
+  u64 *d_bodies = nullptr, *d_out = nullptr;
+  const size_t out_bytes = (out_len + TFHE_HIP_SEEDED_GUARD_WORDS) * 8;
+  RC_TRY(tmp.alloc(s.device, bodies_len * 8, (void**)&d_bodies));
+  RC_TRY(tmp.alloc(s.device, out_bytes, (void**)&d_out));
+  HIP_TRY(hipMemsetAsync(d_out, 0xA5, out_bytes, s.stream));
+  if (bodies_len) HIP_TRY(hipMemcpyAsync(d_bodies, bodies, bodies_len * 8, hipMemcpyHostToDevice, s.stream));
+  HIP_TRY(tfhe::launch_seeded_rows(rk, kind, shp, d_bodies, d_out, s.stream));
+  HIP_TRY(hipMemcpyAsync(out_host, d_out, out_bytes, hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  return 0;
+}
+
+int tfhe_hip_seeded_expand_bsk(tfhe_ctx* c, uint32_t g, const uint64_t seed[2], const uint64_t* bodies,
+                               uint64_t* out_host) {
+  if (c && g == 0) return fail(TFHE_HIP_EINVAL, "seeded_expand_bsk: grouping factor 0");
+  RC_TRY(seeded_load_check(c, "seeded_expand_bsk", g, seed, bodies, c ? seeded_bsk_bodies_len(c->p, g) : 0, false,
+                           nullptr, nullptr, 0));
+  if (!out_host) return fail(TFHE_HIP_EINVAL, "seeded_expand_bsk: null argument");
+  const size_t out_len = g > 1 ? tfhe::client::mb_bsk_len(c->p, g) : tfhe::client::bsk_len(c->p);
+  return seeded_expand_call(c, g > 1 ? tfhe::SEEDED_BSK_MB : tfhe::SEEDED_BSK,
+                            seeded_shape_of(c->p, g), seed, bodies, seeded_bsk_bodies_len(c->p, g), out_len, out_host);
+}
+
+int tfhe_hip_seeded_expand_ksk(tfhe_ctx* c, const uint64_t seed[2], const uint64_t* bodies, uint64_t* out_host) {
+  if (!c || !seed || !bodies || !out_host) return fail(TFHE_HIP_EINVAL, "seeded_expand_ksk: null argument");
+  if (c->p.transform != TFHE_HIP_TRANSFORM_FFT64)
+    return fail(TFHE_HIP_EUNSUPPORTED, "seeded_expand_ksk: seeded keys exist for the native-torus (FFT64) presets only");
+  return seeded_expand_call(c, tfhe::SEEDED_KSK, seeded_shape_of(c->p, 1), seed, bodies,
+                            (size_t)c->p.k * c->p.N * c->p.ks_level, tfhe::client::ksk_len(c->p), out_host);
+}
+
+int tfhe_hip_seeded_expand_lwe_list(tfhe_ctx* c, uint32_t dim, uint32_t count, const uint64_t seed[2],
+                                    const uint64_t* bodies, uint64_t* out_host) {
+  if (!c || !seed || !out_host || (count && !bodies)) return fail(TFHE_HIP_EINVAL, "seeded_expand_lwe_list: null argument");
+  if (dim == 0 || dim > 0x7FFFFFFEu || count > 0x7FFFFFFFu)
+    return fail(TFHE_HIP_EINVAL, "seeded_expand_lwe_list: dim = %u, count = %u out of range", dim, count);
+  tfhe::seeded_shape shp{};
+  shp.n = dim, shp.count = count;
+  return seeded_expand_call(c, tfhe::SEEDED_LIST, shp, seed, bodies, count,
+                            (size_t)count * ((size_t)dim + 1), out_host);
+}
+
+// tfhe_hip_load_ms_key*: the checks behind the argument check, shared by the host and the seeded source
+static int ms_key_check(const tfhe_ctx* c, const char* what, uint32_t count, double bound, double r_sigma,
+                        double input_variance) {
   if (c->grouping > 1)
-    return fail(TFHE_HIP_EUNSUPPORTED, "load_ms_key: multi-bit keys are loaded (grouping %u); the noise-reduction pick "
-                                       "is defined for the per-element modulus switch", c->grouping);
+    return fail(TFHE_HIP_EUNSUPPORTED, "%s: multi-bit keys are loaded (grouping %u); the noise-reduction pick "
+                                       "is defined for the per-element modulus switch", what, c->grouping);
   if (c->p.order != 1 && count)
-    return fail(TFHE_HIP_EUNSUPPORTED, "load_ms_key: the noise reduction runs between keyswitch and blind rotation "
-                                       "(KS -> PBS parameter sets only)");
+    return fail(TFHE_HIP_EUNSUPPORTED, "%s: the noise reduction runs between keyswitch and blind rotation "
+                                       "(KS -> PBS parameter sets only)", what);
   if (count > 0x7FFFFFFF || !(bound >= 0) || !(r_sigma >= 0) || !(input_variance >= 0))
-    return fail(TFHE_HIP_EINVAL, "load_ms_key: count %u / bound / r_sigma / variance out of range", count);
+    return fail(TFHE_HIP_EINVAL, "%s: count %u / bound / r_sigma / variance out of range", what, count);
   // the scan addresses the element-major transpose through a buffer resource with 32-bit byte offsets
   // (ms_reduce.hip): (n + 1) x pitch x 8 must stay below 2^31, or raw loads past num_records would read zeros
   // silently.  n = 918 allows ~292 k zeros; the reference's key carries 1449.
   if ((double)(c->p.n + 1) * (double)tfhe::ms_zeros_pitch(count) * 8.0 >= 0x1p31)
-    return fail(TFHE_HIP_EINVAL, "load_ms_key: %u zeros x %u elements exceed the 2 GiB scan window", count,
+    return fail(TFHE_HIP_EINVAL, "%s: %u zeros x %u elements exceed the 2 GiB scan window", what, count,
                 (unsigned)(c->p.n + 1));
+  return 0;
+}
+
+int tfhe_hip_load_ms_key(tfhe_ctx* c, const uint64_t* zeros, uint32_t count, double bound, double r_sigma,
+                         double input_variance) {
+  if (!c || (count && !zeros)) return fail(TFHE_HIP_EINVAL, "load_ms_key: bad arguments");
+  RC_TRY(ms_key_check(c, "load_ms_key", count, bound, r_sigma, input_variance));
   std::lock_guard<std::mutex> lk(c->mu);
   c->ms_count = 0;
   // two layouts in one allocation: rows [count][n+1] (the add of the chosen zero) then the element-major
@@ -1258,6 +1520,45 @@ int tfhe_hip_load_ms_key(tfhe_ctx* c, const uint64_t* zeros, uint32_t count, dou
     HIP_TRY(hipMalloc(&s.d_ms_zeros, bytes));
     HIP_TRY(hipMemcpy(s.d_ms_zeros, zeros, count * dim * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s.d_ms_zeros + count * dim, tr.data(), tr.size() * 8, hipMemcpyHostToDevice));
+  }
+  c->ms_count = count;
+  c->ms_bound = bound;
+  c->ms_r_sigma = r_sigma;
+  c->ms_var128 = input_variance * 0x1p128;
+  return 0;
+}
+
+// The zeros from their seeded form: count body words go to every shard, which expands the rows [count][n+1] and
+// builds the element-major transpose behind them on its own stream (same allocation and layouts as above).
+int tfhe_hip_load_ms_key_seeded(tfhe_ctx* c, const uint64_t seed[2], const uint64_t* bodies, uint32_t count,
+                                double bound, double r_sigma, double input_variance) {
+  if (!c || (count && (!seed || !bodies))) return fail(TFHE_HIP_EINVAL, "load_ms_key_seeded: bad arguments");
+  if (c->p.transform != TFHE_HIP_TRANSFORM_FFT64)
+    return fail(TFHE_HIP_EUNSUPPORTED, "load_ms_key_seeded: seeded keys exist for the native-torus (FFT64) presets only");
+  RC_TRY(ms_key_check(c, "load_ms_key_seeded", count, bound, r_sigma, input_variance));
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->ms_count = 0;
+  const size_t dim = c->p.n + 1, zp = tfhe::ms_zeros_pitch(count);
+  const size_t bytes = (count * dim + dim * zp) * 8;
+  tfhe::seeded_round_keys rk{};
+  tfhe::seeded_shape shp{};
+  shp.n = c->p.n, shp.count = count;
+  if (count) rk = round_keys_of(seed);
+  for (auto& s : c->sh) {
+    DeviceGuard g(s.device);
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    RC_TRY(ws_host_wait(s));
+    (void)hipFree(s.d_ms_zeros);
+    s.d_ms_zeros = nullptr;
+    if (!count) continue;
+    temp_buffers tmp;
+    u64* d_bodies = nullptr;
+    RC_TRY(tmp.alloc(s.device, (size_t)count * 8, (void**)&d_bodies));
+    HIP_TRY(hipMalloc(&s.d_ms_zeros, bytes));
+    HIP_TRY(hipMemcpyAsync(d_bodies, bodies, (size_t)count * 8, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(tfhe::launch_seeded_rows(rk, tfhe::SEEDED_LIST, shp, d_bodies, s.d_ms_zeros, s.stream));
+    HIP_TRY(tfhe::launch_ms_zeros_transpose(s.d_ms_zeros, count, (u32)dim, s.d_ms_zeros + count * dim, s.stream));
+    HIP_TRY(hipStreamSynchronize(s.stream));  // before the bodies are released
   }
   c->ms_count = count;
   c->ms_bound = bound;

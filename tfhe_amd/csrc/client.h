@@ -60,6 +60,13 @@ void csprng_words(const uint64_t seed[2], uint64_t first, size_t count, uint64_t
 void seeded_server_keygen(const tfhe_params& p, const tfhe_rng_key& rk, const uint64_t bsk_seed[2],
                           const uint64_t ksk_seed[2], const uint64_t* lwe_key, const uint64_t* glwe_key,
                           uint64_t* bsk_bodies, uint64_t* ksk_bodies);
+// multi-bit: bodies [n/g][2^g][L][k+1][N] (seeded.cpp); g in {2, 3, 4}, n % g == 0 and the shape are the caller's checks
+void seeded_mb_server_keygen(const tfhe_params& p, uint32_t g, const tfhe_rng_key& rk, const uint64_t bsk_seed[2],
+                             const uint64_t* lwe_key, const uint64_t* glwe_key, uint64_t* bsk_bodies);
+void decompress_bsk_mb(const tfhe_params& p, uint32_t g, const uint64_t seed[2], const uint64_t* bodies,
+                       uint64_t* bsk_mb);
+// the 44 little-endian round-key words of a seed (the argument of the device kernels in seeded_keys.hip)
+void aes_round_keys(const uint64_t seed[2], uint32_t out[44]);
 void seeded_lwe_list(uint32_t dim, uint32_t count, const uint64_t* key, int32_t noise_log2, const tfhe_rng_key& rk,
                      uint64_t stream0, const uint64_t seed[2], const uint64_t* msgs, uint64_t* bodies);
 void decompress_bsk(const tfhe_params& p, const uint64_t seed[2], const uint64_t* bodies, uint64_t* bsk);

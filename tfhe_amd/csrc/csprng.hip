@@ -12,15 +12,16 @@
 // 4096-row call 4096 workgroups; one long row (a key's mask run) spreads over ceil(dim / 1022) workgroups, each of
 // which recomputes the one or two boundary blocks it shares with its neighbours.
 //
-// LDS (9.9 KB): the T-table Te0 (1 KB, staged once per workgroup from the static table below; Te1..Te3 are byte
-// rotations of it and the S-box is its second byte), the row's 44 round-key words (lane 0 expands the key after
-// the table is staged), and the exchange area: a lane stores the two words of its block as one 16-byte LDS write
-// (odd word with a zero top byte) plus the block's byte 0 into a byte array; after one barrier the lanes read the
+// LDS (9.9 KB): the T-table Te0 (1 KB, staged once per workgroup from the static table of aes_ctr.h, which holds the
+// cipher's round functions for this file and seeded_keys.hip; Te1..Te3 are byte rotations of it and the S-box is its
+// second byte), the row's 44 round-key words (lane 0 expands the key after the table is staged), and the exchange
+// area: a lane stores the two words of its block as one 16-byte LDS write (odd word with a zero top byte) plus the block's byte 0 into a byte array; after one barrier the lanes read the
 // chunk back in word order, OR the straddling byte from the next block into the odd words, and store
 // lane-contiguous 8-byte words (rows are only 8-byte aligned: n + 1 is odd for n = 918).  Every data-dependent
 // lookup of the cipher is an LDS read.
 #include <hip/hip_runtime.h>
 
+#include "aes_ctr.h"
 #include "pbs_kernels.h"
 
 namespace tfhe {
@@ -29,49 +30,6 @@ namespace {
 constexpr int CS_THREADS = 256;
 constexpr int CS_CHUNK = 1022;       // words per workgroup
 constexpr int CS_MAX_BLOCKS = 512;   // AES blocks that CS_CHUNK words can touch
-
-// ---- Te0[x] = (2 S(x), S(x), S(x), 3 S(x)) as a little-endian column, built at compile time from the field
-// arithmetic (FIPS-197 §4.2, §5.1.1; the walk over the multiplicative group is init_sbox of seeded.cpp)
-struct te_table {
-  u32 v[256];
-};
-
-constexpr u32 cs_rotl8(u32 x, int s) { return ((x << s) | (x >> (8 - s))) & 0xffu; }
-
-constexpr te_table make_te0() {
-  te_table t{};
-  u32 sbox[256] = {};
-  u32 p = 1, q = 1;
-  do {
-    p = (p ^ (p << 1) ^ ((p & 0x80u) ? 0x1bu : 0u)) & 0xffu;  // p *= 3
-    q = (q ^ (q << 1)) & 0xffu;                                // q /= 3
-    q = (q ^ (q << 2)) & 0xffu;
-    q = (q ^ (q << 4)) & 0xffu;
-    if (q & 0x80u) q ^= 0x09u;
-    sbox[p] = q ^ cs_rotl8(q, 1) ^ cs_rotl8(q, 2) ^ cs_rotl8(q, 3) ^ cs_rotl8(q, 4) ^ 0x63u;
-  } while (p != 1);
-  sbox[0] = 0x63u;
-  for (int x = 0; x < 256; x++) {
-    const u32 s = sbox[x], s2 = ((s << 1) ^ ((s >> 7) * 0x1bu)) & 0xffu, s3 = s2 ^ s;
-    t.v[x] = s2 | (s << 8) | (s << 16) | (s3 << 24);
-  }
-  return t;
-}
-
-static const __device__ te_table TE0 = make_te0();
-static_assert(make_te0().v[0] == 0xa56363c6u && make_te0().v[0x53] == 0x2cededc1u, "Te0: S(00) = 63, S(53) = ed");
-
-__device__ __forceinline__ u32 rotl32(u32 x, int s) { return (x << s) | (x >> (32 - s)); }
-__device__ __forceinline__ u32 sub_byte(const u32* te, u32 x) { return (te[x] >> 8) & 0xffu; }
-
-// one column of a full round: SubBytes + ShiftRows + MixColumns of the bytes (row r from column c + r)
-__device__ __forceinline__ u32 round_col(const u32* te, u32 a, u32 b, u32 c, u32 d) {
-  return te[a & 0xffu] ^ rotl32(te[(b >> 8) & 0xffu], 8) ^ rotl32(te[(c >> 16) & 0xffu], 16) ^ rotl32(te[d >> 24], 24);
-}
-__device__ __forceinline__ u32 last_col(const u32* te, u32 a, u32 b, u32 c, u32 d) {
-  return sub_byte(te, a & 0xffu) | (sub_byte(te, (b >> 8) & 0xffu) << 8) | (sub_byte(te, (c >> 16) & 0xffu) << 16) |
-         (sub_byte(te, d >> 24) << 24);
-}
 
 // grid: rows * chunks workgroups, index r * chunks + c
 __global__ __launch_bounds__(CS_THREADS) void csprng_rows_kernel(const u64* __restrict__ seeds, unsigned chunks,
@@ -89,44 +47,15 @@ __global__ __launch_bounds__(CS_THREADS) void csprng_rows_kernel(const u64* __re
   const u64 b0 = w_first >> 1;
   const int nblk = (int)(((w_first + cnt) >> 1) - b0) + 1;  // through the block of the last word's top byte; <= 512
 
-  te[tid] = TE0.v[tid];
+  te[tid] = aes::TE0.v[tid];
   __syncthreads();
-  if (tid == 0) {  // AES-128 key expansion (FIPS-197 §5.2) on little-endian words
-    const u64 lo = seeds[2 * r], hi = seeds[2 * r + 1];
-    u32 w0 = (u32)lo, w1 = (u32)(lo >> 32), w2 = (u32)hi, w3 = (u32)(hi >> 32);
-    rk[0] = w0, rk[1] = w1, rk[2] = w2, rk[3] = w3;
-    u32 rcon = 1;
-    for (int i = 1; i <= 10; i++) {
-      const u32 t = (w3 >> 8) | (w3 << 24);  // RotWord
-      w0 ^= last_col(te, t, t, t, t) ^ rcon;
-      w1 ^= w0, w2 ^= w1, w3 ^= w2;
-      rk[4 * i] = w0, rk[4 * i + 1] = w1, rk[4 * i + 2] = w2, rk[4 * i + 3] = w3;
-      rcon = ((rcon << 1) ^ ((rcon >> 7) * 0x1bu)) & 0xffu;
-    }
-  }
+  if (tid == 0) aes::expand_key(te, seeds[2 * r], seeds[2 * r + 1], rk);
   __syncthreads();
 
   for (int j = tid; j < nblk; j += CS_THREADS) {
-    const u64 b = b0 + (u64)j;
-    u32 s0 = (u32)b ^ rk[0], s1 = (u32)(b >> 32) ^ rk[1], s2 = rk[2], s3 = rk[3];
-#pragma unroll
-    for (int round = 1; round < 10; round++) {
-      const u32 t0 = round_col(te, s0, s1, s2, s3) ^ rk[4 * round];
-      const u32 t1 = round_col(te, s1, s2, s3, s0) ^ rk[4 * round + 1];
-      const u32 t2 = round_col(te, s2, s3, s0, s1) ^ rk[4 * round + 2];
-      const u32 t3 = round_col(te, s3, s0, s1, s2) ^ rk[4 * round + 3];
-      s0 = t0, s1 = t1, s2 = t2, s3 = t3;
-    }
-    const u32 o0 = last_col(te, s0, s1, s2, s3) ^ rk[40];
-    const u32 o1 = last_col(te, s1, s2, s3, s0) ^ rk[41];
-    const u32 o2 = last_col(te, s2, s3, s0, s1) ^ rk[42];
-    const u32 o3 = last_col(te, s3, s0, s1, s2) ^ rk[43];
-    const u64 lo = (u64)o0 | ((u64)o1 << 32), hi = (u64)o2 | ((u64)o3 << 32);
-    ulonglong2 pair;
-    pair.x = (lo >> 8) | (hi << 56);  // word 2b: bytes 1..8
-    pair.y = hi >> 8;                 // word 2b + 1: bytes 9..15; its top byte is byte 0 of block b + 1
-    *(ulonglong2*)&wbuf[2 * j] = pair;
-    top[j] = (unsigned char)(o0 & 0xffu);
+    u32 o[4];
+    aes::ctr_block(te, rk, b0 + (u64)j, o);
+    *(ulonglong2*)&wbuf[2 * j] = aes::block_words(o, &top[j]);  // word 2b + 1's top byte is byte 0 of block b + 1
   }
   __syncthreads();
 

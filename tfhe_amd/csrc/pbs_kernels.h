@@ -145,6 +145,27 @@ hipError_t launch_expand_compact(const u64* list, size_t count, int lwe_dim, int
 // rows * ceil(dim / 1022) <= 0x7FFFFFFF (hipErrorInvalidValue otherwise); rows == 0 or dim == 0 launches nothing
 hipError_t launch_csprng_rows(const u64* seeds, size_t rows, u64 first_word, u32 dim, size_t row_stride,
                               bool zero_body, u64* out, hipStream_t s);
+// ---- seeded_keys.hip: seeded (compressed) server keys expanded on the device, into the standard-domain layouts that
+// the conversion kernels read (seeded.cpp decompress_* are the host references).  rk: the 44 round-key words of the
+// key's seed (seeded::aes_round_keys, once per seed on the host).  Shape fields read per kind:
+//   SEEDED_LIST    n (the dimension), count: bodies [count]                       -> out [count][n + 1]
+//   SEEDED_KSK     n, k, N, LV:              bodies [k N][LV]                      -> out [k N][LV - 1 - s][n + 1]
+//   SEEDED_BSK     n, k, N, L:               bodies [n][L][k + 1][N]               -> out [n][c L + l][(k + 1) N]
+//   SEEDED_BSK_MB  n, k, N, L, g:            bodies [n / g][2^g][L][k + 1][N]      -> out [n / g][sigma - 1][l][c][(k + 1) N],
+//                                            sigma = 0 neither read nor written, its stream words stepped over
+// hipErrorInvalidValue for a null buffer, a zero level count, g outside 2..4, n % g != 0 or a grid past 2^31 - 1
+// workgroups; zero rows launch nothing.
+struct seeded_round_keys {
+  u32 w[44];
+};
+enum seeded_kind { SEEDED_LIST = 0, SEEDED_KSK = 1, SEEDED_BSK = 2, SEEDED_BSK_MB = 3 };
+struct seeded_shape {
+  u32 n, k, N, L, LV, g, count;
+};
+hipError_t launch_seeded_rows(const seeded_round_keys& rk, seeded_kind kind, const seeded_shape& sh, const u64* bodies,
+                              u64* out, hipStream_t s);
+// rows [count][dim] -> the element-major transpose [dim][ms_zeros_pitch(count)] behind them (ms_reduce.hip)
+hipError_t launch_ms_zeros_transpose(const u64* rows, u32 count, u32 dim, u64* tr, hipStream_t s);
 // ---- matmul.hip: encrypted matrix x clear matrix.  expand: G seeded GLWEs (seeds G x 2, packed G x ceil(N w / 64)
 // words of w-bit body values) -> glwes G x 2 x N.  dot: glwes R x Kb x 2 x N times the resident matrix W (Kb N x Cpad
 // u32, value + 2^31, zero = 2^31 past K and past C) -> LWE c < C of row r at out + (r * col_stride + c) * (N + 1).

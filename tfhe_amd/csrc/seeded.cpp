@@ -23,6 +23,15 @@
 // A GGSW row c < k of tfhe-rs encrypts -m*g*S_c and row k encrypts m*g (g = 2^(64 - beta (l + 1))); this engine's
 // keygen adds m*g to mask c of an encryption of zero instead.  Both have the same phase, which is all the external
 // product uses, so an ingested row is stored as it is.
+//
+// Multi-bit bootstrapping key (tfhe-rs SeededLweMultiBitBootstrapKey, grouping factor g; PARITY UNPINNED at the byte
+// level like the rest): group q < n/g holds 2^g GGSWs, sigma = 0 .. 2^g - 1, bit i of sigma belonging to key element
+// g q + i; GGSW (q, sigma) encrypts the indicator [(s_{gq+i})_i = bits of sigma] in the row form above.  Bodies
+// [n/g][2^g][L][k+1][N]; stream row rho = ((q 2^g + sigma) L + l)(k+1) + c owns mask words rho k N ... of the seed's
+// stream.  This engine keeps sigma >= 1 only, in [q][sigma - 1][l][c][j][N] (level-major, unlike the classic
+// [i][c L + l]): decompress_bsk_mb ignores the bodies of sigma = 0 and steps over its mask words.  That is valid
+// because sum_sigma indicator_sigma = 1, so tfhe-rs's sum_sigma X^{t_sigma} GGSW_sigma [.] acc equals this engine's
+// acc + sum_{sigma >= 1} (X^{t_sigma} - 1) GGSW_sigma [.] acc up to noise.
 #include <stdint.h>
 #include <string.h>
 
@@ -169,6 +178,17 @@ void add_product(uint32_t N, const uint64_t* a, const uint64_t* s, uint64_t* bod
 
 void aes128_block(const uint8_t key[16], const uint8_t in[16], uint8_t out[16]) { Aes128(key).encrypt(in, out); }
 
+// the 44 round-key words of a seed, little endian (word 4 i + c = column c of round key i): what the device kernels
+// of seeded_keys.hip take, so the key schedule runs once per seed
+void aes_round_keys(const uint64_t seed[2], uint32_t out[44]) {
+  uint8_t key[16];
+  key_bytes(seed, key);
+  const Aes128 aes(key);
+  for (int i = 0; i < 44; i++)
+    out[i] = (uint32_t)aes.rk[4 * i] | ((uint32_t)aes.rk[4 * i + 1] << 8) | ((uint32_t)aes.rk[4 * i + 2] << 16) |
+             ((uint32_t)aes.rk[4 * i + 3] << 24);
+}
+
 void csprng_words(const uint64_t seed[2], uint64_t first, size_t count, uint64_t* out) {
   uint8_t key[16];
   key_bytes(seed, key);
@@ -230,6 +250,40 @@ void seeded_server_keygen(const tfhe_params& p, const tfhe_rng_key& rk, const ui
   }
 }
 
+// seeded multi-bit BSK bodies [n/g][2^g][L][k+1][N] (the header of this file); noise of GGSW (q, sigma) from ChaCha
+// stream 0x700000 + 16 q + sigma
+void seeded_mb_server_keygen(const tfhe_params& p, uint32_t g, const tfhe_rng_key& rk, const uint64_t bsk_seed[2],
+                             const uint64_t* lwe_key, const uint64_t* glwe_key, uint64_t* bsk_bodies) {
+  const uint32_t k = p.k, N = p.N, L = p.pbs_level, per_q = 1u << g;
+  uint8_t key[16];
+  key_bytes(bsk_seed, key);
+  const Aes128 aes(key);
+  parallel_for((int64_t)(p.n / g) * per_q, [&](int64_t idx) {
+    const uint32_t q = (uint32_t)(idx / per_q), sigma = (uint32_t)(idx % per_q);
+    bool ind = true;
+    for (uint32_t i = 0; i < g; i++) ind = ind && lwe_key[(size_t)g * q + i] == ((sigma >> i) & 1u);
+    std::vector<uint64_t> mask((size_t)k * N);
+    std::vector<int64_t> e((size_t)L * (k + 1) * N);
+    client::noise_words(rk, 0x700000 + 16 * (uint64_t)q + sigma, p.glwe_noise_log2, e.size(), e.data());
+    for (uint32_t l = 0; l < L; l++) {
+      const uint64_t gl = 1ull << (64 - p.pbs_base_log * (l + 1));
+      for (uint32_t c = 0; c <= k; c++) {
+        const size_t row = ((size_t)idx * L + l) * (k + 1) + c;
+        mask_words(aes, row * k * N, (size_t)k * N, mask.data());
+        uint64_t* body = bsk_bodies + row * N;
+        for (uint32_t t = 0; t < N; t++) body[t] = (uint64_t)e[((size_t)l * (k + 1) + c) * N + t];
+        for (uint32_t cc = 0; cc < k; cc++) add_product(N, mask.data() + (size_t)cc * N, glwe_key + (size_t)cc * N, body);
+        if (ind) {  // plaintext -m g S_c (row c < k) / m g (row k)
+          if (c < k)
+            for (uint32_t t = 0; t < N; t++) body[t] -= gl * glwe_key[(size_t)c * N + t];
+          else
+            body[0] += gl;
+        }
+      }
+    }
+  });
+}
+
 void seeded_lwe_list(uint32_t dim, uint32_t count, const uint64_t* key, int32_t noise_log2, const tfhe_rng_key& rk,
                      uint64_t stream0, const uint64_t seed[2], const uint64_t* msgs, uint64_t* bodies) {
   uint8_t kb[16];
@@ -260,6 +314,26 @@ void decompress_bsk(const tfhe_params& p, const uint64_t seed[2], const uint64_t
         mask_words(aes, row * k * N, (size_t)k * N, out);
         memcpy(out + (size_t)k * N, bodies + row * N, (size_t)N * 8);
       }
+  });
+}
+
+// the multi-bit key in this engine's layout [q][sigma - 1][l][c][j][N]: sigma = 0 is skipped (its bodies ignored,
+// its mask words stepped over by the source row index)
+void decompress_bsk_mb(const tfhe_params& p, uint32_t g, const uint64_t seed[2], const uint64_t* bodies,
+                       uint64_t* bsk_mb) {
+  const uint32_t k = p.k, N = p.N, L = p.pbs_level, per_q = (1u << g) - 1;
+  const size_t row_len = (size_t)(k + 1) * N, rows_per_ggsw = (size_t)L * (k + 1);
+  uint8_t key[16];
+  key_bytes(seed, key);
+  const Aes128 aes(key);
+  parallel_for((int64_t)(p.n / g) * per_q, [&](int64_t idx) {
+    const size_t q = (size_t)idx / per_q, sigma = (size_t)idx % per_q + 1;
+    for (size_t t = 0; t < rows_per_ggsw; t++) {  // t = l (k + 1) + c in both layouts
+      const size_t src = (q * (per_q + 1) + sigma) * rows_per_ggsw + t;
+      uint64_t* out = bsk_mb + ((size_t)idx * rows_per_ggsw + t) * row_len;
+      mask_words(aes, src * k * N, (size_t)k * N, out);
+      memcpy(out + (size_t)k * N, bodies + src * N, (size_t)N * 8);
+    }
   });
 }
 
