@@ -305,7 +305,18 @@ int tfhe_hip_pbs(tfhe_ctx* ctx, const uint64_t* lwe_in, size_t B, const uint64_t
 /* Device buffers, enqueued on `stream` (hipStream_t; NULL = the shard's stream, TFHE_HIP_NULL_STREAM = the
  * device's legacy null stream, e.g. torch's default stream).  Inputs resident in HBM, on the device of the
  * shard that runs the batch: the first shard whose device holds d_lwe_in.  Calls on different streams
- * are ordered on the shard's workspaces by an event (a later call waits for the previous one's kernels). */
+ * are ordered on the shard's workspaces by an event (a later call waits for the previous one's kernels).
+ * What a call touches of the caller's memory (tests/test_gpu_device_buffers.py pins it with guard rows on every
+ * blind-rotation kernel, both keyswitch kernels and both forms of the many-LUT extraction; the same holds for
+ * tfhe_hip_pbs_many_async and tfhe_hip_bootstrap_async): it writes exactly the B rows of d_lwe_out (B * n_fn rows for
+ * the many-LUT call) and nothing else; it reads rows 0 .. B - 1 of d_lwe_in and nothing past them (a padded workgroup
+ * reruns row B - 1 and stores nothing), n_lut * N words of d_luts and B entries of d_lut_index.
+ * Alignment: every kernel loads d_lwe_in and d_luts and stores d_lwe_out as single 8-byte words (4-byte halves at
+ * most), because rows of n + 1 or kN + 1 words leave every second row of an odd length 8-byte aligned whatever the
+ * base is.  The three pointers therefore need the natural 8-byte alignment of uint64_t and no more, d_lut_index 4
+ * bytes.  The 16-byte loads of the many-LUT extraction read the ctx's own accumulator workspace (its launcher refuses
+ * any other alignment), never a caller's buffer.  The guard-row tests run at the 16-byte-aligned bases a fresh
+ * allocation gives. */
 #define TFHE_HIP_NULL_STREAM ((void*)(intptr_t)-1)
 int tfhe_hip_pbs_async(tfhe_ctx* ctx, const uint64_t* d_lwe_in, size_t B, const uint64_t* d_luts, size_t n_lut,
                        const uint32_t* d_lut_index, uint64_t* d_lwe_out, void* stream);

@@ -9,6 +9,7 @@ import pytest
 
 import tfhe_amd
 from tfhe_amd import compression as C
+import guard_rows as G
 import test_decompress as T
 
 pytestmark = pytest.mark.gpu
@@ -56,10 +57,11 @@ def test_unpack_extract_sweep(oracle_mod, k, N, lpg, w, counts):
             got = packer.unpack_extract(comp)
             assert got.shape == ref.shape
             assert np.array_equal(got, ref), f"host form, count {count}: rows {np.nonzero((got != ref).any(1))[0][:8]}"
-            d_out = to_dev(np.zeros_like(ref))
+            whole, d_out = G.guarded(count, ref.shape[1])
             packer.unpack_extract_async(to_dev(packed), count, d_out)
             got = to_host(d_out)
             assert np.array_equal(got, ref), f"async form, count {count}: rows {np.nonzero((got != ref).any(1))[0][:8]}"
+            G.assert_guards(whole, count, f"unpack_extract_async, {k} x {N}, {lpg} per GLWE, count {count}")
     finally:
         packer.close()
     # degree 0 (every j > 0 negated) in every shape; degree N - 1 (nothing negated) wherever a group is full
@@ -125,6 +127,9 @@ def product_side(cs):
     return dk, comp
 
 
+SMALLEST_E2E = min(T.E2E_SHAPES, key=lambda s: (s[5], tfhe_amd.Params.preset(s[0]).N))  # fewest rows, then the shorter
+
+
 @pytest.mark.parametrize("shape", T.E2E_SHAPES, ids=lambda s: "p%d-%dx%d-%d-%d" % s[:5])
 def test_decompress_end_to_end(shape, oracle_mod, request):
     O = oracle_mod
@@ -141,6 +146,11 @@ def test_decompress_end_to_end(shape, oracle_mod, request):
         assert np.array_equal(T.decode(cs.phases(out)), cs.msgs)
         d_lut = to_dev(T.identity_lut(O, N))
         assert np.array_equal(to_host(dec.decompress_device(to_dev(cs.packed), cs.count, d_lut)), ref)
+        if shape == SMALLEST_E2E:  # the rotation's write-big epilogue behind the unpack kernel, between guard rows
+            whole, d_out = G.guarded(cs.count, ref.shape[1])
+            dec.decompress_async(to_dev(cs.packed), cs.count, d_lut, d_out)
+            assert np.array_equal(to_host(d_out), ref)
+            G.assert_guards(whole, cs.count, "decompress_async, shape %s" % (shape,))
         # a non-identity LUT on the odd rows, through lut_index
         idx = (np.arange(cs.count) % 2).astype(np.uint32)
         odd = [q for q in rows if q % 2]

@@ -10,6 +10,7 @@ import pytest
 import tfhe_amd
 from tfhe_amd import ctlist
 from tfhe_amd import radix as R
+import guard_rows as G
 import test_expand as E
 from test_ctlist import _fixtures
 
@@ -59,10 +60,11 @@ def test_expand_sweep(plain_engine, N, counts, reps):
                 got = eng.expand_compact(words, N, count, rep, rows)
                 assert got.shape == ref.shape
                 assert np.array_equal(got, ref), f"host form, count {count} rep {rep} rows {rows}: rows {first_rows(got, ref)}"
-                d_out = to_dev(np.zeros_like(ref))
+                whole, d_out = G.guarded(rows, N + 1)  # rows = count * rep - 1: the kernel must stop one row early
                 eng.expand_compact_async(d_words, N, count, d_out, rep, rows)
                 got = to_host(d_out)
                 assert np.array_equal(got, ref), f"async form, count {count} rep {rep} rows {rows}: rows {first_rows(got, ref)}"
+                G.assert_guards(whole, rows, f"expand_compact_async, N {N} count {count} rep {rep} rows {rows}")
         got = to_host(eng.expand_compact_device(d_words, N, count))  # the defaults: rep 1, every row
         assert np.array_equal(got, ex), f"device form, count {count}: rows {first_rows(got, ex)}"
         assert np.array_equal(ctlist.expand_device(eng, cl), ex)
@@ -106,6 +108,11 @@ def test_expand_cast_small_shape():
             d = eng.expand_cast_device(to_dev(words), cs.cl.count, to_dev(cs.luts), cs.REP,
                                        d_lut_index=idx_dev(cs.idx))
             assert np.array_equal(to_host(d), ref), f"async form on {kernel}: rows {first_rows(to_host(d), ref)}"
+            whole, d_out = G.guarded(cs.rows, ref.shape[1])
+            d_words, d_luts, d_idx = to_dev(words), to_dev(cs.luts), idx_dev(cs.idx)
+            eng.expand_cast_async(d_words, cs.cl.count, d_luts, d_out, cs.REP, d_lut_index=d_idx)
+            assert np.array_equal(to_host(d_out), ref), f"guarded async form on {kernel}: rows {first_rows(to_host(d_out), ref)}"
+            G.assert_guards(whole, cs.rows, f"expand_cast_async on {kernel}")
             # an odd block count, and one LUT for every row
             odd = eng.expand_cast(words, cs.cl.count, cs.luts, cs.REP, rows=cs.rows - 1, lut_index=cs.idx[:-1])
             assert np.array_equal(odd, ref[:-1])

@@ -747,7 +747,9 @@ class Engine:
 
     def pbs_async(self, d_in, d_luts, d_out, d_lut_index=None, stream=None) -> None:
         """Device-resident batch (torch tensors on this device), enqueued on ``stream``
-        (a torch.cuda.Stream or raw handle; default torch's current stream if torch is loaded)."""
+        (a torch.cuda.Stream or raw handle; default torch's current stream if torch is loaded).  The call writes
+        exactly the B rows of ``d_out`` and nothing else, and reads nothing past row B of ``d_in``.  The kernels access
+        ``d_in``, ``d_luts`` and ``d_out`` as 8-byte words: the natural alignment of the words is all they need."""
         head, tail = self._pbs_async_args(d_in, d_luts, d_lut_index, d_out, stream)
         _check(lib().tfhe_hip_pbs_async(*head, *tail))
 
@@ -771,7 +773,8 @@ class Engine:
 
     def bootstrap_async(self, d_in, d_luts, d_out, d_lut_index=None, stream=None) -> None:
         """Device-resident ``bootstrap`` (torch tensors on this device: d_in (B, n+1), d_out (B, kN+1)), enqueued
-        on ``stream`` like ``pbs_async``."""
+        on ``stream`` like ``pbs_async``.  The call writes exactly the B rows of ``d_out`` and nothing else, and reads
+        nothing past row B of ``d_in``; 8-byte alignment of ``d_in``, ``d_luts`` and ``d_out`` is all the kernels need."""
         head, tail = self._pbs_async_args(d_in, d_luts, d_lut_index, d_out, stream)
         _check(lib().tfhe_hip_bootstrap_async(*head, *tail))
 
@@ -797,7 +800,9 @@ class Engine:
 
     def pbs_many_async(self, d_in, d_luts, d_out, n_fn: int, stride: int, d_lut_index=None, stream=None) -> None:
         """Device-resident ``pbs_many`` (torch tensors on this device; d_out: (B, n_fn, dim+1)), enqueued on
-        ``stream`` like ``pbs_async``."""
+        ``stream`` like ``pbs_async``.  The call writes exactly the B * n_fn rows of ``d_out`` and nothing else, and
+        reads nothing past row B of ``d_in``; 8-byte alignment of ``d_in``, ``d_luts`` and ``d_out`` is all the kernels
+        need (the 16-byte loads of the extraction read the engine's own accumulator workspace)."""
         head, tail = self._pbs_async_args(d_in, d_luts, d_lut_index, d_out, stream)
         _check(lib().tfhe_hip_pbs_many_async(*head, int(n_fn), int(stride), *tail))
 
