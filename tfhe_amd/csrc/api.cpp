@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -921,20 +922,29 @@ static bool mb_scope(const tfhe_params* p) {
          p->pbs_level == 1;
 }
 
+// the grouping factor of a multi-bit key: 2, 3 or 4 (include/tfhe_hip.h)
+static bool grouping_valid(uint32_t g) { return g >= 2 && g <= 4; }
+
+// the refusals of every parameter-level multi-bit call (key generation, seeded key generation, host decompression)
+static int mb_params_check(const char* what, const tfhe_params* p, uint32_t g) {
+  if (!grouping_valid(g)) return fail(TFHE_HIP_EINVAL, "%s: grouping factor %u, expected 2, 3 or 4", what, g);
+  if (p->n % g) return fail(TFHE_HIP_EINVAL, "%s: n = %u is not divisible by the grouping factor %u", what, p->n, g);
+  if (!mb_scope(p))
+    return fail(TFHE_HIP_EUNSUPPORTED, "%s: multi-bit keys cover FFT64, k = 1, N = 2048, PBS 23x1; got transform %u "
+                                       "k=%u N=%u pbs %ux%u", what, p->transform, p->k, p->N, p->pbs_base_log,
+                p->pbs_level);
+  return 0;
+}
+
 size_t tfhe_hip_mb_bsk_len(const tfhe_params* p, uint32_t g) {
-  return params_valid(p) && g >= 2 && g <= 4 && p->n % g == 0 ? tfhe::client::mb_bsk_len(*p, g) : 0;
+  return params_valid(p) && grouping_valid(g) && p->n % g == 0 ? tfhe::client::mb_bsk_len(*p, g) : 0;
 }
 
 int tfhe_hip_mb_server_keygen_k(const tfhe_params* p, uint32_t g, const tfhe_rng_key* rk, const uint64_t* lwe_key,
                                 const uint64_t* glwe_key, uint64_t* bsk_mb, uint64_t* ksk) {
   if (!params_valid(p) || !rk || !lwe_key || !glwe_key || !bsk_mb)
     return fail(TFHE_HIP_EINVAL, "mb_server_keygen: bad arguments");
-  if (g < 2 || g > 4) return fail(TFHE_HIP_EINVAL, "mb_server_keygen: grouping factor %u, expected 2, 3 or 4", g);
-  if (p->n % g) return fail(TFHE_HIP_EINVAL, "mb_server_keygen: n = %u is not divisible by the grouping factor %u", p->n, g);
-  if (!mb_scope(p))
-    return fail(TFHE_HIP_EUNSUPPORTED, "mb_server_keygen: multi-bit keys cover FFT64, k = 1, N = 2048, PBS 23x1; got "
-                                       "transform %u k=%u N=%u pbs %ux%u", p->transform, p->k, p->N, p->pbs_base_log,
-                p->pbs_level);
+  RC_TRY(mb_params_check("mb_server_keygen", p, g));
   RC_TRY(check_binary(lwe_key, p->n, "mb_server_keygen: lwe_key"));
   RC_TRY(check_binary(glwe_key, (size_t)p->k * p->N, "mb_server_keygen: glwe_key"));
   tfhe::client::mb_server_keygen(*p, g, *rk, lwe_key, glwe_key, bsk_mb, ksk);
@@ -1011,21 +1021,8 @@ int tfhe_hip_decompress_lwe_list(uint32_t dim, uint32_t count, const uint64_t se
   return 0;
 }
 
-// the refusals shared by the two host calls of the seeded multi-bit key: those of tfhe_hip_load_keys_mb
-static int seeded_mb_check(const char* what, const tfhe_params* p, uint32_t g) {
-  if (g < 2 || g > 4) return fail(TFHE_HIP_EINVAL, "%s: grouping factor %u, expected 2, 3 or 4", what, g);
-  if (p->n % g) return fail(TFHE_HIP_EINVAL, "%s: n = %u is not divisible by the grouping factor %u", what, p->n, g);
-  if (!mb_scope(p))
-    return fail(TFHE_HIP_EUNSUPPORTED, "%s: multi-bit keys cover FFT64, k = 1, N = 2048, PBS 23x1; got transform %u "
-                                       "k=%u N=%u pbs %ux%u", what, p->transform, p->k, p->N, p->pbs_base_log,
-                p->pbs_level);
-  return 0;
-}
-
 size_t tfhe_hip_seeded_mb_bodies_len(const tfhe_params* p, uint32_t g) {
-  return params_valid(p) && g >= 2 && g <= 4 && p->n % g == 0
-             ? (size_t)(p->n / g) * (1u << g) * p->pbs_level * (p->k + 1) * p->N
-             : 0;
+  return params_valid(p) && grouping_valid(g) && p->n % g == 0 ? tfhe::client::bsk_bodies_len(*p, g) : 0;
 }
 
 int tfhe_hip_seeded_mb_server_keygen_k(const tfhe_params* p, uint32_t g, const tfhe_rng_key* rk,
@@ -1033,7 +1030,7 @@ int tfhe_hip_seeded_mb_server_keygen_k(const tfhe_params* p, uint32_t g, const t
                                        uint64_t* bsk_bodies) {
   if (!params_valid(p) || !rk || !bsk_seed || !lwe_key || !glwe_key || !bsk_bodies)
     return fail(TFHE_HIP_EINVAL, "seeded_mb_server_keygen: bad arguments");
-  RC_TRY(seeded_mb_check("seeded_mb_server_keygen", p, g));
+  RC_TRY(mb_params_check("seeded_mb_server_keygen", p, g));
   RC_TRY(check_binary(lwe_key, p->n, "seeded_mb_server_keygen: lwe_key"));
   RC_TRY(check_binary(glwe_key, (size_t)p->k * p->N, "seeded_mb_server_keygen: glwe_key"));
   tfhe::seeded::seeded_mb_server_keygen(*p, g, *rk, bsk_seed, lwe_key, glwe_key, bsk_bodies);
@@ -1043,7 +1040,7 @@ int tfhe_hip_seeded_mb_server_keygen_k(const tfhe_params* p, uint32_t g, const t
 int tfhe_hip_decompress_bsk_mb(const tfhe_params* p, uint32_t g, const uint64_t seed[2], const uint64_t* bodies,
                                uint64_t* bsk_mb) {
   if (!params_valid(p) || !seed || !bodies || !bsk_mb) return fail(TFHE_HIP_EINVAL, "decompress_bsk_mb: bad arguments");
-  RC_TRY(seeded_mb_check("decompress_bsk_mb", p, g));
+  RC_TRY(mb_params_check("decompress_bsk_mb", p, g));
   tfhe::seeded::decompress_bsk_mb(*p, g, seed, bodies, bsk_mb);
   return 0;
 }
@@ -1151,17 +1148,59 @@ int tfhe_hip_bcast_plan(const int* devices, int ndev, const char* policy, int rc
   return n < 0 ? fail(n, "bcast_plan: %s", why.c_str()) : n;
 }
 
-// the grouping factor of a multi-bit key: 2, 3 or 4 (include/tfhe_hip.h)
-static bool grouping_valid(uint32_t g) { return g >= 2 && g <= 4; }
+// ---- key loading: every tfhe_hip_load_keys* / tfhe_hip_load_bsk* call fills one key_load, key_load_check holds every
+// refusal (all of them precede the first change of the ctx), key_load_run is the one pipeline.
+enum key_source { SRC_HOST, SRC_DEVICE, SRC_SEEDED };
 
-// A seeded key source of load_keys_impl (tfhe_hip_load_*_seeded): seeds and HOST body buffers in the container's
-// layouts (include/tfhe_hip.h).  Only bodies and round keys travel; every shard expands into its own d_stage / d_ksk.
-struct seeded_src {
-  const uint64_t *bsk_seed, *bsk_bodies;
-  size_t bsk_bodies_len;
-  const uint64_t *ksk_seed, *ksk_bodies;  // unused without a KSK
-  size_t ksk_bodies_len;
+// What a load call asked for.  The words that travel to shard 0 and on to the other shards are the standard-domain
+// keys of a host or device source and the bodies of a seeded one (include/tfhe_hip.h has the layouts).
+struct key_load {
+  const char* what;  // the call's name, the prefix of its messages
+  key_source src;
+  const uint64_t* bsk;
+  size_t bsk_len;
+  const uint64_t* ksk = nullptr;
+  size_t ksk_len = 0;
+  bool with_ksk = false;  // false: the BSK alone (ksk, ksk_len, ksk_seed unused), a rotation-only engine
+  const uint64_t *bsk_seed = nullptr, *ksk_seed = nullptr;  // SRC_SEEDED only
+  bool multi_bit = false;  // a multi-bit entry point: g must be a grouping factor; otherwise a classic key, g == 1
+  uint32_t g = 1;
 };
+
+static size_t std_bsk_len(const tfhe_params& p, uint32_t g) {
+  return g > 1 ? tfhe::client::mb_bsk_len(p, g) : tfhe::client::bsk_len(p);
+}
+
+static int native_torus_check(const tfhe_ctx* c, const char* what) {
+  if (c->p.transform != TFHE_HIP_TRANSFORM_FFT64)
+    return fail(TFHE_HIP_EUNSUPPORTED, "%s: seeded keys exist for the native-torus (FFT64) presets only", what);
+  return 0;
+}
+
+// can this ctx hold a multi-bit key of grouping factor g
+static int mb_key_check(const tfhe_ctx* c, const char* what, uint32_t g) {
+  if (!c->eng_mb)
+    return fail(TFHE_HIP_EUNSUPPORTED, "%s: the multi-bit back end covers the FFT64 transform at N = 2048 (PBS 23x1); "
+                                       "this ctx runs transform %u, N = %u", what, c->p.transform, c->p.N);
+  if (!grouping_valid(g) || g < c->eng_mb->g_min || g > c->eng_mb->g_max)
+    return fail(TFHE_HIP_EINVAL, "%s: grouping factor %u, expected 2, 3 or 4", what, g);
+  if (c->p.n % g) return fail(TFHE_HIP_EINVAL, "%s: n = %u is not divisible by the grouping factor %u", what, c->p.n, g);
+  return 0;
+}
+
+static int key_load_check(const tfhe_ctx* c, const key_load& r) {
+  const bool seeded = r.src == SRC_SEEDED;
+  if (!c || !r.bsk || (r.with_ksk && !r.ksk) || (seeded && (!r.bsk_seed || (r.with_ksk && !r.ksk_seed))))
+    return fail(TFHE_HIP_EINVAL, "%s: null argument", r.what);
+  if (seeded) RC_TRY(native_torus_check(c, r.what));
+  if (r.multi_bit) RC_TRY(mb_key_check(c, r.what, r.g));
+  const size_t want_b = seeded ? tfhe::client::bsk_bodies_len(c->p, r.g) : std_bsk_len(c->p, r.g);
+  const size_t want_k = seeded ? tfhe::client::ksk_bodies_len(c->p) : tfhe::client::ksk_len(c->p);
+  if (r.bsk_len != want_b || (r.with_ksk && r.ksk_len != want_k))
+    return fail(TFHE_HIP_EINVAL, "%s: %s %zu/%zu, expected %zu/%zu", r.what, seeded ? "body counts" : "sizes", r.bsk_len,
+                r.with_ksk ? r.ksk_len : want_k, want_b, want_k);
+  return 0;
+}
 
 static tfhe::seeded_shape seeded_shape_of(const tfhe_params& p, uint32_t g, uint32_t count = 0) {
   return tfhe::seeded_shape{p.n, p.k, p.N, p.pbs_level, p.ks_level, g, count};
@@ -1171,10 +1210,6 @@ static tfhe::seeded_round_keys round_keys_of(const uint64_t seed[2]) {
   tfhe::seeded_round_keys rk;
   tfhe::seeded::aes_round_keys(seed, rk.w);
   return rk;
-}
-
-static size_t seeded_bsk_bodies_len(const tfhe_params& p, uint32_t g) {
-  return (size_t)(g > 1 ? (p.n / g) * (1u << g) : p.n) * p.pbs_level * (p.k + 1) * p.N;
 }
 
 // device buffers that live for one call (the uploaded bodies of a seeded load): freed on every path out
@@ -1195,92 +1230,47 @@ struct temp_buffers {
   }
 };
 
-// The seeded half of load_keys_impl (caller holds c->mu, has sized every shard's d_bsk / d_ksk / d_stage and waited
-// for their previous users).  Shard 0's stream carries three timed phases (tfhe_hip_seeded_load_stats): the upload
-// of the bodies, the expansion kernels, the conversion.
-static int load_seeded(tfhe_ctx* c, const seeded_src& sd, size_t bsk_len, bool with_ksk, uint32_t g) {
-  const size_t nd = c->sh.size();
-  shard& s0 = c->sh[0];
-  temp_buffers tmp;
-  std::vector<u64*> tb(nd, nullptr), tk(nd, nullptr);
-  for (size_t i = 0; i < nd; i++) {
-    RC_TRY(tmp.alloc(c->sh[i].device, sd.bsk_bodies_len * 8, (void**)&tb[i]));
-    if (with_ksk) RC_TRY(tmp.alloc(c->sh[i].device, sd.ksk_bodies_len * 8, (void**)&tk[i]));
+// device-time marks on one shard's stream, destroyed with the scope; without a shard mark() does nothing
+struct stream_marks {
+  shard* s;
+  std::vector<hipEvent_t> ev;
+  int mark() {
+    if (!s) return 0;
+    DeviceGuard g(s->device);
+    hipEvent_t e = nullptr;
+    HIP_TRY(hipEventCreate(&e));
+    ev.push_back(e);
+    HIP_TRY(hipEventRecord(e, s->stream));
+    return 0;
   }
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  struct ev_guard {
-    hipEvent_t* e;
-    ~ev_guard() {
-      for (int i = 0; i < 5; i++)
-        if (e[i]) (void)hipEventDestroy(e[i]);
-    }
-  } eg{ev};
-  {
-    DeviceGuard gd(s0.device);
-    for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(ev[0], s0.stream));
-    RC_TRY(upload_pinned(s0, tb[0], sd.bsk_bodies, sd.bsk_bodies_len * 8));
-    if (with_ksk) RC_TRY(upload_pinned(s0, tk[0], sd.ksk_bodies, sd.ksk_bodies_len * 8));
-    HIP_TRY(hipEventRecord(ev[1], s0.stream));
+  int ms(size_t from, size_t to, double* out) {  // waits for mark `to`
+    DeviceGuard g(s->device);
+    float t = 0;
+    HIP_TRY(hipEventSynchronize(ev[to]));
+    HIP_TRY(hipEventElapsedTime(&t, ev[from], ev[to]));
+    *out = t;
+    return 0;
   }
-  if (nd > 1 || getenv("TFHE_HIP_BCAST")) {  // bodies, not expanded keys: 1 / (k + 1) and 1 / (n + 1) of the words
-    RC_TRY(broadcast(c, tb[0], tb, sd.bsk_bodies_len));
-    if (with_ksk) RC_TRY(broadcast(c, tk[0], tk, sd.ksk_bodies_len));
+  ~stream_marks() {
+    for (auto e : ev) (void)hipEventDestroy(e);
   }
-  const tfhe::seeded_round_keys rk_b = round_keys_of(sd.bsk_seed);
-  const tfhe::seeded_round_keys rk_k = with_ksk ? round_keys_of(sd.ksk_seed) : tfhe::seeded_round_keys{};
-  const tfhe::seeded_shape shp = seeded_shape_of(c->p, g);
-  for (size_t i = 0; i < nd; i++) {
-    shard& s = c->sh[i];
-    {
-      DeviceGuard gd(s.device);
-      if (i == 0) HIP_TRY(hipEventRecord(ev[2], s.stream));
-      HIP_TRY(tfhe::launch_seeded_rows(rk_b, g > 1 ? tfhe::SEEDED_BSK_MB : tfhe::SEEDED_BSK, shp, tb[i], (u64*)s.d_stage,
-                                       s.stream));
-      if (with_ksk) HIP_TRY(tfhe::launch_seeded_rows(rk_k, tfhe::SEEDED_KSK, shp, tk[i], s.d_ksk, s.stream));
-      if (i == 0) HIP_TRY(hipEventRecord(ev[3], s.stream));
-    }
-    RC_TRY(convert_keys(c, s, (const u64*)s.d_stage, bsk_len, with_ksk));  // waits for the shard's stream
-    if (i == 0) {
-      DeviceGuard gd(s.device);
-      HIP_TRY(hipEventRecord(ev[4], s.stream));
-      HIP_TRY(hipEventSynchronize(ev[4]));
-      float up = 0, ex = 0, cv = 0;
-      HIP_TRY(hipEventElapsedTime(&up, ev[0], ev[1]));
-      HIP_TRY(hipEventElapsedTime(&ex, ev[2], ev[3]));
-      HIP_TRY(hipEventElapsedTime(&cv, ev[3], ev[4]));
-      c->seeded_ms[0] = up, c->seeded_ms[1] = ex, c->seeded_ms[2] = cv;
-    }
-  }
-  c->bsk = true;
-  c->keys = with_ksk;
-  c->grouping = g;
-  return 0;
-}
+};
 
-// tfhe_hip_load_keys* (with_ksk) and tfhe_hip_load_bsk* (the BSK half alone; ksk / ksk_len unused); g > 1: a
-// multi-bit key of that grouping factor (tfhe_hip_load_keys_mb), g == 1: a classic key.  sd: a seeded source
-// instead of bsk / ksk (its lengths already checked): bodies go up to shard 0 and on to the other shards, and every
-// shard expands them on its own stream into the buffers that the unseeded route fills by copy.
-static int load_keys_impl(tfhe_ctx* c, const char* what, const uint64_t* bsk, size_t bsk_len, const uint64_t* ksk,
-                          size_t ksk_len, bool with_ksk, bool from_host, uint32_t g = 1,
-                          const seeded_src* sd = nullptr) {
-  if (!c || (!sd && (!bsk || (with_ksk && !ksk)))) return fail(TFHE_HIP_EINVAL, "%s: null argument", what);
-  if (!with_ksk || sd) ksk_len = tfhe::client::ksk_len(c->p);
-  const size_t want_bsk = g > 1 ? tfhe::client::mb_bsk_len(c->p, g) : tfhe::client::bsk_len(c->p);
-  if (sd) bsk_len = want_bsk;
-  if (bsk_len != want_bsk || ksk_len != tfhe::client::ksk_len(c->p))
-    return fail(TFHE_HIP_EINVAL, "%s: sizes %zu/%zu, expected %zu/%zu", what, bsk_len, ksk_len, want_bsk,
-                tfhe::client::ksk_len(c->p));
+// The pipeline of a checked load.  A seeded load leaves its three phases on shard 0's stream in c->seeded_ms
+// (tfhe_hip_seeded_load_stats): marks 0-1 the upload, 2-3 the expansion, 3-4 the conversion.
+static int key_load_run(tfhe_ctx* c, const key_load& r) {
+  const bool seeded = r.src == SRC_SEEDED, with_ksk = r.with_ksk;
+  const size_t nd = c->sh.size(), bsk_len = std_bsk_len(c->p, r.g), ksk_len = tfhe::client::ksk_len(c->p);
+  // 1. prepare
   std::lock_guard<std::mutex> lk(c->mu);
   c->keys = c->bsk = false;  // after a BSK-only load an earlier KSK belongs to another key set: rotation-only
   c->grouping = 1;
   c->bcast_mode = 0;
-  if (g > 1) {
+  if (r.g > 1) {
     c->ms_count = 0;  // the noise-reduction pick is defined for the per-element switch
     std::vector<u64> tw(c->eng_mb->table_words);
     if (!c->eng_mb->make_tables(tw.data()))
-      return fail(TFHE_HIP_EUNSUPPORTED, "%s: the host root table's entry 0 is not exactly 1", what);
+      return fail(TFHE_HIP_EUNSUPPORTED, "%s: the host root table's entry 0 is not exactly 1", r.what);
     for (auto& s : c->sh) {
       if (s.d_tw_mb) continue;
       DeviceGuard gd(s.device);
@@ -1288,7 +1278,6 @@ static int load_keys_impl(tfhe_ctx* c, const char* what, const uint64_t* bsk, si
       HIP_TRY(hipMemcpy(s.d_tw_mb, tw.data(), tw.size() * 8, hipMemcpyHostToDevice));
     }
   }
-  const size_t nd = c->sh.size();
   // every shard: key buffers + a standard-domain BSK staging area (its d_stage)
   for (auto& s : c->sh) {
     DeviceGuard g(s.device);
@@ -1304,114 +1293,112 @@ static int load_keys_impl(tfhe_ctx* c, const char* what, const uint64_t* bsk, si
     if (with_ksk && !s.d_ksk) HIP_TRY(hipMalloc(&s.d_ksk, ksk_len * 8));
     RC_TRY(ws_grow(s, &s.d_stage, &s.stage_cap, bsk_len * 8));
   }
+  // 2. travel: onto shard 0, then to every other shard, once.  Standard keys land where the conversion reads them;
+  // bodies (1 / (k + 1) and 1 / (n + 1) of the words) in temporaries, which the conversion's stream synchronise of
+  // every shard precedes the release of.
+  temp_buffers tmp;
+  std::vector<u64*> dst_b(nd), dst_k(nd);
+  for (size_t i = 0; i < nd; i++) {
+    shard& s = c->sh[i];
+    dst_b[i] = (u64*)s.d_stage, dst_k[i] = s.d_ksk;
+    if (!seeded) continue;
+    RC_TRY(tmp.alloc(s.device, r.bsk_len * 8, (void**)&dst_b[i]));
+    if (with_ksk) RC_TRY(tmp.alloc(s.device, r.ksk_len * 8, (void**)&dst_k[i]));
+  }
   shard& s0 = c->sh[0];
-  if (sd) return load_seeded(c, *sd, bsk_len, with_ksk, g);
-  const u64* bsk0 = (const u64*)bsk;  // standard BSK on shard 0's device
+  stream_marks tm{seeded ? &s0 : nullptr, {}};
+  // a device source is read in place on shard 0: the caller's BSK is broadcast and converted without a copy
+  const u64* bsk0 = r.src == SRC_DEVICE ? (const u64*)r.bsk : dst_b[0];
   {
     DeviceGuard g(s0.device);
-    if (from_host) {
-      RC_TRY(upload_pinned(s0, s0.d_stage, bsk, bsk_len * 8));
-      if (with_ksk) RC_TRY(upload_pinned(s0, s0.d_ksk, ksk, ksk_len * 8));
-      bsk0 = (const u64*)s0.d_stage;
+    RC_TRY(tm.mark());
+    if (r.src != SRC_DEVICE) {
+      RC_TRY(upload_pinned(s0, dst_b[0], r.bsk, r.bsk_len * 8));
+      if (with_ksk) RC_TRY(upload_pinned(s0, dst_k[0], r.ksk, r.ksk_len * 8));
     } else if (with_ksk) {
-      HIP_TRY(hipMemcpyAsync(s0.d_ksk, ksk, ksk_len * 8, hipMemcpyDeviceToDevice, s0.stream));
+      HIP_TRY(hipMemcpyAsync(dst_k[0], r.ksk, r.ksk_len * 8, hipMemcpyDeviceToDevice, s0.stream));
       HIP_TRY(hipStreamSynchronize(s0.stream));
     }
+    RC_TRY(tm.mark());
   }
-  if (nd > 1 || getenv("TFHE_HIP_BCAST")) {  // standard keys from shard 0 to every other shard, once
-    std::vector<u64*> dst_b(nd), dst_k(nd);
-    for (size_t i = 0; i < nd; i++) {
-      dst_b[i] = (u64*)c->sh[i].d_stage;
-      dst_k[i] = c->sh[i].d_ksk;
+  RC_TRY(broadcast(c, bsk0, dst_b, r.bsk_len));  // nothing to do on one shard (bcast_plan)
+  if (with_ksk) RC_TRY(broadcast(c, dst_k[0], dst_k, r.ksk_len));
+  const tfhe::seeded_round_keys rk_b = seeded ? round_keys_of(r.bsk_seed) : tfhe::seeded_round_keys{};
+  const tfhe::seeded_round_keys rk_k = seeded && with_ksk ? round_keys_of(r.ksk_seed) : tfhe::seeded_round_keys{};
+  const tfhe::seeded_shape shp = seeded_shape_of(c->p, r.g);
+  for (size_t i = 0; i < nd; i++) {
+    shard& s = c->sh[i];
+    if (seeded) {  // 3. expand the bodies into the buffers that the other sources fill by copy
+      DeviceGuard g(s.device);
+      if (i == 0) RC_TRY(tm.mark());
+      HIP_TRY(tfhe::launch_seeded_rows(rk_b, r.g > 1 ? tfhe::SEEDED_BSK_MB : tfhe::SEEDED_BSK, shp, dst_b[i],
+                                       (u64*)s.d_stage, s.stream));
+      if (with_ksk) HIP_TRY(tfhe::launch_seeded_rows(rk_k, tfhe::SEEDED_KSK, shp, dst_k[i], s.d_ksk, s.stream));
+      if (i == 0) RC_TRY(tm.mark());
     }
-    RC_TRY(broadcast(c, bsk0, dst_b, bsk_len));
-    if (with_ksk) RC_TRY(broadcast(c, s0.d_ksk, dst_k, ksk_len));
+    // 4. convert (waits for the shard's stream)
+    RC_TRY(convert_keys(c, s, i == 0 && !seeded ? bsk0 : (const u64*)s.d_stage, bsk_len, with_ksk));
+    if (i == 0 && seeded) {
+      RC_TRY(tm.mark());
+      double ms[3];
+      RC_TRY(tm.ms(0, 1, &ms[0]));
+      RC_TRY(tm.ms(2, 3, &ms[1]));
+      RC_TRY(tm.ms(3, 4, &ms[2]));
+      std::copy(ms, ms + 3, c->seeded_ms);
+    }
   }
-  for (size_t i = 0; i < nd; i++)
-    RC_TRY(convert_keys(c, c->sh[i], i == 0 ? bsk0 : (const u64*)c->sh[i].d_stage, bsk_len, with_ksk));
+  // 5. commit
   c->bsk = true;
   c->keys = with_ksk;
-  c->grouping = g;
+  c->grouping = r.g;
   return 0;
 }
 
+static int load_from(tfhe_ctx* c, const key_load& r) {
+  RC_TRY(key_load_check(c, r));
+  return key_load_run(c, r);
+}
+
 int tfhe_hip_load_keys(tfhe_ctx* c, const uint64_t* bsk, size_t bsk_len, const uint64_t* ksk, size_t ksk_len) {
-  return load_keys_impl(c, "load_keys", bsk, bsk_len, ksk, ksk_len, true, true);
+  return load_from(c, {"load_keys", SRC_HOST, bsk, bsk_len, ksk, ksk_len, true});
 }
 
 int tfhe_hip_load_keys_device(tfhe_ctx* c, const uint64_t* d_bsk, size_t bsk_len, const uint64_t* d_ksk,
                               size_t ksk_len) {
-  return load_keys_impl(c, "load_keys", d_bsk, bsk_len, d_ksk, ksk_len, true, false);
+  return load_from(c, {"load_keys", SRC_DEVICE, d_bsk, bsk_len, d_ksk, ksk_len, true});
 }
 
 int tfhe_hip_load_bsk(tfhe_ctx* c, const uint64_t* bsk, size_t bsk_len) {
-  return load_keys_impl(c, "load_bsk", bsk, bsk_len, nullptr, 0, false, true);
+  return load_from(c, {"load_bsk", SRC_HOST, bsk, bsk_len});
 }
 
 int tfhe_hip_load_bsk_device(tfhe_ctx* c, const uint64_t* d_bsk, size_t bsk_len) {
-  return load_keys_impl(c, "load_bsk", d_bsk, bsk_len, nullptr, 0, false, false);
+  return load_from(c, {"load_bsk", SRC_DEVICE, d_bsk, bsk_len});
 }
 
 int tfhe_hip_load_keys_mb(tfhe_ctx* c, uint32_t g, const uint64_t* bsk_mb, size_t bsk_mb_len, const uint64_t* ksk,
                           size_t ksk_len) {
-  if (!c || !bsk_mb) return fail(TFHE_HIP_EINVAL, "load_keys_mb: null argument");
-  if (!c->eng_mb)
-    return fail(TFHE_HIP_EUNSUPPORTED, "load_keys_mb: the multi-bit back end covers the FFT64 transform at N = 2048 "
-                                       "(PBS 23x1); this ctx runs transform %u, N = %u", c->p.transform, c->p.N);
-  if (!grouping_valid(g) || g < c->eng_mb->g_min || g > c->eng_mb->g_max)
-    return fail(TFHE_HIP_EINVAL, "load_keys_mb: grouping factor %u, expected 2, 3 or 4", g);
-  if (c->p.n % g) return fail(TFHE_HIP_EINVAL, "load_keys_mb: n = %u is not divisible by the grouping factor %u", c->p.n, g);
-  return load_keys_impl(c, "load_keys_mb", bsk_mb, bsk_mb_len, ksk, ksk_len, ksk != nullptr, true, g);
+  return load_from(c, {"load_keys_mb", SRC_HOST, bsk_mb, bsk_mb_len, ksk, ksk_len, ksk != nullptr, nullptr, nullptr,
+                       true, g});
 }
 
 int tfhe_hip_grouping(const tfhe_ctx* c) { return c ? (int)c->grouping : 1; }
 
-// ---- seeded loaders: every argument and length check precedes load_keys_impl, which touches the ctx
-static int seeded_load_check(const tfhe_ctx* c, const char* what, uint32_t g, const uint64_t* bsk_seed,
-                             const uint64_t* bsk_bodies, size_t bsk_bodies_len, bool with_ksk, const uint64_t* ksk_seed,
-                             const uint64_t* ksk_bodies, size_t ksk_bodies_len) {
-  if (!c || !bsk_seed || !bsk_bodies || (with_ksk && (!ksk_seed || !ksk_bodies)))
-    return fail(TFHE_HIP_EINVAL, "%s: null argument", what);
-  if (c->p.transform != TFHE_HIP_TRANSFORM_FFT64)
-    return fail(TFHE_HIP_EUNSUPPORTED, "%s: seeded keys exist for the native-torus (FFT64) presets only", what);
-  if (g > 1) {
-    if (!c->eng_mb)
-      return fail(TFHE_HIP_EUNSUPPORTED, "%s: the multi-bit back end covers the FFT64 transform at N = 2048 (PBS 23x1); "
-                                         "this ctx runs transform %u, N = %u", what, c->p.transform, c->p.N);
-    if (!grouping_valid(g) || g < c->eng_mb->g_min || g > c->eng_mb->g_max)
-      return fail(TFHE_HIP_EINVAL, "%s: grouping factor %u, expected 2, 3 or 4", what, g);
-    if (c->p.n % g) return fail(TFHE_HIP_EINVAL, "%s: n = %u is not divisible by the grouping factor %u", what, c->p.n, g);
-  }
-  const size_t want_b = seeded_bsk_bodies_len(c->p, g), want_k = (size_t)c->p.k * c->p.N * c->p.ks_level;
-  if (bsk_bodies_len != want_b || (with_ksk && ksk_bodies_len != want_k))
-    return fail(TFHE_HIP_EINVAL, "%s: body counts %zu/%zu, expected %zu/%zu", what, bsk_bodies_len,
-                with_ksk ? ksk_bodies_len : want_k, want_b, want_k);
-  return 0;
-}
-
 int tfhe_hip_load_keys_seeded(tfhe_ctx* c, const uint64_t bsk_seed[2], const uint64_t* bsk_bodies, size_t bsk_bodies_len,
                               const uint64_t ksk_seed[2], const uint64_t* ksk_bodies, size_t ksk_bodies_len) {
-  RC_TRY(seeded_load_check(c, "load_keys_seeded", 1, bsk_seed, bsk_bodies, bsk_bodies_len, true, ksk_seed, ksk_bodies,
-                           ksk_bodies_len));
-  const seeded_src sd{bsk_seed, bsk_bodies, bsk_bodies_len, ksk_seed, ksk_bodies, ksk_bodies_len};
-  return load_keys_impl(c, "load_keys_seeded", nullptr, 0, nullptr, 0, true, true, 1, &sd);
+  return load_from(c, {"load_keys_seeded", SRC_SEEDED, bsk_bodies, bsk_bodies_len, ksk_bodies, ksk_bodies_len, true,
+                       bsk_seed, ksk_seed});
 }
 
 int tfhe_hip_load_bsk_seeded(tfhe_ctx* c, const uint64_t seed[2], const uint64_t* bodies, size_t bodies_len) {
-  RC_TRY(seeded_load_check(c, "load_bsk_seeded", 1, seed, bodies, bodies_len, false, nullptr, nullptr, 0));
-  const seeded_src sd{seed, bodies, bodies_len, nullptr, nullptr, 0};
-  return load_keys_impl(c, "load_bsk_seeded", nullptr, 0, nullptr, 0, false, true, 1, &sd);
+  return load_from(c, {"load_bsk_seeded", SRC_SEEDED, bodies, bodies_len, nullptr, 0, false, seed});
 }
 
 int tfhe_hip_load_keys_mb_seeded(tfhe_ctx* c, uint32_t g, const uint64_t bsk_seed[2], const uint64_t* bsk_bodies,
                                  size_t bsk_bodies_len, const uint64_t ksk_seed[2], const uint64_t* ksk_bodies,
                                  size_t ksk_bodies_len) {
-  if (c && g == 1) return fail(TFHE_HIP_EINVAL, "load_keys_mb_seeded: grouping factor 1, expected 2, 3 or 4");
-  const bool with_ksk = ksk_bodies != nullptr;
-  RC_TRY(seeded_load_check(c, "load_keys_mb_seeded", g, bsk_seed, bsk_bodies, bsk_bodies_len, with_ksk, ksk_seed,
-                           ksk_bodies, ksk_bodies_len));
-  const seeded_src sd{bsk_seed, bsk_bodies, bsk_bodies_len, ksk_seed, ksk_bodies, ksk_bodies_len};
-  return load_keys_impl(c, "load_keys_mb_seeded", nullptr, 0, nullptr, 0, with_ksk, true, g, &sd);
+  return load_from(c, {"load_keys_mb_seeded", SRC_SEEDED, bsk_bodies, bsk_bodies_len, ksk_bodies, ksk_bodies_len,
+                       ksk_bodies != nullptr, bsk_seed, ksk_seed, true, g});
 }
 
 int tfhe_hip_seeded_load_stats(const tfhe_ctx* c, double* upload_ms, double* expand_ms, double* convert_ms) {
@@ -1424,8 +1411,13 @@ int tfhe_hip_seeded_load_stats(const tfhe_ctx* c, double* upload_ms, double* exp
 
 // ---- the expansion kernels alone (test-facing): the launchers the loaders use, on shard 0, into a fresh device
 // buffer of out_len + TFHE_HIP_SEEDED_GUARD_WORDS words filled with 0xA5 bytes, all of which is copied back
-static int seeded_expand_call(tfhe_ctx* c, tfhe::seeded_kind kind, const tfhe::seeded_shape& shp,
-                              const uint64_t seed[2], const uint64_t* bodies, size_t bodies_len, size_t out_len,
+struct expand_job {
+  tfhe::seeded_kind kind;
+  tfhe::seeded_shape shp;
+  size_t bodies_len, out_len;
+};
+
+static int seeded_expand_call(tfhe_ctx* c, const expand_job& j, const uint64_t seed[2], const uint64_t* bodies,
                               uint64_t* out_host) {
   const tfhe::seeded_round_keys rk = round_keys_of(seed);
   std::lock_guard<std::mutex> lk(c->mu);
@@ -1433,12 +1425,12 @@ static int seeded_expand_call(tfhe_ctx* c, tfhe::seeded_kind kind, const tfhe::s
   DeviceGuard gd(s.device);
   temp_buffers tmp;
   u64 *d_bodies = nullptr, *d_out = nullptr;
-  const size_t out_bytes = (out_len + TFHE_HIP_SEEDED_GUARD_WORDS) * 8;
-  RC_TRY(tmp.alloc(s.device, bodies_len * 8, (void**)&d_bodies));
+  const size_t out_bytes = (j.out_len + TFHE_HIP_SEEDED_GUARD_WORDS) * 8;
+  RC_TRY(tmp.alloc(s.device, j.bodies_len * 8, (void**)&d_bodies));
   RC_TRY(tmp.alloc(s.device, out_bytes, (void**)&d_out));
   HIP_TRY(hipMemsetAsync(d_out, 0xA5, out_bytes, s.stream));
-  if (bodies_len) HIP_TRY(hipMemcpyAsync(d_bodies, bodies, bodies_len * 8, hipMemcpyHostToDevice, s.stream));
-  HIP_TRY(tfhe::launch_seeded_rows(rk, kind, shp, d_bodies, d_out, s.stream));
+  if (j.bodies_len) HIP_TRY(hipMemcpyAsync(d_bodies, bodies, j.bodies_len * 8, hipMemcpyHostToDevice, s.stream));
+  HIP_TRY(tfhe::launch_seeded_rows(rk, j.kind, j.shp, d_bodies, d_out, s.stream));
   HIP_TRY(hipMemcpyAsync(out_host, d_out, out_bytes, hipMemcpyDeviceToHost, s.stream));
   HIP_TRY(hipStreamSynchronize(s.stream));
   return 0;
@@ -1446,21 +1438,22 @@ static int seeded_expand_call(tfhe_ctx* c, tfhe::seeded_kind kind, const tfhe::s
 
 int tfhe_hip_seeded_expand_bsk(tfhe_ctx* c, uint32_t g, const uint64_t seed[2], const uint64_t* bodies,
                                uint64_t* out_host) {
-  if (c && g == 0) return fail(TFHE_HIP_EINVAL, "seeded_expand_bsk: grouping factor 0");
-  RC_TRY(seeded_load_check(c, "seeded_expand_bsk", g, seed, bodies, c ? seeded_bsk_bodies_len(c->p, g) : 0, false,
-                           nullptr, nullptr, 0));
+  if (!c || !seed || !bodies) return fail(TFHE_HIP_EINVAL, "seeded_expand_bsk: null argument");
+  if (g == 0) return fail(TFHE_HIP_EINVAL, "seeded_expand_bsk: grouping factor 0");
+  RC_TRY(native_torus_check(c, "seeded_expand_bsk"));
+  if (g > 1) RC_TRY(mb_key_check(c, "seeded_expand_bsk", g));
   if (!out_host) return fail(TFHE_HIP_EINVAL, "seeded_expand_bsk: null argument");
-  const size_t out_len = g > 1 ? tfhe::client::mb_bsk_len(c->p, g) : tfhe::client::bsk_len(c->p);
-  return seeded_expand_call(c, g > 1 ? tfhe::SEEDED_BSK_MB : tfhe::SEEDED_BSK,
-                            seeded_shape_of(c->p, g), seed, bodies, seeded_bsk_bodies_len(c->p, g), out_len, out_host);
+  return seeded_expand_call(c, {g > 1 ? tfhe::SEEDED_BSK_MB : tfhe::SEEDED_BSK, seeded_shape_of(c->p, g),
+                                tfhe::client::bsk_bodies_len(c->p, g), std_bsk_len(c->p, g)},
+                            seed, bodies, out_host);
 }
 
 int tfhe_hip_seeded_expand_ksk(tfhe_ctx* c, const uint64_t seed[2], const uint64_t* bodies, uint64_t* out_host) {
   if (!c || !seed || !bodies || !out_host) return fail(TFHE_HIP_EINVAL, "seeded_expand_ksk: null argument");
-  if (c->p.transform != TFHE_HIP_TRANSFORM_FFT64)
-    return fail(TFHE_HIP_EUNSUPPORTED, "seeded_expand_ksk: seeded keys exist for the native-torus (FFT64) presets only");
-  return seeded_expand_call(c, tfhe::SEEDED_KSK, seeded_shape_of(c->p, 1), seed, bodies,
-                            (size_t)c->p.k * c->p.N * c->p.ks_level, tfhe::client::ksk_len(c->p), out_host);
+  RC_TRY(native_torus_check(c, "seeded_expand_ksk"));
+  return seeded_expand_call(c, {tfhe::SEEDED_KSK, seeded_shape_of(c->p, 1), tfhe::client::ksk_bodies_len(c->p),
+                                tfhe::client::ksk_len(c->p)},
+                            seed, bodies, out_host);
 }
 
 int tfhe_hip_seeded_expand_lwe_list(tfhe_ctx* c, uint32_t dim, uint32_t count, const uint64_t seed[2],
@@ -1470,20 +1463,24 @@ int tfhe_hip_seeded_expand_lwe_list(tfhe_ctx* c, uint32_t dim, uint32_t count, c
     return fail(TFHE_HIP_EINVAL, "seeded_expand_lwe_list: dim = %u, count = %u out of range", dim, count);
   tfhe::seeded_shape shp{};
   shp.n = dim, shp.count = count;
-  return seeded_expand_call(c, tfhe::SEEDED_LIST, shp, seed, bodies, count,
-                            (size_t)count * ((size_t)dim + 1), out_host);
+  return seeded_expand_call(c, {tfhe::SEEDED_LIST, shp, count, (size_t)count * ((size_t)dim + 1)}, seed, bodies,
+                            out_host);
 }
 
-// tfhe_hip_load_ms_key*: the checks behind the argument check, shared by the host and the seeded source
-static int ms_key_check(const tfhe_ctx* c, const char* what, uint32_t count, double bound, double r_sigma,
-                        double input_variance) {
+// ---- the modulus-switch zeros (tfhe_hip_load_ms_key*)
+struct ms_tuning {
+  double bound, r_sigma, input_variance;
+};
+
+// the checks behind the argument check, shared by the host and the seeded source
+static int ms_key_check(const tfhe_ctx* c, const char* what, uint32_t count, const ms_tuning& t) {
   if (c->grouping > 1)
     return fail(TFHE_HIP_EUNSUPPORTED, "%s: multi-bit keys are loaded (grouping %u); the noise-reduction pick "
                                        "is defined for the per-element modulus switch", what, c->grouping);
   if (c->p.order != 1 && count)
     return fail(TFHE_HIP_EUNSUPPORTED, "%s: the noise reduction runs between keyswitch and blind rotation "
                                        "(KS -> PBS parameter sets only)", what);
-  if (count > 0x7FFFFFFF || !(bound >= 0) || !(r_sigma >= 0) || !(input_variance >= 0))
+  if (count > 0x7FFFFFFF || !(t.bound >= 0) || !(t.r_sigma >= 0) || !(t.input_variance >= 0))
     return fail(TFHE_HIP_EINVAL, "%s: count %u / bound / r_sigma / variance out of range", what, count);
   // the scan addresses the element-major transpose through a buffer resource with 32-bit byte offsets
   // (ms_reduce.hip): (n + 1) x pitch x 8 must stay below 2^31, or raw loads past num_records would read zeros
@@ -1494,22 +1491,15 @@ static int ms_key_check(const tfhe_ctx* c, const char* what, uint32_t count, dou
   return 0;
 }
 
-int tfhe_hip_load_ms_key(tfhe_ctx* c, const uint64_t* zeros, uint32_t count, double bound, double r_sigma,
-                         double input_variance) {
-  if (!c || (count && !zeros)) return fail(TFHE_HIP_EINVAL, "load_ms_key: bad arguments");
-  RC_TRY(ms_key_check(c, "load_ms_key", count, bound, r_sigma, input_variance));
+// Install `count` checked zeros on every shard (0: disable the reduction and free the buffer).  Two layouts in one
+// allocation: rows [count][n+1] (the add of the chosen zero), which fill_rows(shard) puts at s.d_ms_zeros by a copy
+// or by work on the shard's stream, then the element-major transpose [n+1][zp] that the scan reads 64 zeros per load
+// from (pbs_kernels.h: ms_zeros_pitch), built from the rows on the device.
+static int install_ms_zeros(tfhe_ctx* c, uint32_t count, const ms_tuning& t,
+                            const std::function<int(shard&)>& fill_rows) {
   std::lock_guard<std::mutex> lk(c->mu);
   c->ms_count = 0;
-  // two layouts in one allocation: rows [count][n+1] (the add of the chosen zero) then the element-major
-  // transpose [n+1][zp] the scan reads 64 zeros per load from (pbs_kernels.h: ms_zeros_pitch)
   const size_t dim = c->p.n + 1, zp = tfhe::ms_zeros_pitch(count);
-  const size_t bytes = (count * dim + dim * zp) * 8;
-  std::vector<uint64_t> tr;
-  if (count) {
-    tr.assign(dim * zp, 0);
-    for (size_t z = 0; z < count; z++)
-      for (size_t i = 0; i < dim; i++) tr[i * zp + z] = zeros[z * dim + i];
-  }
   for (auto& s : c->sh) {
     DeviceGuard g(s.device);
     HIP_TRY(hipStreamSynchronize(s.stream));
@@ -1517,54 +1507,47 @@ int tfhe_hip_load_ms_key(tfhe_ctx* c, const uint64_t* zeros, uint32_t count, dou
     (void)hipFree(s.d_ms_zeros);
     s.d_ms_zeros = nullptr;
     if (!count) continue;
-    HIP_TRY(hipMalloc(&s.d_ms_zeros, bytes));
-    HIP_TRY(hipMemcpy(s.d_ms_zeros, zeros, count * dim * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s.d_ms_zeros + count * dim, tr.data(), tr.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&s.d_ms_zeros, (count * dim + dim * zp) * 8));
+    RC_TRY(fill_rows(s));
+    HIP_TRY(tfhe::launch_ms_zeros_transpose(s.d_ms_zeros, count, (u32)dim, s.d_ms_zeros + count * dim, s.stream));
+    HIP_TRY(hipStreamSynchronize(s.stream));  // before the caller releases what fill_rows reads
   }
   c->ms_count = count;
-  c->ms_bound = bound;
-  c->ms_r_sigma = r_sigma;
-  c->ms_var128 = input_variance * 0x1p128;
+  c->ms_bound = t.bound;
+  c->ms_r_sigma = t.r_sigma;
+  c->ms_var128 = t.input_variance * 0x1p128;
   return 0;
 }
 
-// The zeros from their seeded form: count body words go to every shard, which expands the rows [count][n+1] and
-// builds the element-major transpose behind them on its own stream (same allocation and layouts as above).
+int tfhe_hip_load_ms_key(tfhe_ctx* c, const uint64_t* zeros, uint32_t count, double bound, double r_sigma,
+                         double input_variance) {
+  if (!c || (count && !zeros)) return fail(TFHE_HIP_EINVAL, "load_ms_key: bad arguments");
+  const ms_tuning t{bound, r_sigma, input_variance};
+  RC_TRY(ms_key_check(c, "load_ms_key", count, t));
+  return install_ms_zeros(c, count, t, [&](shard& s) -> int {
+    HIP_TRY(hipMemcpyAsync(s.d_ms_zeros, zeros, (size_t)count * (c->p.n + 1) * 8, hipMemcpyHostToDevice, s.stream));
+    return 0;
+  });
+}
+
+// The zeros from their seeded form: count body words go to every shard, which expands the rows on its own stream.
 int tfhe_hip_load_ms_key_seeded(tfhe_ctx* c, const uint64_t seed[2], const uint64_t* bodies, uint32_t count,
                                 double bound, double r_sigma, double input_variance) {
   if (!c || (count && (!seed || !bodies))) return fail(TFHE_HIP_EINVAL, "load_ms_key_seeded: bad arguments");
-  if (c->p.transform != TFHE_HIP_TRANSFORM_FFT64)
-    return fail(TFHE_HIP_EUNSUPPORTED, "load_ms_key_seeded: seeded keys exist for the native-torus (FFT64) presets only");
-  RC_TRY(ms_key_check(c, "load_ms_key_seeded", count, bound, r_sigma, input_variance));
-  std::lock_guard<std::mutex> lk(c->mu);
-  c->ms_count = 0;
-  const size_t dim = c->p.n + 1, zp = tfhe::ms_zeros_pitch(count);
-  const size_t bytes = (count * dim + dim * zp) * 8;
-  tfhe::seeded_round_keys rk{};
+  RC_TRY(native_torus_check(c, "load_ms_key_seeded"));
+  const ms_tuning t{bound, r_sigma, input_variance};
+  RC_TRY(ms_key_check(c, "load_ms_key_seeded", count, t));
+  const tfhe::seeded_round_keys rk = count ? round_keys_of(seed) : tfhe::seeded_round_keys{};
   tfhe::seeded_shape shp{};
   shp.n = c->p.n, shp.count = count;
-  if (count) rk = round_keys_of(seed);
-  for (auto& s : c->sh) {
-    DeviceGuard g(s.device);
-    HIP_TRY(hipStreamSynchronize(s.stream));
-    RC_TRY(ws_host_wait(s));
-    (void)hipFree(s.d_ms_zeros);
-    s.d_ms_zeros = nullptr;
-    if (!count) continue;
-    temp_buffers tmp;
+  temp_buffers tmp;  // every shard's bodies, released after the installer's last synchronise
+  return install_ms_zeros(c, count, t, [&](shard& s) -> int {
     u64* d_bodies = nullptr;
     RC_TRY(tmp.alloc(s.device, (size_t)count * 8, (void**)&d_bodies));
-    HIP_TRY(hipMalloc(&s.d_ms_zeros, bytes));
     HIP_TRY(hipMemcpyAsync(d_bodies, bodies, (size_t)count * 8, hipMemcpyHostToDevice, s.stream));
     HIP_TRY(tfhe::launch_seeded_rows(rk, tfhe::SEEDED_LIST, shp, d_bodies, s.d_ms_zeros, s.stream));
-    HIP_TRY(tfhe::launch_ms_zeros_transpose(s.d_ms_zeros, count, (u32)dim, s.d_ms_zeros + count * dim, s.stream));
-    HIP_TRY(hipStreamSynchronize(s.stream));  // before the bodies are released
-  }
-  c->ms_count = count;
-  c->ms_bound = bound;
-  c->ms_r_sigma = r_sigma;
-  c->ms_var128 = input_variance * 0x1p128;
-  return 0;
+    return 0;
+  });
 }
 
 int tfhe_hip_ms_reduce(tfhe_ctx* c, const uint64_t* in, size_t B, uint64_t* out, int32_t* picks) {

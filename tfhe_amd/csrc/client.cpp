@@ -163,6 +163,12 @@ static inline uint64_t pfrom(int64_t v) {
 
 size_t bsk_len(const tfhe_params& p) { return (size_t)p.n * (p.k + 1) * p.pbs_level * (p.k + 1) * p.N; }
 size_t ksk_len(const tfhe_params& p) { return (size_t)p.k * p.N * p.ks_level * (p.n + 1); }
+// the seeded forms (seeded.cpp) keep one body word per mask row: classic [n][L][k+1][N], multi-bit (g > 1)
+// [n/g][2^g][L][k+1][N] with the unused sigma = 0 slot, and the KSK's [kN][ks_level]
+size_t bsk_bodies_len(const tfhe_params& p, uint32_t g) {
+  return (size_t)(g > 1 ? (p.n / g) * (1u << g) : p.n) * p.pbs_level * (p.k + 1) * p.N;
+}
+size_t ksk_bodies_len(const tfhe_params& p) { return (size_t)p.k * p.N * p.ks_level; }
 
 // GLWE_S(0) over Z_p: masks uniform, body = sum_c A_c * S_c + E.  S is binary, so the product is
 // a signed sum of rotated masks.

@@ -11,6 +11,8 @@ tfhe_rng_key rng_key_from_seed(uint64_t seed);
 bool rng_key_entropy(tfhe_rng_key* k);  // getrandom(2), 192 bits
 size_t bsk_len(const tfhe_params& p);
 size_t ksk_len(const tfhe_params& p);
+size_t bsk_bodies_len(const tfhe_params& p, uint32_t g);  // body words of a seeded BSK; g == 1: classic
+size_t ksk_bodies_len(const tfhe_params& p);
 void keygen(const tfhe_params& p, const tfhe_rng_key& rk, uint64_t* lwe_key, uint64_t* glwe_key, uint64_t* bsk, uint64_t* ksk);
 // BSK / KSK for given binary secret keys (e.g. an ingested tfhe-rs ClientKey); same streams as keygen
 void server_keygen(const tfhe_params& p, const tfhe_rng_key& rk, const uint64_t* lwe_key, const uint64_t* glwe_key,

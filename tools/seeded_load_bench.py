@@ -48,8 +48,7 @@ def host_route(eng, blob):
     up = sk.bsk.nbytes + sk.ksk.nbytes
     if zeros is not None:
         eng.load_ms_key(zeros, **csk.ms)
-        n1 = zeros.shape[1]
-        up += zeros.nbytes + n1 * ((zeros.shape[0] + 63) // 64 * 64) * 8   # the rows and their transpose
+        up += zeros.nbytes                       # the rows; their transpose is built on the device
     eng.sync()
     return up
 
