@@ -74,7 +74,9 @@ uint32_t tfhe_hip_io_dim(const tfhe_params* p);
  * Replaces TfheClientKey.generate / ServerKey generation (sdk/relayer/src/tfhe.ts:20-28,
  * generateKeys.js:20-31).  All randomness is ChaCha20 keyed by a 192-bit rng key plus a stream index
  * (LWE key 1, GLWE key 2, BSK_i 0x1000+i, KSK_j 0x100000+j, MS zero z 0x200000+z, multi-bit GGSW (q, sigma)
- * 0x600000 + 16 q + sigma, seeded multi-bit GGSW (q, sigma) 0x700000 + 16 q + sigma, ciphertext q stream0+q).
+ * 0x600000 + 16 q + sigma, seeded multi-bit GGSW (q, sigma) 0x700000 + 16 q + sigma, ciphertext q stream0+q;
+ * further down: packing key 4 and 0x300000+j, squashing key 5 and 0x400000+i, ct128 packing key 6 and 0x500000+j,
+ * seeded squashing GGSW i 0x800000+i, seeded ct128 packing row j 0x900000+j).
  *   - tfhe_hip_rng_key_entropy: 192 bits from the OS (getrandom) -- production keys and encryptions;
  *   - tfhe_hip_rng_key_from_seed: (seed, a public tag) -- REPRODUCIBLE streams for tests, golden vectors
  *     and the oracle.  A seeded key set is public knowledge: never use one for real data.
@@ -646,6 +648,47 @@ int tfhe_hip_sns_blind_rotate(tfhe_sns_ctx* ctx, const uint64_t* lwe_small, size
 int tfhe_hip_sns_phase(const tfhe_sns_params* sp, const uint64_t* glwe_key, const uint64_t* cts, size_t count,
                        uint64_t* out);
 
+/* ---- the seeded (compressed) squashing key: bodies + a 128-bit seed, DESIGN §7h'' --------------
+ * The form in which a tenant's CompressedServerKey carries the noise-squashing key (tfhe-rs
+ * CompressedNoiseSquashingKey: a SeededLweBootstrapKey over u128).  PARITY UNPINNED at the byte level, as every
+ * seeded path here: the stream and the order below restate tfhe-csprng / tfhe-rs, with no key file to compare with.
+ *   The 128-bit mask stream: u128 mask word w of a seed is bytes 16 w + 1 .. 16 w + 16 of the seed's AES-CTR table,
+ *   little endian (the start at byte 1 of tfhe_hip_csprng_words), so lo = word 2 w and hi = word 2 w + 1 of
+ *   tfhe_hip_csprng_words: block w less its byte 0, plus byte 0 of block w + 1.  tfhe_hip_csprng_words128 writes
+ *   words first_word .. as (lo, hi) pairs.
+ *   Bodies [n][L][k+1][N] u128 words as (lo, hi) u64 pairs (the bytes of a Vec<u128>), n L (k+1) 2 N words
+ *   (tfhe_hip_sns_seeded_bodies_len; 0 for parameters outside the device kernels).  Stream row rho = (i L + l)(k+1) + c,
+ *   level l = 0 most significant, owns u128 mask words rho k N .. (polynomial j, then coefficient t).  Rows are in
+ *   tfhe-rs's GGSW form (row c < k: -s_i g_l S_c in the body, row k: s_i g_l on body coefficient 0,
+ *   g_l = 2^(128 - base_log (l + 1))); noise from the Gaussian sampler of tfhe_hip_sns_keygen, GGSW i on ChaCha
+ *   stream 0x800000 + i; the GLWE key is that of tfhe_hip_sns_keygen (stream 5).
+ * tfhe_hip_sns_decompress_bsk writes the loader's [i][c*L+l][j][lo, hi][N] layout on the host: the host route
+ * (followed by tfhe_hip_sns_load_key) and the CPU reference, word for word, of the device expansion. */
+size_t tfhe_hip_sns_seeded_bodies_len(const tfhe_sns_params* sp);
+int tfhe_hip_sns_seeded_keygen(const tfhe_sns_params* sp, uint64_t rng_seed, const uint64_t seed[2],
+                               const uint64_t* lwe_key, uint64_t* glwe_key, uint64_t* bodies /* nullable */);
+int tfhe_hip_sns_seeded_keygen_k(const tfhe_sns_params* sp, const tfhe_rng_key* rk, const uint64_t seed[2],
+                                 const uint64_t* lwe_key, uint64_t* glwe_key, uint64_t* bodies /* nullable */);
+int tfhe_hip_sns_decompress_bsk(const tfhe_sns_params* sp, const uint64_t seed[2], const uint64_t* bodies,
+                                uint64_t* bsk);
+int tfhe_hip_csprng_words128(const uint64_t seed[2], uint64_t first_word, size_t count, uint64_t* out_pairs);
+/* tfhe_hip_sns_load_key from the seeded form: the HOST bodies go up in chunks of whole GGSWs (75 = 2025 polynomials;
+ * TFHE_HIP_SNS_SEEDED_CHUNK, read at every load, sets the GGSWs per chunk), a HIP kernel
+ * (tfhe_amd/csrc/seeded_keys128.hip) regenerates the masks into the staging buffer in the loader's layout, and the
+ * conversion of tfhe_hip_sns_load_key follows on the same stream: a third of the bytes travel and no host AES runs.
+ * The resident key equals that of tfhe_hip_sns_decompress_bsk + tfhe_hip_sns_load_key bit for bit.  EINVAL for a null
+ * argument or len != tfhe_hip_sns_seeded_bodies_len, before any change to the ctx; a refused load, or one that cannot
+ * allocate its buffers, leaves the resident key usable.  Waits for every call still in flight on the ctx. */
+int tfhe_hip_sns_load_key_seeded(tfhe_sns_ctx* ctx, const uint64_t seed[2], const uint64_t* bodies, size_t len);
+/* Device milliseconds of the last seeded load: upload of the bodies, expansion kernels, conversion (a measurement
+ * aid, tools/sns_seeded_load_bench.py; any pointer may be null). */
+int tfhe_hip_sns_seeded_load_stats(const tfhe_sns_ctx* ctx, double* upload_ms, double* expand_ms, double* convert_ms);
+/* Test-facing, in the manner of tfhe_hip_seeded_expand_bsk: the loader's chunks through the loader's launcher into a
+ * fresh device buffer; out_host receives tfhe_hip_sns_bsk_len words FOLLOWED BY TFHE_HIP_SEEDED_GUARD_WORDS words of
+ * the device buffer behind them, which were filled with 0xA5 bytes before the launch. */
+int tfhe_hip_sns_seeded_expand_bsk(tfhe_sns_ctx* ctx, const uint64_t seed[2], const uint64_t* bodies,
+                                   uint64_t* out_host);
+
 /* ---- compression of squashed ciphertexts: packing keyswitch over the 2^128 torus ---------------
  * The stored form of fhEVM's sns-worker output (the ct128 bucket, coprocessor-docker-compose.yml:124-140;
  * tfhe-rs CompressedSquashedNoiseCiphertextList): up to lwe_per_glwe squashed LWEs (dimension in_dim, words of
@@ -715,6 +758,35 @@ int tfhe_hip_sns_pks_compress(const tfhe_sns_pks_params* pp, const uint64_t* glw
 int tfhe_hip_sns_pks_extract(const tfhe_sns_pks_params* pp, const uint64_t* packed, uint32_t bodies, uint64_t* glwe);
 /* client-side decryption of a 128-bit GLWE: body - sum_c mask_c * S_c -> [lo][N], [hi][N] */
 int tfhe_hip_glwe_phase128(uint32_t k, uint32_t N, const uint64_t* key, const uint64_t* glwe, uint64_t* out);
+/* The seeded (compressed) ct128 packing key (tfhe-rs CompressedNoiseSquashingCompressionKey: a seeded packing
+ * keyswitch key over u128), DESIGN §7h''; PARITY UNPINNED at the byte level.  One seeded 128-bit GLWE per (input
+ * element j, storage row s), stream row rho = j level + s of the 128-bit mask stream above: out_k out_N u128 mask
+ * words, then a body of [out_N] (lo, hi) pairs; bodies [in_dim][level][out_N][2], in_dim level 2 out_N words
+ * (tfhe_hip_sns_pks_seeded_bodies_len, 0 for invalid parameters).  Storage row s holds decomposition level
+ * `level - s` (least significant first, the keyswitching-key rule of the seeded section above) and lands in this
+ * engine's row l = level - 1 - s, with in_key[j] 2^(128 - base_log (l + 1)) on body coefficient 0.  Noise of input
+ * element j from ChaCha stream 0x900000 + j; the output key is that of tfhe_hip_sns_pks_keygen (stream 6).
+ * tfhe_hip_sns_pks_decompress_key writes the loader's [j][l][c][lo, hi][N] layout on the host (the host route and the
+ * CPU reference of the device expansion, word for word). */
+size_t tfhe_hip_sns_pks_seeded_bodies_len(const tfhe_sns_pks_params* pp);
+int tfhe_hip_sns_pks_seeded_keygen(const tfhe_sns_pks_params* pp, uint64_t rng_seed, const uint64_t seed[2],
+                                   const uint64_t* in_key, uint64_t* out_key, uint64_t* bodies /* nullable */);
+int tfhe_hip_sns_pks_seeded_keygen_k(const tfhe_sns_pks_params* pp, const tfhe_rng_key* rk, const uint64_t seed[2],
+                                     const uint64_t* in_key, uint64_t* out_key, uint64_t* bodies /* nullable */);
+int tfhe_hip_sns_pks_decompress_key(const tfhe_sns_pks_params* pp, const uint64_t seed[2], const uint64_t* bodies,
+                                    uint64_t* pksk);
+/* tfhe_hip_sns_pks_load_key from the seeded form: the bodies go up into a buffer of this call, the expansion kernel
+ * writes the rows straight into the resident key and the correction kernel of tfhe_hip_sns_pks_load_key follows.  The
+ * resident key equals that of the host route bit for bit.  EINVAL for a null argument or a wrong length, before any
+ * change to the ctx; a refused load, or one that cannot allocate, leaves the resident key usable.  Waits for calls in
+ * flight.  _load_stats: device ms of the last seeded load (upload, expansion, correction). */
+int tfhe_hip_sns_pks_load_key_seeded(tfhe_sns_pks_ctx* ctx, const uint64_t seed[2], const uint64_t* bodies, size_t len);
+int tfhe_hip_sns_pks_seeded_load_stats(const tfhe_sns_pks_ctx* ctx, double* upload_ms, double* expand_ms,
+                                       double* corr_ms);
+/* Test-facing: the loader's launcher into a fresh device buffer; out_host receives tfhe_hip_sns_pksk_len words
+ * followed by TFHE_HIP_SEEDED_GUARD_WORDS pre-filled (0xA5) guard words. */
+int tfhe_hip_sns_pks_seeded_expand_key(tfhe_sns_pks_ctx* ctx, const uint64_t seed[2], const uint64_t* bodies,
+                                       uint64_t* out_host);
 
 /* ---- encrypted matrix x clear matrix (the front half of the compression path) ------------------
  * Replaces the reference's GLWE x clear-matrix product (ml/extensions/rust/src: driver lib_python.rs:243-337

@@ -124,6 +124,11 @@ ABI_SYMBOLS = (
     "tfhe_hip_sns_pks_create", "tfhe_hip_sns_pks_destroy", "tfhe_hip_sns_pks_load_key", "tfhe_hip_sns_pks_pack",
     "tfhe_hip_sns_pks_pack_async", "tfhe_hip_sns_pks_pack_host", "tfhe_hip_sns_pks_packed_words",
     "tfhe_hip_sns_pks_compress", "tfhe_hip_sns_pks_extract", "tfhe_hip_glwe_phase128",
+    "tfhe_hip_sns_seeded_bodies_len", "tfhe_hip_sns_seeded_keygen", "tfhe_hip_sns_seeded_keygen_k",
+    "tfhe_hip_sns_decompress_bsk", "tfhe_hip_csprng_words128", "tfhe_hip_sns_load_key_seeded",
+    "tfhe_hip_sns_seeded_load_stats", "tfhe_hip_sns_seeded_expand_bsk", "tfhe_hip_sns_pks_seeded_bodies_len",
+    "tfhe_hip_sns_pks_seeded_keygen", "tfhe_hip_sns_pks_seeded_keygen_k", "tfhe_hip_sns_pks_decompress_key",
+    "tfhe_hip_sns_pks_load_key_seeded", "tfhe_hip_sns_pks_seeded_load_stats", "tfhe_hip_sns_pks_seeded_expand_key",
     "tfhe_hip_lut_oprf", "tfhe_hip_csprng_rows", "tfhe_hip_csprng_rows_async", "tfhe_hip_oprf", "tfhe_hip_oprf_async",
     "tfhe_hip_lwe_lincomb", "tfhe_hip_lwe_lincomb_async", "tfhe_hip_lincomb_pbs_async",
     "tfhe_hip_matmul_params_preset", "tfhe_hip_matmul_body_words", "tfhe_hip_matmul_keygen_k", "tfhe_hip_matmul_encrypt_k",

@@ -74,6 +74,18 @@ void seeded_lwe_list(uint32_t dim, uint32_t count, const uint64_t* key, int32_t 
 void decompress_bsk(const tfhe_params& p, const uint64_t seed[2], const uint64_t* bodies, uint64_t* bsk);
 void decompress_ksk(const tfhe_params& p, const uint64_t seed[2], const uint64_t* bodies, uint64_t* ksk);
 void decompress_lwe_list(uint32_t dim, uint32_t count, const uint64_t seed[2], const uint64_t* bodies, uint64_t* out);
+// seeded 128-bit keys (seeded.cpp; include/tfhe_hip.h tfhe_hip_sns_seeded_*, tfhe_hip_sns_pks_seeded_*): u128 words
+// as (lo, hi) u64 pairs in the stream and in the bodies
+void csprng_words128(const uint64_t seed[2], uint64_t first, size_t count, uint64_t* out_pairs);
+size_t sns_bodies_len(const tfhe_sns_params& sp);          // n L (k+1) 2 N
+size_t sns_pks_bodies_len(const tfhe_sns_pks_params& pp);  // in_dim level 2 out_N
+void sns_seeded_keygen(const tfhe_sns_params& sp, const tfhe_rng_key& rk, const uint64_t seed[2],
+                       const uint64_t* lwe_key, uint64_t* glwe_key, uint64_t* bodies /* nullable */);
+void sns_decompress_bsk(const tfhe_sns_params& sp, const uint64_t seed[2], const uint64_t* bodies, uint64_t* bsk);
+void sns_pks_seeded_keygen(const tfhe_sns_pks_params& pp, const tfhe_rng_key& rk, const uint64_t seed[2],
+                           const uint64_t* in_key, uint64_t* out_key, uint64_t* bodies /* nullable */);
+void sns_pks_decompress_key(const tfhe_sns_pks_params& pp, const uint64_t seed[2], const uint64_t* bodies,
+                            uint64_t* pksk);
 // encrypted matrix x clear matrix, client and CPU side (include/tfhe_hip.h tfhe_hip_matmul_*)
 size_t matmul_body_words(const tfhe_matmul_params& mp);
 void matmul_encrypt(const tfhe_matmul_params& mp, const uint64_t* glwe_key, const tfhe_rng_key& rk, uint64_t stream0,

@@ -196,6 +196,49 @@ int staged_run(S& s, staged_in in, size_t out_bytes, std::initializer_list<copy_
   return 0;
 }
 
+// a device buffer that lives for one call (the uploaded bodies of a seeded load): freed on every path out; the
+// caller's device is current at alloc and at scope end
+struct call_buffer {
+  void* p = nullptr;
+  int alloc(size_t bytes) {
+    HIP_TRY(hipMalloc(&p, bytes ? bytes : 8));
+    return 0;
+  }
+  ~call_buffer() {
+    if (p) (void)hipFree(p);
+  }
+};
+
+// Device-time split of a load on one stream: tick(phase) books the time since the previous tick under `phase`
+// (tick(-1) only opens an interval); totals() waits for the last tick.  Events are destroyed with the scope.
+struct phase_timer {
+  hipStream_t st;
+  std::vector<std::pair<hipEvent_t, int>> ev;
+  explicit phase_timer(hipStream_t s) : st(s) {}
+  int tick(int phase) {
+    hipEvent_t e = nullptr;
+    HIP_TRY(hipEventCreate(&e));
+    ev.emplace_back(e, phase);
+    HIP_TRY(hipEventRecord(e, st));
+    return 0;
+  }
+  int totals(double* ms, int phases) {
+    for (int i = 0; i < phases; i++) ms[i] = 0;
+    if (ev.empty()) return 0;
+    HIP_TRY(hipEventSynchronize(ev.back().first));
+    for (size_t i = 1; i < ev.size(); i++) {
+      if (ev[i].second < 0 || ev[i].second >= phases) continue;
+      float t = 0;
+      HIP_TRY(hipEventElapsedTime(&t, ev[i - 1].first, ev[i].first));
+      ms[ev[i].second] += t;
+    }
+    return 0;
+  }
+  ~phase_timer() {
+    for (auto& x : ev) (void)hipEventDestroy(x.first);
+  }
+};
+
 int check_binary(const uint64_t* key, size_t len, const char* what) {
   for (size_t i = 0; i < len; i++)
     if (key[i] > 1) return fail(TFHE_HIP_EINVAL, "%s[%zu] is not binary", what, i);

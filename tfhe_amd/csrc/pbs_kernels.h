@@ -164,6 +164,20 @@ struct seeded_shape {
 };
 hipError_t launch_seeded_rows(const seeded_round_keys& rk, seeded_kind kind, const seeded_shape& sh, const u64* bodies,
                               u64* out, hipStream_t s);
+// ---- seeded_keys128.hip: seeded 128-bit keys (u128 words as (lo, hi) u64 pairs in the bodies, as [lo][N], [hi][N]
+// planes in the output; seeded.cpp sns_decompress_bsk / sns_pks_decompress_key are the host references).  `rows`
+// stream rows from row0 on, both whole units (SNS_BSK: the L (k + 1) rows of a GGSW; SNS_PKSK: the L rows of an input
+// element); `bodies` holds the body pairs of those rows ([rows][N][2]) and `out` receives their destination rows
+// ([rows][k + 1][2][N], the unit's own order: SNS_BSK [i][c L + l], SNS_PKSK [j][L - 1 - s]), so a key may be
+// expanded in chunks of units through one staging buffer.  hipErrorInvalidValue for N not a power of two >= 32, a
+// zero k or L, a partial unit, a null or not 16-byte-aligned buffer or a grid past 2^31 - 1 workgroups; zero rows
+// launch nothing.
+enum seeded128_kind { SEEDED128_SNS_BSK = 0, SEEDED128_SNS_PKSK = 1 };
+struct seeded128_shape {
+  u32 k, N, L;  // mask polynomials of a row, polynomial size, levels
+};
+hipError_t launch_seeded_rows128(const seeded_round_keys& rk, seeded128_kind kind, const seeded128_shape& sh, u64 row0,
+                                 u64 rows, const u64* bodies, u64* out, hipStream_t s);
 // rows [count][dim] -> the element-major transpose [dim][ms_zeros_pitch(count)] behind them (ms_reduce.hip)
 hipError_t launch_ms_zeros_transpose(const u64* rows, u32 count, u32 dim, u64* tr, hipStream_t s);
 // ---- matmul.hip: encrypted matrix x clear matrix.  expand: G seeded GLWEs (seeds G x 2, packed G x ceil(N w / 64)

@@ -363,6 +363,157 @@ void decompress_lwe_list(uint32_t dim, uint32_t count, const uint64_t seed[2], c
   });
 }
 
+// ------------------------------------------------- seeded 128-bit keys: noise squashing and ct128 packing (DESIGN §7h'')
+// The 128-bit mask stream: u128 mask word w of a seed is stream bytes 16 w + 1 .. 16 w + 16, little endian (the start
+// at byte 1 of the 64-bit stream above), i.e. lo = word 2 w and hi = word 2 w + 1 of csprng_words: block w less its
+// byte 0, plus byte 0 of block w + 1.  PARITY UNPINNED at the byte level, as every seeded path here.
+//   squashing key   bodies [n][L][k+1][N] u128 as (lo, hi) u64 pairs (the bytes of a Vec<u128>); stream row
+//                   rho = (i L + l)(k + 1) + c, level l = 0 most significant, owns u128 mask words rho k N ..
+//                   (polynomial j, then coefficient t); GGSW rows in tfhe-rs's form (row c < k: -s_i g_l S_c, row k:
+//                   s_i g_l on coefficient 0, g_l = 2^(128 - base_log (l + 1))); noise of GGSW i from ChaCha stream
+//                   0x800000 + i; engine layout [i][c L + l][j][lo, hi][N]
+//   packing key     one seeded GLWE per (input element j, storage row s), rho = j level + s; storage row s holds
+//                   decomposition level `level - s` (least significant first, as the keyswitching key above) and lands
+//                   in engine row level - 1 - s; mask out_k out_N u128 words, body [out_N] pairs with
+//                   in_key[j] 2^(128 - base_log (l + 1)) on coefficient 0 (l the engine row); noise of input element j
+//                   from ChaCha stream 0x900000 + j; engine layout [j][l][c][lo, hi][N]
+namespace {
+typedef unsigned __int128 u128;
+
+// u128 mask words [w0, w0 + count) of the seed's stream as planes lo[count], hi[count]
+void mask_planes128(const Aes128& aes, uint64_t w0, size_t count, uint64_t* lo, uint64_t* hi) {
+  std::vector<uint64_t> w(2 * count);
+  mask_words(aes, 2 * w0, w.size(), w.data());
+  for (size_t t = 0; t < count; t++) lo[t] = w[2 * t], hi[t] = w[2 * t + 1];
+}
+
+std::vector<std::vector<uint32_t>> set_bits(uint32_t k, uint32_t N, const uint64_t* key) {
+  std::vector<std::vector<uint32_t>> bits(k);
+  for (uint32_t c = 0; c < k; c++)
+    for (uint32_t u = 0; u < N; u++)
+      if (key[(size_t)c * N + u]) bits[c].push_back(u);
+  return bits;
+}
+
+// body of one seeded 128-bit GLWE row: e + sum_c mask_c (*) S_c (negacyclic, mod 2^128) for the masks of stream row
+// rho; planes is a k x 2 x N scratch
+void zero_body128(const Aes128& aes, uint64_t rho, uint32_t k, uint32_t N,
+                  const std::vector<std::vector<uint32_t>>& bits, const int64_t* e, uint64_t* planes, u128* body) {
+  for (uint32_t t = 0; t < N; t++) body[t] = (u128)(__int128)e[t];
+  for (uint32_t c = 0; c < k; c++) {
+    uint64_t *lo = planes + (size_t)c * 2 * N, *hi = lo + N;
+    mask_planes128(aes, (rho * k + c) * N, N, lo, hi);
+    for (const uint32_t u : bits[c]) {
+      for (uint32_t x = 0; x < u; x++) body[x] -= ((u128)hi[x + N - u] << 64) | lo[x + N - u];
+      for (uint32_t x = u; x < N; x++) body[x] += ((u128)hi[x - u] << 64) | lo[x - u];
+    }
+  }
+}
+
+inline void store_pairs(const u128* body, uint32_t N, uint64_t* out) {
+  for (uint32_t t = 0; t < N; t++) out[2 * t] = (uint64_t)body[t], out[2 * t + 1] = (uint64_t)(body[t] >> 64);
+}
+
+// one expanded row: k mask polynomials of stream row rho as planes, then the body pairs de-interleaved
+void expand_row128(const Aes128& aes, uint64_t rho, uint32_t k, uint32_t N, const uint64_t* body_pairs, uint64_t* out) {
+  for (uint32_t c = 0; c < k; c++) mask_planes128(aes, (rho * k + c) * N, N, out + (size_t)c * 2 * N, out + (size_t)c * 2 * N + N);
+  uint64_t *lo = out + (size_t)k * 2 * N, *hi = lo + N;
+  for (uint32_t t = 0; t < N; t++) lo[t] = body_pairs[2 * t], hi[t] = body_pairs[2 * t + 1];
+}
+}  // namespace
+
+void csprng_words128(const uint64_t seed[2], uint64_t first, size_t count, uint64_t* out_pairs) {
+  csprng_words(seed, 2 * first, 2 * count, out_pairs);
+}
+
+size_t sns_bodies_len(const tfhe_sns_params& sp) { return (size_t)sp.n * sp.level * (sp.k + 1) * 2 * sp.N; }
+size_t sns_pks_bodies_len(const tfhe_sns_pks_params& pp) { return (size_t)pp.in_dim * pp.level * 2 * pp.out_N; }
+
+void sns_seeded_keygen(const tfhe_sns_params& sp, const tfhe_rng_key& rk, const uint64_t seed[2],
+                       const uint64_t* lwe_key, uint64_t* glwe_key, uint64_t* bodies) {
+  const uint32_t k = sp.k, N = sp.N, L = sp.level;
+  client::binary_key(rk, 5, (size_t)k * N, glwe_key);
+  if (!bodies) return;
+  const std::vector<std::vector<uint32_t>> bits = set_bits(k, N, glwe_key);
+  uint8_t key[16];
+  key_bytes(seed, key);
+  const Aes128 aes(key);
+  parallel_for((int64_t)sp.n, [&](int64_t i) {
+    std::vector<int64_t> e((size_t)L * (k + 1) * N);
+    std::vector<uint64_t> planes((size_t)k * 2 * N);
+    std::vector<u128> body(N);
+    client::noise_words(rk, 0x800000 + (uint64_t)i, sp.noise_log2, e.size(), e.data());
+    for (uint32_t l = 0; l < L; l++) {
+      const u128 g = (u128)1 << (128 - sp.base_log * (l + 1));
+      for (uint32_t c = 0; c <= k; c++) {
+        const uint64_t rho = ((uint64_t)i * L + l) * (k + 1) + c;
+        zero_body128(aes, rho, k, N, bits, e.data() + ((size_t)l * (k + 1) + c) * N, planes.data(), body.data());
+        if (lwe_key[i]) {  // plaintext -s_i g S_c (row c < k) / s_i g (row k)
+          if (c < k) {
+            for (const uint32_t u : bits[c]) body[u] -= g;
+          } else {
+            body[0] += g;
+          }
+        }
+        store_pairs(body.data(), N, bodies + rho * 2 * N);
+      }
+    }
+  });
+}
+
+void sns_decompress_bsk(const tfhe_sns_params& sp, const uint64_t seed[2], const uint64_t* bodies, uint64_t* bsk) {
+  const uint32_t k = sp.k, N = sp.N, L = sp.level;
+  const size_t row_len = (size_t)(k + 1) * 2 * N, per_i = (size_t)(k + 1) * L * row_len;
+  uint8_t key[16];
+  key_bytes(seed, key);
+  const Aes128 aes(key);
+  parallel_for((int64_t)sp.n, [&](int64_t i) {
+    for (uint32_t l = 0; l < L; l++)
+      for (uint32_t c = 0; c <= k; c++) {
+        const uint64_t rho = ((uint64_t)i * L + l) * (k + 1) + c;
+        expand_row128(aes, rho, k, N, bodies + rho * 2 * N, bsk + per_i * i + row_len * (c * L + l));
+      }
+  });
+}
+
+void sns_pks_seeded_keygen(const tfhe_sns_pks_params& pp, const tfhe_rng_key& rk, const uint64_t seed[2],
+                           const uint64_t* in_key, uint64_t* out_key, uint64_t* bodies) {
+  const uint32_t k = pp.out_k, N = pp.out_N, L = pp.level;
+  client::binary_key(rk, 6, (size_t)k * N, out_key);
+  if (!bodies) return;
+  const std::vector<std::vector<uint32_t>> bits = set_bits(k, N, out_key);
+  uint8_t key[16];
+  key_bytes(seed, key);
+  const Aes128 aes(key);
+  parallel_for((int64_t)pp.in_dim, [&](int64_t j) {
+    std::vector<int64_t> e((size_t)L * N);
+    std::vector<uint64_t> planes((size_t)k * 2 * N);
+    std::vector<u128> body(N);
+    client::noise_words(rk, 0x900000 + (uint64_t)j, pp.noise_log2, e.size(), e.data());
+    for (uint32_t s = 0; s < L; s++) {  // storage row s = engine row L - 1 - s
+      const uint64_t rho = (uint64_t)j * L + s;
+      zero_body128(aes, rho, k, N, bits, e.data() + (size_t)s * N, planes.data(), body.data());
+      if (in_key[j]) body[0] += (u128)1 << (128 - pp.base_log * (L - s));
+      store_pairs(body.data(), N, bodies + rho * 2 * N);
+    }
+  });
+}
+
+void sns_pks_decompress_key(const tfhe_sns_pks_params& pp, const uint64_t seed[2], const uint64_t* bodies,
+                            uint64_t* pksk) {
+  const uint32_t k = pp.out_k, N = pp.out_N, L = pp.level;
+  const size_t row_len = (size_t)(k + 1) * 2 * N;
+  uint8_t key[16];
+  key_bytes(seed, key);
+  const Aes128 aes(key);
+  parallel_for((int64_t)pp.in_dim, [&](int64_t j) {
+    for (uint32_t s = 0; s < L; s++) {
+      const uint64_t rho = (uint64_t)j * L + s;
+      expand_row128(aes, rho, k, N, bodies + rho * 2 * N, pksk + ((size_t)j * L + (L - 1 - s)) * row_len);
+    }
+  });
+}
+
 // ------------------------------------------------- encrypted matrix x clear matrix: client and CPU side
 // The conventions of include/tfhe_hip.h (tfhe_hip_matmul_*), restated from the reference: encode encryption.rs:5-40,
 // seeded encryption ml.rs:131-189 / encryption.rs:88-133, storage switch and packing compression.rs:59-105, expansion

@@ -36,6 +36,23 @@ size_t sns_chunk() {
   return v;
 }
 
+// GGSWs per chunk of a seeded load: the staging buffer takes whole rows, and a GGSW is L (k + 1) rows = 27
+// polynomials, so the 2048 polynomials of tfhe_hip_sns_load_key become 75 GGSWs = 2025.  TFHE_HIP_SNS_SEEDED_CHUNK
+// (GGSWs, read at every load) overrides: the tests cross chunk boundaries at n = 3
+size_t seeded_units(const tfhe_sns_params& sp) {
+  const char* e = getenv("TFHE_HIP_SNS_SEEDED_CHUNK");
+  const long x = e ? atol(e) : 0;
+  const size_t unit_polys = (size_t)sp.level * (sp.k + 1) * (sp.k + 1);
+  const size_t u = x > 0 ? (size_t)x : std::max<size_t>(1, 2048 / unit_polys);
+  return std::min<size_t>(u, sp.n);
+}
+
+tfhe::seeded_round_keys round_keys_of(const uint64_t seed[2]) {
+  tfhe::seeded_round_keys rk;
+  tfhe::seeded::aes_round_keys(seed, rk.w);
+  return rk;
+}
+
 }  // namespace
 
 // d_acc, d_D, d_O, d_lut and the key are shared by every call: ordered across streams by the slot's ws_begin / ws_end
@@ -50,6 +67,7 @@ struct tfhe_sns_ctx : device_slot {
   u64* d_lut = nullptr;
   uint32_t lut_mm = 0;
   size_t ws_cap = 0;
+  double seeded_ms[3] = {0, 0, 0};  // the last seeded load: upload, expansion, conversion (device ms)
   std::mutex mu;
 };
 
@@ -196,6 +214,118 @@ int tfhe_hip_sns_load_key(tfhe_sns_ctx* c, const uint64_t* bsk, size_t len) {
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->key = true;
+  return 0;
+}
+
+size_t tfhe_hip_sns_seeded_bodies_len(const tfhe_sns_params* sp) {
+  return sns_valid(sp) ? tfhe::seeded::sns_bodies_len(*sp) : 0;
+}
+
+int tfhe_hip_sns_seeded_keygen_k(const tfhe_sns_params* sp, const tfhe_rng_key* rk, const uint64_t seed[2],
+                                 const uint64_t* lwe_key, uint64_t* glwe_key, uint64_t* bodies) {
+  if (!sns_valid(sp) || !rk || !seed || !lwe_key || !glwe_key)
+    return fail(TFHE_HIP_EINVAL, "sns_seeded_keygen: bad arguments");
+  RC_TRY(check_binary(lwe_key, sp->n, "sns_seeded_keygen: lwe_key"));
+  tfhe::seeded::sns_seeded_keygen(*sp, *rk, seed, lwe_key, glwe_key, bodies);
+  return 0;
+}
+
+int tfhe_hip_sns_seeded_keygen(const tfhe_sns_params* sp, uint64_t rng_seed, const uint64_t seed[2],
+                               const uint64_t* lwe_key, uint64_t* glwe_key, uint64_t* bodies) {
+  const tfhe_rng_key rk = tfhe::client::rng_key_from_seed(rng_seed);
+  return tfhe_hip_sns_seeded_keygen_k(sp, &rk, seed, lwe_key, glwe_key, bodies);
+}
+
+int tfhe_hip_sns_decompress_bsk(const tfhe_sns_params* sp, const uint64_t seed[2], const uint64_t* bodies,
+                                uint64_t* bsk) {
+  if (!sns_valid(sp) || !seed || !bodies || !bsk) return fail(TFHE_HIP_EINVAL, "sns_decompress_bsk: bad arguments");
+  tfhe::seeded::sns_decompress_bsk(*sp, seed, bodies, bsk);
+  return 0;
+}
+
+int tfhe_hip_csprng_words128(const uint64_t seed[2], uint64_t first_word, size_t count, uint64_t* out_pairs) {
+  if (!seed || (count && !out_pairs)) return fail(TFHE_HIP_EINVAL, "csprng_words128: null argument");
+  if (first_word > (1ull << 59) || count > (1ull << 59)) return fail(TFHE_HIP_EINVAL, "csprng_words128: out of range");
+  tfhe::seeded::csprng_words128(seed, first_word, count, out_pairs);
+  return 0;
+}
+
+// Every refusal and every allocation comes before the resident key is touched: a refused load, or one that cannot
+// allocate, leaves the previous key usable.  Chunks of whole GGSWs: bodies up, rows expanded into the staging buffer,
+// launch_sns_bsk_to_fft as tfhe_hip_sns_load_key runs it, all on the ctx's stream
+int tfhe_hip_sns_load_key_seeded(tfhe_sns_ctx* c, const uint64_t seed[2], const uint64_t* bodies, size_t len) {
+  if (!c || !seed || !bodies) return fail(TFHE_HIP_EINVAL, "sns_load_key_seeded: null argument");
+  if (len != tfhe::seeded::sns_bodies_len(c->sp))
+    return fail(TFHE_HIP_EINVAL, "sns_load_key_seeded: length %zu, expected %zu", len,
+                tfhe::seeded::sns_bodies_len(c->sp));
+  const tfhe::seeded_round_keys rk = round_keys_of(seed);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  RC_TRY(ws_host_wait(*c));  // a call in flight on a caller's stream still reads the resident key
+  const tfhe::seeded128_shape shp{c->sp.k, c->sp.N, c->sp.level};
+  const size_t poly_words = 2 * (size_t)c->sp.N, unit_rows = (size_t)c->sp.level * (c->sp.k + 1);
+  const size_t unit_polys = unit_rows * (c->sp.k + 1), units = seeded_units(c->sp);
+  call_buffer d_bodies;
+  RC_TRY(d_bodies.alloc(units * unit_rows * poly_words * 8));
+  RC_TRY(ws_grow(*c, &c->d_stage, &c->stage_cap, units * unit_polys * poly_words * 8));
+  if (!c->d_bskf) HIP_TRY(hipMalloc(&c->d_bskf, tfhe::sns_fft_key_len(c->sp.n) * 16));
+  phase_timer tm(c->stream);
+  c->key = false;
+  for (size_t u = 0; u < c->sp.n; u += units) {
+    const size_t nu = std::min(units, c->sp.n - u), rows = nu * unit_rows;
+    RC_TRY(tm.tick(-1));
+    HIP_TRY(hipMemcpyAsync(d_bodies.p, bodies + u * unit_rows * poly_words, rows * poly_words * 8,
+                           hipMemcpyHostToDevice, c->stream));
+    RC_TRY(tm.tick(0));
+    HIP_TRY(tfhe::launch_seeded_rows128(rk, tfhe::SEEDED128_SNS_BSK, shp, u * unit_rows, rows,
+                                        (const u64*)d_bodies.p, (u64*)c->d_stage, c->stream));
+    RC_TRY(tm.tick(1));
+    HIP_TRY(tfhe::launch_sns_bsk_to_fft((const u64*)c->d_stage,
+                                        (char*)c->d_bskf + u * unit_polys * tfhe::SNS_FFT_POLY_BYTES, nu * unit_polys,
+                                        c->d_fconst, c->stream));
+    RC_TRY(tm.tick(2));
+    // the body and staging buffers are reused by the next chunk: same stream, ordered
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  RC_TRY(tm.totals(c->seeded_ms, 3));
+  c->key = true;
+  return 0;
+}
+
+int tfhe_hip_sns_seeded_load_stats(const tfhe_sns_ctx* c, double* upload_ms, double* expand_ms, double* convert_ms) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "sns_seeded_load_stats: null ctx");
+  if (upload_ms) *upload_ms = c->seeded_ms[0];
+  if (expand_ms) *expand_ms = c->seeded_ms[1];
+  if (convert_ms) *convert_ms = c->seeded_ms[2];
+  return 0;
+}
+
+// test-facing: the chunks of the loader, expanded by the loader's launcher into a fresh device buffer of the key's
+// length + TFHE_HIP_SEEDED_GUARD_WORDS words filled with 0xA5 bytes, all of which is copied back
+int tfhe_hip_sns_seeded_expand_bsk(tfhe_sns_ctx* c, const uint64_t seed[2], const uint64_t* bodies,
+                                   uint64_t* out_host) {
+  if (!c || !seed || !bodies || !out_host) return fail(TFHE_HIP_EINVAL, "sns_seeded_expand_bsk: null argument");
+  const tfhe::seeded_round_keys rk = round_keys_of(seed);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const tfhe::seeded128_shape shp{c->sp.k, c->sp.N, c->sp.level};
+  const size_t poly_words = 2 * (size_t)c->sp.N, unit_rows = (size_t)c->sp.level * (c->sp.k + 1);
+  const size_t unit_polys = unit_rows * (c->sp.k + 1), units = seeded_units(c->sp);
+  const size_t out_bytes = (tfhe::client::sns_bsk_len(c->sp) + TFHE_HIP_SEEDED_GUARD_WORDS) * 8;
+  call_buffer d_bodies, d_out;
+  RC_TRY(d_bodies.alloc(units * unit_rows * poly_words * 8));
+  RC_TRY(d_out.alloc(out_bytes));
+  HIP_TRY(hipMemsetAsync(d_out.p, 0xA5, out_bytes, c->stream));
+  for (size_t u = 0; u < c->sp.n; u += units) {
+    const size_t nu = std::min(units, c->sp.n - u), rows = nu * unit_rows;
+    HIP_TRY(hipMemcpyAsync(d_bodies.p, bodies + u * unit_rows * poly_words, rows * poly_words * 8,
+                           hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(tfhe::launch_seeded_rows128(rk, tfhe::SEEDED128_SNS_BSK, shp, u * unit_rows, rows,
+                                        (const u64*)d_bodies.p, (u64*)d_out.p + u * unit_polys * poly_words,
+                                        c->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(out_host, d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
 

@@ -24,6 +24,12 @@ bool spk_valid(const tfhe_sns_pks_params* pp) {
          pp->noise_log2 < 0 && pp->noise_log2 > -64;
 }
 
+tfhe::seeded_round_keys round_keys_of(const uint64_t seed[2]) {
+  tfhe::seeded_round_keys rk;
+  tfhe::seeded::aes_round_keys(seed, rk.w);
+  return rk;
+}
+
 constexpr size_t SPK_T_BUDGET = 512ull << 20;    // T workspace per chunk of groups
 constexpr size_t SPK_MAX_ROWS = 65535ull * 64;   // the GEMM grid's row tiles (sns_pks.hip)
 
@@ -39,6 +45,7 @@ struct tfhe_sns_pks_ctx : device_slot {
   u64* d_A = nullptr;
   u64* d_T = nullptr;
   size_t rows_cap = 0;  // LWEs the A / T workspaces hold
+  double seeded_ms[3] = {0, 0, 0};  // the last seeded load: upload, expansion, correction (device ms)
   std::mutex mu;
 };
 
@@ -154,6 +161,99 @@ int tfhe_hip_sns_pks_load_key(tfhe_sns_pks_ctx* c, const uint64_t* pksk, size_t 
                                     (int)c->pp.base_log, c->d_corr, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->key = true;
+  return 0;
+}
+
+size_t tfhe_hip_sns_pks_seeded_bodies_len(const tfhe_sns_pks_params* pp) {
+  return spk_valid(pp) ? tfhe::seeded::sns_pks_bodies_len(*pp) : 0;
+}
+
+int tfhe_hip_sns_pks_seeded_keygen_k(const tfhe_sns_pks_params* pp, const tfhe_rng_key* rk, const uint64_t seed[2],
+                                     const uint64_t* in_key, uint64_t* out_key, uint64_t* bodies) {
+  if (!spk_valid(pp) || !rk || !seed || !in_key || !out_key)
+    return fail(TFHE_HIP_EINVAL, "sns_pks_seeded_keygen: bad arguments");
+  RC_TRY(check_binary(in_key, pp->in_dim, "sns_pks_seeded_keygen: in_key"));
+  tfhe::seeded::sns_pks_seeded_keygen(*pp, *rk, seed, in_key, out_key, bodies);
+  return 0;
+}
+
+int tfhe_hip_sns_pks_seeded_keygen(const tfhe_sns_pks_params* pp, uint64_t rng_seed, const uint64_t seed[2],
+                                   const uint64_t* in_key, uint64_t* out_key, uint64_t* bodies) {
+  const tfhe_rng_key rk = tfhe::client::rng_key_from_seed(rng_seed);
+  return tfhe_hip_sns_pks_seeded_keygen_k(pp, &rk, seed, in_key, out_key, bodies);
+}
+
+int tfhe_hip_sns_pks_decompress_key(const tfhe_sns_pks_params* pp, const uint64_t seed[2], const uint64_t* bodies,
+                                    uint64_t* pksk) {
+  if (!spk_valid(pp) || !seed || !bodies || !pksk)
+    return fail(TFHE_HIP_EINVAL, "sns_pks_decompress_key: bad arguments");
+  tfhe::seeded::sns_pks_decompress_key(*pp, seed, bodies, pksk);
+  return 0;
+}
+
+// Every refusal and every allocation comes before the resident key is touched: a refused load, or one that cannot
+// allocate, leaves the previous key usable.  The bodies go up into a buffer of this call, the rows are expanded
+// straight into the resident key, and the correction kernel follows as in tfhe_hip_sns_pks_load_key
+int tfhe_hip_sns_pks_load_key_seeded(tfhe_sns_pks_ctx* c, const uint64_t seed[2], const uint64_t* bodies, size_t len) {
+  if (!c || !seed || !bodies) return fail(TFHE_HIP_EINVAL, "sns_pks_load_key_seeded: null argument");
+  if (len != tfhe::seeded::sns_pks_bodies_len(c->pp))
+    return fail(TFHE_HIP_EINVAL, "sns_pks_load_key_seeded: length %zu, expected %zu", len,
+                tfhe::seeded::sns_pks_bodies_len(c->pp));
+  const tfhe::seeded_round_keys rk = round_keys_of(seed);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  RC_TRY(ws_host_wait(*c));  // a call in flight on a caller's stream still reads the resident key
+  const size_t Nc = (size_t)(c->pp.out_k + 1) * c->pp.out_N;
+  call_buffer d_bodies;
+  RC_TRY(d_bodies.alloc(len * 8));
+  if (!c->d_pksk) HIP_TRY(hipMalloc(&c->d_pksk, tfhe::client::sns_pksk_len(c->pp) * 8));
+  if (!c->d_corr) HIP_TRY(hipMalloc(&c->d_corr, Nc * 16));
+  phase_timer tm(c->stream);
+  RC_TRY(tm.tick(-1));
+  HIP_TRY(hipMemcpyAsync(d_bodies.p, bodies, len * 8, hipMemcpyHostToDevice, c->stream));
+  RC_TRY(tm.tick(0));
+  c->key = false;
+  HIP_TRY(tfhe::launch_seeded_rows128(rk, tfhe::SEEDED128_SNS_PKSK, {c->pp.out_k, c->pp.out_N, c->pp.level}, 0,
+                                      (u64)c->pp.in_dim * c->pp.level, (const u64*)d_bodies.p, c->d_pksk, c->stream));
+  RC_TRY(tm.tick(1));
+  HIP_TRY(tfhe::launch_sns_pks_corr(c->d_pksk, (int)(c->pp.in_dim * c->pp.level), (int)Nc, (int)c->pp.out_N,
+                                    (int)c->pp.base_log, c->d_corr, c->stream));
+  RC_TRY(tm.tick(2));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  RC_TRY(tm.totals(c->seeded_ms, 3));
+  c->key = true;
+  return 0;
+}
+
+int tfhe_hip_sns_pks_seeded_load_stats(const tfhe_sns_pks_ctx* c, double* upload_ms, double* expand_ms,
+                                       double* corr_ms) {
+  if (!c) return fail(TFHE_HIP_EINVAL, "sns_pks_seeded_load_stats: null ctx");
+  if (upload_ms) *upload_ms = c->seeded_ms[0];
+  if (expand_ms) *expand_ms = c->seeded_ms[1];
+  if (corr_ms) *corr_ms = c->seeded_ms[2];
+  return 0;
+}
+
+// test-facing: the loader's launcher into a fresh device buffer of the key's length + TFHE_HIP_SEEDED_GUARD_WORDS
+// words filled with 0xA5 bytes, all of which is copied back
+int tfhe_hip_sns_pks_seeded_expand_key(tfhe_sns_pks_ctx* c, const uint64_t seed[2], const uint64_t* bodies,
+                                       uint64_t* out_host) {
+  if (!c || !seed || !bodies || !out_host) return fail(TFHE_HIP_EINVAL, "sns_pks_seeded_expand_key: null argument");
+  const tfhe::seeded_round_keys rk = round_keys_of(seed);
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const size_t len = tfhe::seeded::sns_pks_bodies_len(c->pp);
+  const size_t out_bytes = (tfhe::client::sns_pksk_len(c->pp) + TFHE_HIP_SEEDED_GUARD_WORDS) * 8;
+  call_buffer d_bodies, d_out;
+  RC_TRY(d_bodies.alloc(len * 8));
+  RC_TRY(d_out.alloc(out_bytes));
+  HIP_TRY(hipMemsetAsync(d_out.p, 0xA5, out_bytes, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_bodies.p, bodies, len * 8, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(tfhe::launch_seeded_rows128(rk, tfhe::SEEDED128_SNS_PKSK, {c->pp.out_k, c->pp.out_N, c->pp.level}, 0,
+                                      (u64)c->pp.in_dim * c->pp.level, (const u64*)d_bodies.p, (u64*)d_out.p,
+                                      c->stream));
+  HIP_TRY(hipMemcpyAsync(out_host, d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
 

@@ -18,6 +18,7 @@ import numpy as np
 from . import RngKey, _c_u64, _check, _stream_handle, _u64, lib, rng_key
 
 SNS_PRESET_FHEVM = 0
+SEEDED_GUARD_WORDS = 64  # TFHE_HIP_SEEDED_GUARD_WORDS
 _U64P = ctypes.POINTER(ctypes.c_uint64)
 
 
@@ -57,6 +58,15 @@ def _lib():
                                                 ctypes.c_void_p, ctypes.c_void_p]
         L.tfhe_hip_sns_blind_rotate.argtypes = [ctypes.c_void_p, _U64P, ctypes.c_size_t, ctypes.c_uint32, _U64P]
         L.tfhe_hip_sns_phase.argtypes = [P, _U64P, _U64P, ctypes.c_size_t, _U64P]
+        L.tfhe_hip_sns_seeded_bodies_len.argtypes = [P]
+        L.tfhe_hip_sns_seeded_bodies_len.restype = ctypes.c_size_t
+        L.tfhe_hip_sns_seeded_keygen.argtypes = [P, ctypes.c_uint64, _U64P, _U64P, _U64P, _U64P]
+        L.tfhe_hip_sns_seeded_keygen_k.argtypes = [P, ctypes.POINTER(RngKey), _U64P, _U64P, _U64P, _U64P]
+        L.tfhe_hip_sns_decompress_bsk.argtypes = [P, _U64P, _U64P, _U64P]
+        L.tfhe_hip_csprng_words128.argtypes = [_U64P, ctypes.c_uint64, ctypes.c_size_t, _U64P]
+        L.tfhe_hip_sns_load_key_seeded.argtypes = [ctypes.c_void_p, _U64P, _U64P, ctypes.c_size_t]
+        L.tfhe_hip_sns_seeded_load_stats.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_double)] * 3
+        L.tfhe_hip_sns_seeded_expand_bsk.argtypes = [ctypes.c_void_p, _U64P, _U64P, _U64P]
         _BOUND = True
     return L
 
@@ -71,8 +81,23 @@ class SquashedKey:
         self.glwe_key = np.zeros(params.k * params.N, dtype=np.uint64)
         self.bsk = np.zeros(L.tfhe_hip_sns_bsk_len(ctypes.byref(params)), dtype=np.uint64) if with_bsk else None
         rk = rng_key(seed)  # None: 192 bits of OS entropy (production); an int: the public test stream
+        self._rk = rk       # compress() draws the same GLWE key from it
         _check(L.tfhe_hip_sns_keygen_k(ctypes.byref(params), ctypes.byref(rk), _u64(self.lwe_key), _u64(self.glwe_key),
                                      _u64(self.bsk) if with_bsk else None))
+
+    def compress(self, mask_seed: Optional[int] = None) -> "CompressedSquashedKey":
+        """The seeded form of this key's squashing BSK (the CompressedNoiseSquashingKey::new role): a fresh key under
+        the same GLWE key, bodies only, its masks the 128-bit AES-CTR stream of `mask_seed` (OS entropy when None; a
+        given seed makes every mask public, test data only).  Parity with tfhe-rs unpinned at the byte level."""
+        import os
+        p = self.params
+        ms = int.from_bytes(os.urandom(16), "little") if mask_seed is None else int(mask_seed)
+        bodies = np.zeros((p.n, p.level, p.k + 1, p.N, 2), dtype=np.uint64)
+        glwe = np.zeros_like(self.glwe_key)
+        _check(_lib().tfhe_hip_sns_seeded_keygen_k(ctypes.byref(p), ctypes.byref(self._rk), _u64(seed_words(ms)),
+                                                   _u64(self.lwe_key), _u64(glwe), _u64(bodies)))
+        assert np.array_equal(glwe, self.glwe_key)
+        return CompressedSquashedKey(p, ms, bodies)
 
     def phase(self, cts: np.ndarray) -> list:
         p = self.params
@@ -85,6 +110,49 @@ class SquashedKey:
         """round(phase / (2^127 / msg_modulus)) mod msg_modulus (one padding bit)."""
         delta = (1 << 127) // msg_modulus
         return np.array([((ph + delta // 2) // delta) % msg_modulus for ph in self.phase(cts)], dtype=np.uint64)
+
+
+def seed_words(seed: int) -> np.ndarray:
+    """A 128-bit compression seed as the (lo, hi) u64 pair of the C interface."""
+    if not 0 <= seed < 1 << 128:
+        raise ValueError(f"compression seed out of range: {seed}")
+    return np.array([seed & ((1 << 64) - 1), seed >> 64], dtype=np.uint64)
+
+
+def stream_words128(seed: int, first: int, count: int) -> np.ndarray:
+    """u128 mask words first .. first + count - 1 of a seed's stream as (count, 2) u64 pairs (lo, hi): word w is
+    bytes 16 w + 1 .. 16 w + 16 of the AES-CTR table, little endian (include/tfhe_hip.h)."""
+    out = np.zeros((count, 2), dtype=np.uint64)
+    _check(_lib().tfhe_hip_csprng_words128(_u64(seed_words(seed)), first, count, _u64(out)))
+    return out
+
+
+class CompressedSquashedKey:
+    """The seeded squashing key a server ingests without any secret: bodies [n][L][k+1][N] of u128 words as (lo, hi)
+    pairs and the 128-bit seed of their masks (include/tfhe_hip.h, the seeded squashing key; parity unpinned).
+    `Squasher.load_compressed_key` expands it on the device; `decompress()` is the host route and its reference."""
+
+    def __init__(self, params: SnsParams, seed: int, bodies: np.ndarray):
+        b = _c_u64(bodies)
+        if b.size != _lib().tfhe_hip_sns_seeded_bodies_len(ctypes.byref(params)) or b.size == 0:
+            raise ValueError("CompressedSquashedKey: the bodies do not match the parameters")
+        self.params, self.seed = params, int(seed)
+        self.bodies = b.reshape(params.n, params.level, params.k + 1, params.N, 2)
+        seed_words(self.seed)
+
+    def decompress(self) -> "DecompressedSquashedKey":
+        p = self.params
+        bsk = np.zeros(_lib().tfhe_hip_sns_bsk_len(ctypes.byref(p)), dtype=np.uint64)
+        _check(_lib().tfhe_hip_sns_decompress_bsk(ctypes.byref(p), _u64(seed_words(self.seed)), _u64(self.bodies),
+                                                  _u64(bsk)))
+        return DecompressedSquashedKey(p, bsk)
+
+
+class DecompressedSquashedKey:
+    """Standard-domain words of a squashing BSK in the layout `Squasher.load_key` reads ([i][c*L+l][j][lo, hi][N])."""
+
+    def __init__(self, params: SnsParams, bsk: np.ndarray):
+        self.params, self.bsk = params, bsk
 
 
 class Squasher:
@@ -111,6 +179,28 @@ class Squasher:
         b = _c_u64(key.bsk)
         _check(_lib().tfhe_hip_sns_load_key(self._h, _u64(b), b.size))
         return self
+
+    def load_compressed_key(self, key: CompressedSquashedKey) -> "Squasher":
+        """Bodies and seed go up, the masks are generated into the key layout on the device
+        (tfhe_amd/csrc/seeded_keys128.hip) and the usual conversion follows: the same resident key as
+        `load_key(key.decompress())`, bit for bit."""
+        b = _c_u64(key.bodies).ravel()
+        _check(_lib().tfhe_hip_sns_load_key_seeded(self._h, _u64(seed_words(key.seed)), _u64(b), b.size))
+        return self
+
+    def seeded_load_stats(self) -> dict:
+        """Device milliseconds of the last load_compressed_key: upload, expansion, conversion."""
+        v = [ctypes.c_double() for _ in range(3)]
+        _check(_lib().tfhe_hip_sns_seeded_load_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("upload_ms", "expand_ms", "convert_ms"), (x.value for x in v)))
+
+    def seeded_expand(self, key: CompressedSquashedKey):
+        """Test aid: the loader's expansion alone -> (key words in the loader's layout, guard words behind them)."""
+        b = _c_u64(key.bodies).ravel()
+        n = _lib().tfhe_hip_sns_bsk_len(ctypes.byref(self.params))
+        out = np.zeros(n + SEEDED_GUARD_WORDS, dtype=np.uint64)
+        _check(_lib().tfhe_hip_sns_seeded_expand_bsk(self._h, _u64(seed_words(key.seed)), _u64(b), _u64(out)))
+        return out[:n], out[n:]
 
     def squash(self, small: np.ndarray, msg_modulus: int = 16) -> np.ndarray:
         """small-key ciphertexts (B x (n+1)) -> B x (k N + 1) x 2 u64 (128-bit LWEs, (lo, hi))."""

@@ -20,6 +20,7 @@ from typing import List, Optional
 import numpy as np
 
 from . import RngKey, _c_u64, _check, _stream_handle, _u64, lib, rng_key
+from .sns import SEEDED_GUARD_WORDS, seed_words
 
 SNS_PKS_PRESET_FHEVM = 0
 _U64P = ctypes.POINTER(ctypes.c_uint64)
@@ -72,6 +73,14 @@ def _lib():
         L.tfhe_hip_sns_pks_compress.argtypes = [P, _U64P, ctypes.c_uint32, _U64P]
         L.tfhe_hip_sns_pks_extract.argtypes = [P, _U64P, ctypes.c_uint32, _U64P]
         L.tfhe_hip_glwe_phase128.argtypes = [ctypes.c_uint32, ctypes.c_uint32, _U64P, _U64P, _U64P]
+        L.tfhe_hip_sns_pks_seeded_bodies_len.argtypes = [P]
+        L.tfhe_hip_sns_pks_seeded_bodies_len.restype = ctypes.c_size_t
+        L.tfhe_hip_sns_pks_seeded_keygen.argtypes = [P, ctypes.c_uint64, _U64P, _U64P, _U64P, _U64P]
+        L.tfhe_hip_sns_pks_seeded_keygen_k.argtypes = [P, ctypes.POINTER(RngKey), _U64P, _U64P, _U64P, _U64P]
+        L.tfhe_hip_sns_pks_decompress_key.argtypes = [P, _U64P, _U64P, _U64P]
+        L.tfhe_hip_sns_pks_load_key_seeded.argtypes = [ctypes.c_void_p, _U64P, _U64P, ctypes.c_size_t]
+        L.tfhe_hip_sns_pks_seeded_load_stats.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_double)] * 3
+        L.tfhe_hip_sns_pks_seeded_expand_key.argtypes = [ctypes.c_void_p, _U64P, _U64P, _U64P]
         _BOUND = True
     return L
 
@@ -97,8 +106,52 @@ class SquashedCompressionKey:
         self.post_packing_key = np.zeros(params.out_k * params.out_N, dtype=np.uint64)
         self.pksk = np.zeros(L.tfhe_hip_sns_pksk_len(ctypes.byref(params)), dtype=np.uint64) if with_key else None
         rk = rng_key(seed)  # None: 192 bits of OS entropy (production); an int: the public test stream
+        self._rk = rk       # compress() draws the same post-packing key from it
         _check(L.tfhe_hip_sns_pks_keygen_k(ctypes.byref(params), ctypes.byref(rk), _u64(self.in_key),
                                            _u64(self.post_packing_key), _u64(self.pksk) if with_key else None))
+
+    def compress(self, mask_seed: Optional[int] = None) -> "CompressedSquashedCompressionKey":
+        """The seeded form of this packing key (the CompressedNoiseSquashingCompressionKey::new role): a fresh key
+        to the same post-packing key, bodies only, its masks the 128-bit AES-CTR stream of `mask_seed` (OS entropy
+        when None; a given seed makes every mask public, test data only).  Parity with tfhe-rs unpinned."""
+        import os
+        p = self.params
+        ms = int.from_bytes(os.urandom(16), "little") if mask_seed is None else int(mask_seed)
+        bodies = np.zeros((p.in_dim, p.level, p.out_N, 2), dtype=np.uint64)
+        out_key = np.zeros_like(self.post_packing_key)
+        _check(_lib().tfhe_hip_sns_pks_seeded_keygen_k(ctypes.byref(p), ctypes.byref(self._rk), _u64(seed_words(ms)),
+                                                       _u64(self.in_key), _u64(out_key), _u64(bodies)))
+        assert np.array_equal(out_key, self.post_packing_key)
+        return CompressedSquashedCompressionKey(p, ms, bodies)
+
+
+class CompressedSquashedCompressionKey:
+    """The seeded ct128 packing key a server ingests without any secret: bodies [in_dim][level][out_N] of u128 words
+    as (lo, hi) pairs, storage row s = decomposition level `level - s`, and the 128-bit seed of their masks
+    (include/tfhe_hip.h; parity unpinned).  `SquashedPacker.load_compressed_key` expands it on the device;
+    `decompress()` is the host route and its reference."""
+
+    def __init__(self, params: SnsPksParams, seed: int, bodies: np.ndarray):
+        b = _c_u64(bodies)
+        if b.size != _lib().tfhe_hip_sns_pks_seeded_bodies_len(ctypes.byref(params)) or b.size == 0:
+            raise ValueError("CompressedSquashedCompressionKey: the bodies do not match the parameters")
+        self.params, self.seed = params, int(seed)
+        self.bodies = b.reshape(params.in_dim, params.level, params.out_N, 2)
+        seed_words(self.seed)
+
+    def decompress(self) -> "DecompressedSquashedCompressionKey":
+        p = self.params
+        pksk = np.zeros(_lib().tfhe_hip_sns_pksk_len(ctypes.byref(p)), dtype=np.uint64)
+        _check(_lib().tfhe_hip_sns_pks_decompress_key(ctypes.byref(p), _u64(seed_words(self.seed)), _u64(self.bodies),
+                                                      _u64(pksk)))
+        return DecompressedSquashedCompressionKey(p, pksk)
+
+
+class DecompressedSquashedCompressionKey:
+    """Standard-domain words of a ct128 packing key in the layout `SquashedPacker.load_key` reads."""
+
+    def __init__(self, params: SnsPksParams, pksk: np.ndarray):
+        self.params, self.pksk = params, pksk
 
 
 def pack_host(params: SnsPksParams, pksk: np.ndarray, lwes: np.ndarray) -> np.ndarray:
@@ -189,6 +242,27 @@ class SquashedPacker:
         k = _c_u64(key.pksk)
         _check(_lib().tfhe_hip_sns_pks_load_key(self._h, _u64(k), k.size))
         return self
+
+    def load_compressed_key(self, key: CompressedSquashedCompressionKey) -> "SquashedPacker":
+        """Bodies and seed go up and the masks are generated straight into the resident key on the device
+        (tfhe_amd/csrc/seeded_keys128.hip): the same resident key as `load_key(key.decompress())`, bit for bit."""
+        b = _c_u64(key.bodies).ravel()
+        _check(_lib().tfhe_hip_sns_pks_load_key_seeded(self._h, _u64(seed_words(key.seed)), _u64(b), b.size))
+        return self
+
+    def seeded_load_stats(self) -> dict:
+        """Device milliseconds of the last load_compressed_key: upload, expansion, correction."""
+        v = [ctypes.c_double() for _ in range(3)]
+        _check(_lib().tfhe_hip_sns_pks_seeded_load_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("upload_ms", "expand_ms", "corr_ms"), (x.value for x in v)))
+
+    def seeded_expand(self, key: CompressedSquashedCompressionKey):
+        """Test aid: the loader's expansion alone -> (key words in the loader's layout, guard words behind them)."""
+        b = _c_u64(key.bodies).ravel()
+        n = _lib().tfhe_hip_sns_pksk_len(ctypes.byref(self.params))
+        out = np.zeros(n + SEEDED_GUARD_WORDS, dtype=np.uint64)
+        _check(_lib().tfhe_hip_sns_pks_seeded_expand_key(self._h, _u64(seed_words(key.seed)), _u64(b), _u64(out)))
+        return out[:n], out[n:]
 
     def pack(self, lwes: np.ndarray) -> np.ndarray:
         """count squashed LWEs (count, in_dim + 1, 2) -> (ceil(count / lwe_per_glwe), out_k + 1, 2, N) GLWEs."""
