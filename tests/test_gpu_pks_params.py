@@ -28,6 +28,7 @@ from test_gpu_keyswitch import _edge_rows
 pytestmark = pytest.mark.gpu
 
 U64 = 2 ** 64 - 1
+EINVAL = -1                                                 # TFHE_HIP_EINVAL
 # (in_dim, out_k, out_N, base_log, level, lwe_per_glwe) -> the GEMM tfhe_hip_pks_create must choose
 SWEEP = {
     "mfma_k64_smallest": ((64, 1, 32, 4, 1, 32), "mfma"),
@@ -399,5 +400,25 @@ def test_load_key_behind_async_call(oracle_mod, name):
         got_a = xa.check(oracle_mod, opp, key_a, f"{name}: async pack under key A")
         _assert_groups_equal_oracle(oracle_mod, pp, opp, key_b, X, got_b, None, f"{name}: host pack under key B")
         assert not np.array_equal(got_a, got_b)
+    finally:
+        packer.close()
+
+
+# ---- 6. refusals -----------------------------------------------------------------------------------------
+def test_refused_loads_leave_the_resident_key():
+    """tfhe_hip_pks_load_key with a null context, null words and the lengths len - 1, len + 1 and 0: EINVAL each, and
+    the pack under the resident key is what it was."""
+    from tfhe_amd import _u64
+    pp, _, key, lwes = sweep_inputs("mfma_k64_smallest")
+    load = C._lib().tfhe_hip_pks_load_key
+    words = np.ascontiguousarray(key.pksk)
+    packer = _packer(pp, key)
+    try:
+        before = packer.pack(lwes[:65])
+        assert load(None, _u64(words), words.size) == EINVAL
+        assert load(packer._h, None, words.size) == EINVAL
+        for wrong in (words.size - 1, words.size + 1, 0):
+            assert load(packer._h, _u64(words), wrong) == EINVAL
+        assert np.array_equal(packer.pack(lwes[:65]), before)
     finally:
         packer.close()

@@ -56,8 +56,9 @@ def _squash_pair(sq, n, seed, salt):
     return dev, ckey.decompress().bsk
 
 
-# chunk None: the whole key in one launch (75 GGSWs per chunk); 1 and 2: launches whose first row is not row 0
-@pytest.mark.parametrize("n,chunk", [(1, None), (2, None), (3, None), (3, "1"), (3, "2")])
+# chunk None: the whole key in one launch (75 GGSWs per chunk); 1 and 2: launches whose first row is not row 0; n = 76
+# with the default chunk: a launch of 75 GGSWs and one of the last GGSW alone
+@pytest.mark.parametrize("n,chunk", [(1, None), (2, None), (3, None), (3, "1"), (3, "2"), (76, None)])
 def test_squashing_rows(squashers, monkeypatch, n, chunk):
     if chunk is None:
         monkeypatch.delenv(CHUNK_ENV, raising=False)
@@ -163,7 +164,75 @@ def test_packer_load_sequence():
     assert np.array_equal(SC.decrypt_list(key, SC._compress_groups(pp, got, count)), msgs)
 
 
+# n = 76 is the smallest n whose 27 n = 2052 polynomials exceed both the unseeded loader's chunk of 2048 polynomials and
+# the seeded loader's 75 GGSWs: every smaller n is one chunk on both routes
+N_EDGE = 76
+
+
+@pytest.fixture(scope="module")
+def edge_keys():
+    """two keys of random body words at N_EDGE (no real keys: the routes are compared with each other) and their
+    host decompressions, built once and left read-only"""
+    sp = C.squash_params(N_EDGE)
+    out = []
+    for seed in (C.MASK_SEED, C.MASK_SEED_TOP):
+        ck = S.CompressedSquashedKey(sp, seed, _rand_words(N_EDGE * sp.level * (sp.k + 1) * 2 * sp.N, N_EDGE))
+        dk = ck.decompress()
+        ck.bodies.setflags(write=False)
+        dk.bsk.setflags(write=False)
+        out += [ck, dk]
+    return out
+
+
+# None: chunks of 75 GGSWs and 1; "7": ten chunks of 7 and a tail of 6.  The unseeded loads: 2048 polynomials and 4
+@pytest.mark.parametrize("chunk", [None, "7"])
+def test_chunk_edges_of_both_sources(squashers, edge_keys, monkeypatch, chunk):
+    """unseeded A -> seeded B -> unseeded B -> seeded A at n = 76, where both loaders run a second chunk: the
+    accumulator and the output of one ciphertext after each seeded load equal those of the host route, bit for bit"""
+    if chunk is None:
+        monkeypatch.delenv(CHUNK_ENV, raising=False)
+    else:
+        monkeypatch.setenv(CHUNK_ENV, chunk)
+    ck_a, dk_a, ck_b, dk_b = edge_keys
+    x = _rand_words(N_EDGE + 1, 7600).reshape(1, N_EDGE + 1)
+    sq = squashers(N_EDGE)
+    acc_a, out_a = _run(sq.load_key(dk_a), x)
+    acc_sb, out_sb = _run(sq.load_compressed_key(ck_b), x)
+    acc_b, out_b = _run(sq.load_key(dk_b), x)
+    acc_sa, out_sa = _run(sq.load_compressed_key(ck_a), x)
+    assert np.array_equal(acc_sb, acc_b) and np.array_equal(out_sb, out_b)
+    assert np.array_equal(acc_sa, acc_a) and np.array_equal(out_sa, out_a)
+    assert not np.array_equal(acc_a, acc_b) and not np.array_equal(out_a, out_b)
+
+
 # ------------------------------------------------------------------ refusals
+def _refuses(load, ctx, words):
+    """null context, null words and the lengths len - 1, len + 1 and 0: EINVAL each"""
+    assert load(None, tfhe_amd._u64(words), words.size) == EINVAL
+    assert load(ctx, None, words.size) == EINVAL
+    for wrong in (words.size - 1, words.size + 1, 0):
+        assert load(ctx, tfhe_amd._u64(words), wrong) == EINVAL
+
+
+def test_refused_unseeded_loads_leave_the_resident_key(squashers, load_inputs):
+    _, x = load_inputs
+    sp, key, ckey, dk = C.squash_keys(N_LOAD)
+    sq = squashers(N_LOAD)
+    before = sq.load_key(dk).squash(x)
+    _refuses(S._lib().tfhe_hip_sns_load_key, sq._h, np.ascontiguousarray(dk.bsk).ravel())
+    assert np.array_equal(sq.squash(x), before)
+
+    pp, pkey, pck, pdk = C.packing_keys(32, 1, 64, 3)
+    lw = R.encrypt(pp, pkey.in_key, np.arange(5, dtype=np.uint64))
+    packer = SC.SquashedPacker(pp, 0)
+    try:
+        pbefore = packer.load_key(pdk).pack(lw)
+        _refuses(SC._lib().tfhe_hip_sns_pks_load_key, packer._h, np.ascontiguousarray(pdk.pksk).ravel())
+        assert np.array_equal(packer.pack(lw), pbefore)
+    finally:
+        packer.close()
+
+
 def test_refused_loads_leave_the_resident_key(squashers, load_inputs, monkeypatch):
     monkeypatch.delenv(CHUNK_ENV, raising=False)
     _, x = load_inputs

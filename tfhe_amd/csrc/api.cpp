@@ -1206,58 +1206,8 @@ static tfhe::seeded_shape seeded_shape_of(const tfhe_params& p, uint32_t g, uint
   return tfhe::seeded_shape{p.n, p.k, p.N, p.pbs_level, p.ks_level, g, count};
 }
 
-static tfhe::seeded_round_keys round_keys_of(const uint64_t seed[2]) {
-  tfhe::seeded_round_keys rk;
-  tfhe::seeded::aes_round_keys(seed, rk.w);
-  return rk;
-}
-
-// device buffers that live for one call (the uploaded bodies of a seeded load): freed on every path out
-struct temp_buffers {
-  std::vector<std::pair<int, void*>> v;  // (device, pointer)
-  int alloc(int device, size_t bytes, void** out) {
-    DeviceGuard g(device);
-    *out = nullptr;
-    HIP_TRY(hipMalloc(out, bytes ? bytes : 8));
-    v.emplace_back(device, *out);
-    return 0;
-  }
-  ~temp_buffers() {
-    for (auto& x : v) {
-      DeviceGuard g(x.first);
-      (void)hipFree(x.second);
-    }
-  }
-};
-
-// device-time marks on one shard's stream, destroyed with the scope; without a shard mark() does nothing
-struct stream_marks {
-  shard* s;
-  std::vector<hipEvent_t> ev;
-  int mark() {
-    if (!s) return 0;
-    DeviceGuard g(s->device);
-    hipEvent_t e = nullptr;
-    HIP_TRY(hipEventCreate(&e));
-    ev.push_back(e);
-    HIP_TRY(hipEventRecord(e, s->stream));
-    return 0;
-  }
-  int ms(size_t from, size_t to, double* out) {  // waits for mark `to`
-    DeviceGuard g(s->device);
-    float t = 0;
-    HIP_TRY(hipEventSynchronize(ev[to]));
-    HIP_TRY(hipEventElapsedTime(&t, ev[from], ev[to]));
-    *out = t;
-    return 0;
-  }
-  ~stream_marks() {
-    for (auto e : ev) (void)hipEventDestroy(e);
-  }
-};
-
 // The pipeline of a checked load.  A seeded load leaves its three phases on shard 0's stream in c->seeded_ms
-// (tfhe_hip_seeded_load_stats): marks 0-1 the upload, 2-3 the expansion, 3-4 the conversion.
+// (tfhe_hip_seeded_load_stats): phase 0 the upload, 1 the expansion, 2 the conversion.
 static int key_load_run(tfhe_ctx* c, const key_load& r) {
   const bool seeded = r.src == SRC_SEEDED, with_ksk = r.with_ksk;
   const size_t nd = c->sh.size(), bsk_len = std_bsk_len(c->p, r.g), ksk_len = tfhe::client::ksk_len(c->p);
@@ -1296,22 +1246,22 @@ static int key_load_run(tfhe_ctx* c, const key_load& r) {
   // 2. travel: onto shard 0, then to every other shard, once.  Standard keys land where the conversion reads them;
   // bodies (1 / (k + 1) and 1 / (n + 1) of the words) in temporaries, which the conversion's stream synchronise of
   // every shard precedes the release of.
-  temp_buffers tmp;
+  call_buffers tmp;
   std::vector<u64*> dst_b(nd), dst_k(nd);
   for (size_t i = 0; i < nd; i++) {
     shard& s = c->sh[i];
     dst_b[i] = (u64*)s.d_stage, dst_k[i] = s.d_ksk;
     if (!seeded) continue;
-    RC_TRY(tmp.alloc(s.device, r.bsk_len * 8, (void**)&dst_b[i]));
-    if (with_ksk) RC_TRY(tmp.alloc(s.device, r.ksk_len * 8, (void**)&dst_k[i]));
+    RC_TRY(tmp.alloc(s.device, r.bsk_len * 8, &dst_b[i]));
+    if (with_ksk) RC_TRY(tmp.alloc(s.device, r.ksk_len * 8, &dst_k[i]));
   }
   shard& s0 = c->sh[0];
-  stream_marks tm{seeded ? &s0 : nullptr, {}};
+  phase_timer tm(seeded ? &s0 : nullptr);
   // a device source is read in place on shard 0: the caller's BSK is broadcast and converted without a copy
   const u64* bsk0 = r.src == SRC_DEVICE ? (const u64*)r.bsk : dst_b[0];
   {
     DeviceGuard g(s0.device);
-    RC_TRY(tm.mark());
+    RC_TRY(tm.tick(-1));
     if (r.src != SRC_DEVICE) {
       RC_TRY(upload_pinned(s0, dst_b[0], r.bsk, r.bsk_len * 8));
       if (with_ksk) RC_TRY(upload_pinned(s0, dst_k[0], r.ksk, r.ksk_len * 8));
@@ -1319,7 +1269,7 @@ static int key_load_run(tfhe_ctx* c, const key_load& r) {
       HIP_TRY(hipMemcpyAsync(dst_k[0], r.ksk, r.ksk_len * 8, hipMemcpyDeviceToDevice, s0.stream));
       HIP_TRY(hipStreamSynchronize(s0.stream));
     }
-    RC_TRY(tm.mark());
+    RC_TRY(tm.tick(0));
   }
   RC_TRY(broadcast(c, bsk0, dst_b, r.bsk_len));  // nothing to do on one shard (bcast_plan)
   if (with_ksk) RC_TRY(broadcast(c, dst_k[0], dst_k, r.ksk_len));
@@ -1330,21 +1280,17 @@ static int key_load_run(tfhe_ctx* c, const key_load& r) {
     shard& s = c->sh[i];
     if (seeded) {  // 3. expand the bodies into the buffers that the other sources fill by copy
       DeviceGuard g(s.device);
-      if (i == 0) RC_TRY(tm.mark());
+      if (i == 0) RC_TRY(tm.tick(-1));
       HIP_TRY(tfhe::launch_seeded_rows(rk_b, r.g > 1 ? tfhe::SEEDED_BSK_MB : tfhe::SEEDED_BSK, shp, dst_b[i],
                                        (u64*)s.d_stage, s.stream));
       if (with_ksk) HIP_TRY(tfhe::launch_seeded_rows(rk_k, tfhe::SEEDED_KSK, shp, dst_k[i], s.d_ksk, s.stream));
-      if (i == 0) RC_TRY(tm.mark());
+      if (i == 0) RC_TRY(tm.tick(1));
     }
     // 4. convert (waits for the shard's stream)
     RC_TRY(convert_keys(c, s, i == 0 && !seeded ? bsk0 : (const u64*)s.d_stage, bsk_len, with_ksk));
     if (i == 0 && seeded) {
-      RC_TRY(tm.mark());
-      double ms[3];
-      RC_TRY(tm.ms(0, 1, &ms[0]));
-      RC_TRY(tm.ms(2, 3, &ms[1]));
-      RC_TRY(tm.ms(3, 4, &ms[2]));
-      std::copy(ms, ms + 3, c->seeded_ms);
+      RC_TRY(tm.tick(2));
+      RC_TRY(tm.totals(c->seeded_ms, 3));
     }
   }
   // 5. commit
@@ -1403,14 +1349,10 @@ int tfhe_hip_load_keys_mb_seeded(tfhe_ctx* c, uint32_t g, const uint64_t bsk_see
 
 int tfhe_hip_seeded_load_stats(const tfhe_ctx* c, double* upload_ms, double* expand_ms, double* convert_ms) {
   if (!c) return fail(TFHE_HIP_EINVAL, "seeded_load_stats: null ctx");
-  if (upload_ms) *upload_ms = c->seeded_ms[0];
-  if (expand_ms) *expand_ms = c->seeded_ms[1];
-  if (convert_ms) *convert_ms = c->seeded_ms[2];
-  return 0;
+  return seeded_ms_read(c->seeded_ms, upload_ms, expand_ms, convert_ms);
 }
 
-// ---- the expansion kernels alone (test-facing): the launchers the loaders use, on shard 0, into a fresh device
-// buffer of out_len + TFHE_HIP_SEEDED_GUARD_WORDS words filled with 0xA5 bytes, all of which is copied back
+// ---- the expansion kernels alone (test-facing): the launcher the loaders use, on shard 0, through guarded_expand
 struct expand_job {
   tfhe::seeded_kind kind;
   tfhe::seeded_shape shp;
@@ -1423,17 +1365,11 @@ static int seeded_expand_call(tfhe_ctx* c, const expand_job& j, const uint64_t s
   std::lock_guard<std::mutex> lk(c->mu);
   shard& s = c->sh[0];
   DeviceGuard gd(s.device);
-  temp_buffers tmp;
-  u64 *d_bodies = nullptr, *d_out = nullptr;
-  const size_t out_bytes = (j.out_len + TFHE_HIP_SEEDED_GUARD_WORDS) * 8;
-  RC_TRY(tmp.alloc(s.device, j.bodies_len * 8, (void**)&d_bodies));
-  RC_TRY(tmp.alloc(s.device, out_bytes, (void**)&d_out));
-  HIP_TRY(hipMemsetAsync(d_out, 0xA5, out_bytes, s.stream));
-  if (j.bodies_len) HIP_TRY(hipMemcpyAsync(d_bodies, bodies, j.bodies_len * 8, hipMemcpyHostToDevice, s.stream));
-  HIP_TRY(tfhe::launch_seeded_rows(rk, j.kind, j.shp, d_bodies, d_out, s.stream));
-  HIP_TRY(hipMemcpyAsync(out_host, d_out, out_bytes, hipMemcpyDeviceToHost, s.stream));
-  HIP_TRY(hipStreamSynchronize(s.stream));
-  return 0;
+  return guarded_expand(s, j.bodies_len * 8, j.out_len, out_host, [&](u64* d_bodies, u64* d_out) -> int {
+    if (j.bodies_len) HIP_TRY(hipMemcpyAsync(d_bodies, bodies, j.bodies_len * 8, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(tfhe::launch_seeded_rows(rk, j.kind, j.shp, d_bodies, d_out, s.stream));
+    return 0;
+  });
 }
 
 int tfhe_hip_seeded_expand_bsk(tfhe_ctx* c, uint32_t g, const uint64_t seed[2], const uint64_t* bodies,
@@ -1540,10 +1476,10 @@ int tfhe_hip_load_ms_key_seeded(tfhe_ctx* c, const uint64_t seed[2], const uint6
   const tfhe::seeded_round_keys rk = count ? round_keys_of(seed) : tfhe::seeded_round_keys{};
   tfhe::seeded_shape shp{};
   shp.n = c->p.n, shp.count = count;
-  temp_buffers tmp;  // every shard's bodies, released after the installer's last synchronise
+  call_buffers tmp;  // every shard's bodies, released after the installer's last synchronise
   return install_ms_zeros(c, count, t, [&](shard& s) -> int {
     u64* d_bodies = nullptr;
-    RC_TRY(tmp.alloc(s.device, (size_t)count * 8, (void**)&d_bodies));
+    RC_TRY(tmp.alloc(s.device, (size_t)count * 8, &d_bodies));
     HIP_TRY(hipMemcpyAsync(d_bodies, bodies, (size_t)count * 8, hipMemcpyHostToDevice, s.stream));
     HIP_TRY(tfhe::launch_seeded_rows(rk, tfhe::SEEDED_LIST, shp, d_bodies, s.d_ms_zeros, s.stream));
     return 0;

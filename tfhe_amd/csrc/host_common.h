@@ -1,17 +1,23 @@
-// host_common.h — plumbing shared by the C ABI translation units (api.cpp, pks_api.cpp, sns_api.cpp, sns_pks_api.cpp):
-// error reporting, HIP call checking, the device guard, stream resolution, buffer growth, and the device slot:
-// the stream, the cross-stream workspace ordering and the host-call staging of every device context.  Host code only.
+// host_common.h — plumbing shared by the C ABI translation units (api.cpp, pks_api.cpp, sns_api.cpp, sns_pks_api.cpp,
+// matmul_api.cpp): error reporting, HIP call checking, the device guard, stream resolution, buffer growth, the device
+// slot (the stream, the cross-stream workspace ordering and the host-call staging of every device context), and the
+// key-load tools: the load skeleton of the side contexts (side_key_load) and what the seeded loads of all contexts
+// share (round_keys_of, call_buffers, phase_timer, seeded_ms_read, guarded_expand, env_positive).  Host code only.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include <initializer_list>
+#include <mutex>
 #include <utility>
 #include <vector>
 
 #include "../../include/tfhe_hip.h"
+#include "client.h"
+#include "pbs_kernels.h"
 
 // the library's thread-local error slot (owned by api.cpp)
 int tfhe_hip_set_error(int code, const char* msg);
@@ -196,35 +202,60 @@ int staged_run(S& s, staged_in in, size_t out_bytes, std::initializer_list<copy_
   return 0;
 }
 
-// a device buffer that lives for one call (the uploaded bodies of a seeded load): freed on every path out; the
-// caller's device is current at alloc and at scope end
-struct call_buffer {
-  void* p = nullptr;
-  int alloc(size_t bytes) {
-    HIP_TRY(hipMalloc(&p, bytes ? bytes : 8));
+// a tuning variable that counts something: its value where it is a positive number, `dflt` otherwise
+size_t env_positive(const char* name, size_t dflt) {
+  const char* e = getenv(name);
+  const long x = e ? atol(e) : 0;
+  return x > 0 ? (size_t)x : dflt;
+}
+
+// the AES key schedule of a compression seed, once per seed on the host: the 44 words travel as a launch argument
+tfhe::seeded_round_keys round_keys_of(const uint64_t seed[2]) {
+  tfhe::seeded_round_keys rk;
+  tfhe::seeded::aes_round_keys(seed, rk.w);
+  return rk;
+}
+
+// Device buffers that live for one call (the uploaded bodies of a seeded load, the output of an expand aid), on any
+// devices: each is freed under a guard for its own device on every path out of the scope.
+struct call_buffers {
+  std::vector<std::pair<int, void*>> v;  // (device, pointer)
+  template <class T>
+  int alloc(int device, size_t bytes, T** out) {
+    DeviceGuard g(device);
+    *out = nullptr;
+    HIP_TRY(hipMalloc(out, bytes ? bytes : 8));
+    v.emplace_back(device, *out);
     return 0;
   }
-  ~call_buffer() {
-    if (p) (void)hipFree(p);
+  ~call_buffers() {
+    for (auto& x : v) {
+      DeviceGuard g(x.first);
+      (void)hipFree(x.second);
+    }
   }
 };
 
-// Device-time split of a load on one stream: tick(phase) books the time since the previous tick under `phase`
-// (tick(-1) only opens an interval); totals() waits for the last tick.  Events are destroyed with the scope.
+// Device-time split of a seeded load on one slot's stream: tick(phase) books the time since the previous tick under
+// `phase` (tick(-1) only opens an interval); totals() waits for the last tick.  Without a slot (a load from another
+// source) tick() does nothing.  Events are destroyed with the scope.
 struct phase_timer {
-  hipStream_t st;
+  const device_slot* s;
   std::vector<std::pair<hipEvent_t, int>> ev;
-  explicit phase_timer(hipStream_t s) : st(s) {}
+  explicit phase_timer(const device_slot* slot) : s(slot) {}
   int tick(int phase) {
+    if (!s) return 0;
+    DeviceGuard g(s->device);
     hipEvent_t e = nullptr;
     HIP_TRY(hipEventCreate(&e));
     ev.emplace_back(e, phase);
-    HIP_TRY(hipEventRecord(e, st));
+    HIP_TRY(hipEventRecord(e, s->stream));
     return 0;
   }
   int totals(double* ms, int phases) {
     for (int i = 0; i < phases; i++) ms[i] = 0;
     if (ev.empty()) return 0;
+    DeviceGuard g(s->device);
     HIP_TRY(hipEventSynchronize(ev.back().first));
     for (size_t i = 1; i < ev.size(); i++) {
       if (ev[i].second < 0 || ev[i].second >= phases) continue;
@@ -238,6 +269,50 @@ struct phase_timer {
     for (auto& x : ev) (void)hipEventDestroy(x.first);
   }
 };
+
+// the *_seeded_load_stats read-out: a context's seeded_ms (upload, expansion, conversion or correction of its last
+// seeded load, device ms) into the out-pointers that are set
+int seeded_ms_read(const double ms[3], double* upload_ms, double* expand_ms, double* third_ms) {
+  if (upload_ms) *upload_ms = ms[0];
+  if (expand_ms) *expand_ms = ms[1];
+  if (third_ms) *third_ms = ms[2];
+  return 0;
+}
+
+// The key load of a side context (C: tfhe_pks_ctx, tfhe_sns_ctx, tfhe_sns_pks_ctx), after the caller's argument and
+// length checks.  prepare() holds every allocation and every ws_grow, fill() enqueues the copies and kernels on
+// c->stream.  Every refusal and every allocation comes before the resident key is touched: a refused load, or one that
+// cannot allocate, leaves the previous key usable; from fill() on the ctx has no key until the load has completed.
+template <class C, class P, class F>
+int side_key_load(C* c, P&& prepare, F&& fill) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  RC_TRY(ws_host_wait(*c));  // a call in flight on a caller's stream still reads the resident key
+  RC_TRY(prepare());
+  c->key = false;
+  RC_TRY(fill());
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->key = true;
+  return 0;
+}
+
+// The test aid behind the *_seeded_expand_* entry points (the caller holds the context's lock and has set the slot's
+// device): a buffer of body_bytes and a fresh output of out_len + TFHE_HIP_SEEDED_GUARD_WORDS words filled with 0xA5
+// bytes, step(d_bodies, d_out) enqueues the uploads and the loader's launches on the slot's stream, and all of the
+// output is copied back, guard words included.
+template <class F>
+int guarded_expand(device_slot& s, size_t body_bytes, size_t out_len, uint64_t* out_host, F&& step) {
+  call_buffers tmp;
+  uint64_t *d_bodies = nullptr, *d_out = nullptr;
+  const size_t out_bytes = (out_len + TFHE_HIP_SEEDED_GUARD_WORDS) * 8;
+  RC_TRY(tmp.alloc(s.device, body_bytes, &d_bodies));
+  RC_TRY(tmp.alloc(s.device, out_bytes, &d_out));
+  HIP_TRY(hipMemsetAsync(d_out, 0xA5, out_bytes, s.stream));
+  RC_TRY(step(d_bodies, d_out));
+  HIP_TRY(hipMemcpyAsync(out_host, d_out, out_bytes, hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(hipStreamSynchronize(s.stream));
+  return 0;
+}
 
 int check_binary(const uint64_t* key, size_t len, const char* what) {
   for (size_t i = 0; i < len; i++)

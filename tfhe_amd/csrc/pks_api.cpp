@@ -165,24 +165,25 @@ int tfhe_hip_pks_load_key(tfhe_pks_ctx* c, const uint64_t* pksk, size_t len) {
   if (!c || !pksk) return fail(TFHE_HIP_EINVAL, "pks_load_key: null argument");
   if (len != tfhe::client::pksk_len(c->pp))
     return fail(TFHE_HIP_EINVAL, "pks_load_key: length %zu, expected %zu", len, tfhe::client::pksk_len(c->pp));
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  RC_TRY(ws_host_wait(*c));  // a call in flight on a caller's stream still reads the resident key
-  c->key = false;
   const size_t Nc = (size_t)(c->pp.out_k + 1) * c->pp.out_N;
-  if (!c->d_pksk) HIP_TRY(hipMalloc(&c->d_pksk, len * 8));
-  if (!c->d_corr) HIP_TRY(hipMalloc(&c->d_corr, Nc * 8));
-  HIP_TRY(hipMemcpyAsync(c->d_pksk, pksk, len * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(tfhe::launch_pks_corr(c->d_pksk, (int)(c->pp.in_dim * c->pp.level), (int)Nc, (int)c->pp.base_log, c->d_corr,
-                                c->stream));
-  if (!c->valu) {  // balanced byte planes of the key (ks_mfma.hip's recoding, Nc columns)
-    if (!c->d_planes)
-      HIP_TRY(hipMalloc(&c->d_planes, tfhe::ks_planes_bytes((int)c->pp.in_dim, (int)c->pp.level, (int)Nc - 1)));
-    HIP_TRY(tfhe::launch_ksk_planes(c->d_pksk, (int)c->pp.in_dim, (int)c->pp.level, (int)Nc - 1, c->d_planes, c->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  c->key = true;
-  return 0;
+  return side_key_load(
+      c,
+      [&]() -> int {
+        if (!c->d_pksk) HIP_TRY(hipMalloc(&c->d_pksk, len * 8));
+        if (!c->d_corr) HIP_TRY(hipMalloc(&c->d_corr, Nc * 8));
+        if (!c->valu && !c->d_planes)
+          HIP_TRY(hipMalloc(&c->d_planes, tfhe::ks_planes_bytes((int)c->pp.in_dim, (int)c->pp.level, (int)Nc - 1)));
+        return 0;
+      },
+      [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(c->d_pksk, pksk, len * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(tfhe::launch_pks_corr(c->d_pksk, (int)(c->pp.in_dim * c->pp.level), (int)Nc, (int)c->pp.base_log,
+                                      c->d_corr, c->stream));
+        if (!c->valu)  // balanced byte planes of the key (ks_mfma.hip's recoding, Nc columns)
+          HIP_TRY(tfhe::launch_ksk_planes(c->d_pksk, (int)c->pp.in_dim, (int)c->pp.level, (int)Nc - 1, c->d_planes,
+                                          c->stream));
+        return 0;
+      });
 }
 
 int tfhe_hip_pks_pack_async(tfhe_pks_ctx* c, const uint64_t* d_lwes, size_t count, uint64_t* d_glwes, void* stream) {

@@ -1,7 +1,6 @@
 // sns_api.cpp — C ABI of noise squashing (include/tfhe_hip.h, tfhe_hip_sns_*): key residency,
 // workspaces, chunked launches.  Kernels: sns.hip; host key material: client.cpp.
 #include <hip/hip_runtime_api.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -28,30 +27,21 @@ bool sns_valid(const tfhe_sns_params* sp) {
 // (profiles/r06c_sns_chunk.txt; round 5: 4,687 vs 4,568): the inverse gains more from the smaller per-CMUX working set
 // than the MAC and step 1 lose to the half-size grids
 size_t sns_chunk() {
-  static const size_t v = [] {
-    const char* e = getenv("TFHE_HIP_SNS_CHUNK");
-    const long x = e ? atol(e) : 0;
-    return x > 0 ? (size_t)x : (size_t)512;
-  }();
+  static const size_t v = env_positive("TFHE_HIP_SNS_CHUNK", 512);
   return v;
 }
+
+constexpr size_t LOAD_CHUNK_POLYS = 2048;  // polynomials per chunk of tfhe_hip_sns_load_key
 
 // GGSWs per chunk of a seeded load: the staging buffer takes whole rows, and a GGSW is L (k + 1) rows = 27
 // polynomials, so the 2048 polynomials of tfhe_hip_sns_load_key become 75 GGSWs = 2025.  TFHE_HIP_SNS_SEEDED_CHUNK
 // (GGSWs, read at every load) overrides: the tests cross chunk boundaries at n = 3
 size_t seeded_units(const tfhe_sns_params& sp) {
-  const char* e = getenv("TFHE_HIP_SNS_SEEDED_CHUNK");
-  const long x = e ? atol(e) : 0;
   const size_t unit_polys = (size_t)sp.level * (sp.k + 1) * (sp.k + 1);
-  const size_t u = x > 0 ? (size_t)x : std::max<size_t>(1, 2048 / unit_polys);
+  const size_t u = env_positive("TFHE_HIP_SNS_SEEDED_CHUNK", std::max<size_t>(1, LOAD_CHUNK_POLYS / unit_polys));
   return std::min<size_t>(u, sp.n);
 }
-
-tfhe::seeded_round_keys round_keys_of(const uint64_t seed[2]) {
-  tfhe::seeded_round_keys rk;
-  tfhe::seeded::aes_round_keys(seed, rk.w);
-  return rk;
-}
+size_t seeded_chunk_polys(const tfhe_sns_params& sp) { return seeded_units(sp) * sp.level * (sp.k + 1) * (sp.k + 1); }
 
 }  // namespace
 
@@ -119,11 +109,18 @@ int run_device(tfhe_sns_ctx* c, const u64* d_in, size_t B, u64* d_out, u64* d_ac
   return 0;
 }
 
-int host_call(tfhe_sns_ctx* c, const u64* in, size_t B, uint32_t mm, u64* out, bool acc_only) {
+// the argument checks of the host and the async calls (B == 0 passes: the caller returns before it touches the device)
+int squash_checks(tfhe_sns_ctx* c, const void* in, size_t B, uint32_t mm, const void* out) {
   if (!c) return fail(TFHE_HIP_EINVAL, "sns: null ctx");
   if (!c->key) return fail(TFHE_HIP_ENOKEYS, "sns: key not loaded");
   if (B == 0) return 0;
   if (!in || !out || !mm || mm > c->sp.N || (c->sp.N % mm)) return fail(TFHE_HIP_EINVAL, "sns: bad arguments");
+  return 0;
+}
+
+int host_call(tfhe_sns_ctx* c, const u64* in, size_t B, uint32_t mm, u64* out, bool acc_only) {
+  RC_TRY(squash_checks(c, in, B, mm, out));
+  if (B == 0) return 0;
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
   RC_TRY(ensure_lut(c, mm));
@@ -134,6 +131,55 @@ int host_call(tfhe_sns_ctx* c, const u64* in, size_t B, uint32_t mm, u64* out, b
     return run_device(&s, (const u64*)d[0], B, acc_only ? nullptr : d_out, acc_only ? d_out : nullptr, s.stream);
   });
 }
+
+// what a load of chunks of `per` polynomials needs on the device: the staging buffer of one chunk and, on first use,
+// the spectra
+int key_buffers(tfhe_sns_ctx* c, size_t per) {
+  RC_TRY(ws_grow(*c, &c->d_stage, &c->stage_cap, per * 2 * (size_t)c->sp.N * 8));
+  if (!c->d_bskf) HIP_TRY(hipMalloc(&c->d_bskf, tfhe::sns_fft_key_len(c->sp.n) * 16));
+  return 0;
+}
+
+// Walk the key in chunks of `per` polynomials ((lo, hi) planes) on the ctx's stream.  source(first, np, dst) puts the
+// standard-domain words of polynomials first .. first + np - 1 at dst.  The loaders (d_out == null) stage every chunk
+// in d_stage, which the next chunk's source reuses (same stream: ordered), and convert it to limb spectra at its offset
+// in d_bskf; tm books the conversion as phase 2.  The expand aid gives d_out: the chunks land side by side in it and
+// nothing follows.
+template <class Src>
+int key_chunks(tfhe_sns_ctx* c, size_t per, u64* d_out, phase_timer& tm, Src&& source) {
+  const size_t poly_words = 2 * (size_t)c->sp.N, polys = tfhe::client::sns_bsk_len(c->sp) / poly_words;
+  for (size_t f = 0; f < polys; f += per) {
+    const size_t np = std::min(per, polys - f);
+    u64* dst = d_out ? d_out + f * poly_words : (u64*)c->d_stage;
+    RC_TRY(source(f, np, dst));
+    if (d_out) continue;
+    HIP_TRY(tfhe::launch_sns_bsk_to_fft(dst, (char*)c->d_bskf + f * tfhe::SNS_FFT_POLY_BYTES, np, c->d_fconst,
+                                        c->stream));
+    RC_TRY(tm.tick(2));
+  }
+  return 0;
+}
+
+// The seeded source of key_chunks, for chunks of whole GGSWs (seeded_units): a row of k + 1 polynomials has one body
+// polynomial, so the bodies of the chunk's rows go up into d_bodies (one chunk's worth, reused by the next chunk) and
+// launch_seeded_rows128 expands them from the chunk's first stream row.  tm books phases 0 and 1.
+struct seeded_source {
+  tfhe_sns_ctx* c;
+  tfhe::seeded_round_keys rk;
+  const u64* bodies;
+  u64* d_bodies;
+  phase_timer& tm;
+  size_t body_bytes(size_t polys) const { return polys / (c->sp.k + 1) * 2 * c->sp.N * 8; }
+  int operator()(size_t first, size_t np, u64* dst) const {
+    const size_t row0 = first / (c->sp.k + 1), rows = np / (c->sp.k + 1);
+    RC_TRY(tm.tick(-1));
+    HIP_TRY(hipMemcpyAsync(d_bodies, bodies + row0 * 2 * c->sp.N, body_bytes(np), hipMemcpyHostToDevice, c->stream));
+    RC_TRY(tm.tick(0));
+    HIP_TRY(tfhe::launch_seeded_rows128(rk, tfhe::SEEDED128_SNS_BSK, {c->sp.k, c->sp.N, c->sp.level}, row0, rows,
+                                        d_bodies, dst, c->stream));
+    return tm.tick(1);
+  }
+};
 
 }  // namespace
 
@@ -196,25 +242,16 @@ int tfhe_hip_sns_load_key(tfhe_sns_ctx* c, const uint64_t* bsk, size_t len) {
   if (!c || !bsk) return fail(TFHE_HIP_EINVAL, "sns_load_key: null argument");
   if (len != tfhe::client::sns_bsk_len(c->sp))
     return fail(TFHE_HIP_EINVAL, "sns_load_key: length %zu, expected %zu", len, tfhe::client::sns_bsk_len(c->sp));
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  RC_TRY(ws_host_wait(*c));  // a call in flight on a caller's stream still reads the resident key
-  c->key = false;
-  if (!c->d_bskf) HIP_TRY(hipMalloc(&c->d_bskf, tfhe::sns_fft_key_len(c->sp.n) * 16));
-  // stage the key words in chunks of polynomials (lo, hi planes) through the staging buffer, convert to limb spectra
-  const size_t poly_words = 2 * (size_t)c->sp.N, polys = len / poly_words, per = 2048;
-  const size_t bytes = per * poly_words * 8;
-  RC_TRY(ws_grow(*c, &c->d_stage, &c->stage_cap, bytes));
-  for (size_t f = 0; f < polys; f += per) {
-    const size_t np = std::min(per, polys - f);
-    HIP_TRY(hipMemcpyAsync(c->d_stage, bsk + f * poly_words, np * poly_words * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(tfhe::launch_sns_bsk_to_fft((const u64*)c->d_stage, (char*)c->d_bskf + f * tfhe::SNS_FFT_POLY_BYTES, np,
-                                        c->d_fconst, c->stream));
-    // the staging buffer is reused by the next chunk's copy: same stream, ordered
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  c->key = true;
-  return 0;
+  const size_t poly_words = 2 * (size_t)c->sp.N;
+  phase_timer none(nullptr);
+  return side_key_load(
+      c, [&] { return key_buffers(c, LOAD_CHUNK_POLYS); },
+      [&] {
+        return key_chunks(c, LOAD_CHUNK_POLYS, nullptr, none, [&](size_t first, size_t np, u64* dst) -> int {
+          HIP_TRY(hipMemcpyAsync(dst, bsk + first * poly_words, np * poly_words * 8, hipMemcpyHostToDevice, c->stream));
+          return 0;
+        });
+      });
 }
 
 size_t tfhe_hip_sns_seeded_bodies_len(const tfhe_sns_params* sp) {
@@ -250,83 +287,48 @@ int tfhe_hip_csprng_words128(const uint64_t seed[2], uint64_t first_word, size_t
   return 0;
 }
 
-// Every refusal and every allocation comes before the resident key is touched: a refused load, or one that cannot
-// allocate, leaves the previous key usable.  Chunks of whole GGSWs: bodies up, rows expanded into the staging buffer,
-// launch_sns_bsk_to_fft as tfhe_hip_sns_load_key runs it, all on the ctx's stream
+// tfhe_hip_sns_load_key from the seeded source: a body buffer of one chunk beside the loader's buffers
 int tfhe_hip_sns_load_key_seeded(tfhe_sns_ctx* c, const uint64_t seed[2], const uint64_t* bodies, size_t len) {
   if (!c || !seed || !bodies) return fail(TFHE_HIP_EINVAL, "sns_load_key_seeded: null argument");
   if (len != tfhe::seeded::sns_bodies_len(c->sp))
     return fail(TFHE_HIP_EINVAL, "sns_load_key_seeded: length %zu, expected %zu", len,
                 tfhe::seeded::sns_bodies_len(c->sp));
-  const tfhe::seeded_round_keys rk = round_keys_of(seed);
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  RC_TRY(ws_host_wait(*c));  // a call in flight on a caller's stream still reads the resident key
-  const tfhe::seeded128_shape shp{c->sp.k, c->sp.N, c->sp.level};
-  const size_t poly_words = 2 * (size_t)c->sp.N, unit_rows = (size_t)c->sp.level * (c->sp.k + 1);
-  const size_t unit_polys = unit_rows * (c->sp.k + 1), units = seeded_units(c->sp);
-  call_buffer d_bodies;
-  RC_TRY(d_bodies.alloc(units * unit_rows * poly_words * 8));
-  RC_TRY(ws_grow(*c, &c->d_stage, &c->stage_cap, units * unit_polys * poly_words * 8));
-  if (!c->d_bskf) HIP_TRY(hipMalloc(&c->d_bskf, tfhe::sns_fft_key_len(c->sp.n) * 16));
-  phase_timer tm(c->stream);
-  c->key = false;
-  for (size_t u = 0; u < c->sp.n; u += units) {
-    const size_t nu = std::min(units, c->sp.n - u), rows = nu * unit_rows;
-    RC_TRY(tm.tick(-1));
-    HIP_TRY(hipMemcpyAsync(d_bodies.p, bodies + u * unit_rows * poly_words, rows * poly_words * 8,
-                           hipMemcpyHostToDevice, c->stream));
-    RC_TRY(tm.tick(0));
-    HIP_TRY(tfhe::launch_seeded_rows128(rk, tfhe::SEEDED128_SNS_BSK, shp, u * unit_rows, rows,
-                                        (const u64*)d_bodies.p, (u64*)c->d_stage, c->stream));
-    RC_TRY(tm.tick(1));
-    HIP_TRY(tfhe::launch_sns_bsk_to_fft((const u64*)c->d_stage,
-                                        (char*)c->d_bskf + u * unit_polys * tfhe::SNS_FFT_POLY_BYTES, nu * unit_polys,
-                                        c->d_fconst, c->stream));
-    RC_TRY(tm.tick(2));
-    // the body and staging buffers are reused by the next chunk: same stream, ordered
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  RC_TRY(tm.totals(c->seeded_ms, 3));
-  c->key = true;
-  return 0;
+  const size_t per = seeded_chunk_polys(c->sp);
+  call_buffers tmp;
+  phase_timer tm(c);
+  seeded_source src{c, round_keys_of(seed), bodies, nullptr, tm};
+  return side_key_load(
+      c,
+      [&] {
+        RC_TRY(tmp.alloc(c->device, src.body_bytes(per), &src.d_bodies));
+        return key_buffers(c, per);
+      },
+      [&] {
+        RC_TRY(key_chunks(c, per, nullptr, tm, src));
+        return tm.totals(c->seeded_ms, 3);
+      });
 }
 
 int tfhe_hip_sns_seeded_load_stats(const tfhe_sns_ctx* c, double* upload_ms, double* expand_ms, double* convert_ms) {
   if (!c) return fail(TFHE_HIP_EINVAL, "sns_seeded_load_stats: null ctx");
-  if (upload_ms) *upload_ms = c->seeded_ms[0];
-  if (expand_ms) *expand_ms = c->seeded_ms[1];
-  if (convert_ms) *convert_ms = c->seeded_ms[2];
-  return 0;
+  return seeded_ms_read(c->seeded_ms, upload_ms, expand_ms, convert_ms);
 }
 
-// test-facing: the chunks of the loader, expanded by the loader's launcher into a fresh device buffer of the key's
-// length + TFHE_HIP_SEEDED_GUARD_WORDS words filled with 0xA5 bytes, all of which is copied back
+// test-facing: the chunks of the seeded loader, launch by launch, into guarded_expand's output in place of the
+// staging buffer
 int tfhe_hip_sns_seeded_expand_bsk(tfhe_sns_ctx* c, const uint64_t seed[2], const uint64_t* bodies,
                                    uint64_t* out_host) {
   if (!c || !seed || !bodies || !out_host) return fail(TFHE_HIP_EINVAL, "sns_seeded_expand_bsk: null argument");
-  const tfhe::seeded_round_keys rk = round_keys_of(seed);
+  const size_t per = seeded_chunk_polys(c->sp);
+  phase_timer none(nullptr);
+  seeded_source src{c, round_keys_of(seed), bodies, nullptr, none};
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  const tfhe::seeded128_shape shp{c->sp.k, c->sp.N, c->sp.level};
-  const size_t poly_words = 2 * (size_t)c->sp.N, unit_rows = (size_t)c->sp.level * (c->sp.k + 1);
-  const size_t unit_polys = unit_rows * (c->sp.k + 1), units = seeded_units(c->sp);
-  const size_t out_bytes = (tfhe::client::sns_bsk_len(c->sp) + TFHE_HIP_SEEDED_GUARD_WORDS) * 8;
-  call_buffer d_bodies, d_out;
-  RC_TRY(d_bodies.alloc(units * unit_rows * poly_words * 8));
-  RC_TRY(d_out.alloc(out_bytes));
-  HIP_TRY(hipMemsetAsync(d_out.p, 0xA5, out_bytes, c->stream));
-  for (size_t u = 0; u < c->sp.n; u += units) {
-    const size_t nu = std::min(units, c->sp.n - u), rows = nu * unit_rows;
-    HIP_TRY(hipMemcpyAsync(d_bodies.p, bodies + u * unit_rows * poly_words, rows * poly_words * 8,
-                           hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(tfhe::launch_seeded_rows128(rk, tfhe::SEEDED128_SNS_BSK, shp, u * unit_rows, rows,
-                                        (const u64*)d_bodies.p, (u64*)d_out.p + u * unit_polys * poly_words,
-                                        c->stream));
-  }
-  HIP_TRY(hipMemcpyAsync(out_host, d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return guarded_expand(*c, src.body_bytes(per), tfhe::client::sns_bsk_len(c->sp), out_host,
+                        [&](u64* d_bodies, u64* d_out) {
+                          src.d_bodies = d_bodies;
+                          return key_chunks(c, per, d_out, none, src);
+                        });
 }
 
 int tfhe_hip_sns_squash(tfhe_sns_ctx* c, const uint64_t* in, size_t B, uint32_t mm, uint64_t* out) {
@@ -339,10 +341,8 @@ int tfhe_hip_sns_blind_rotate(tfhe_sns_ctx* c, const uint64_t* in, size_t B, uin
 
 int tfhe_hip_sns_squash_async(tfhe_sns_ctx* c, const uint64_t* d_in, size_t B, uint32_t mm, uint64_t* d_out,
                               void* stream) {
-  if (!c) return fail(TFHE_HIP_EINVAL, "sns: null ctx");
-  if (!c->key) return fail(TFHE_HIP_ENOKEYS, "sns: key not loaded");
+  RC_TRY(squash_checks(c, d_in, B, mm, d_out));
   if (B == 0) return 0;
-  if (!d_in || !d_out || !mm || mm > c->sp.N || (c->sp.N % mm)) return fail(TFHE_HIP_EINVAL, "sns: bad arguments");
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
   RC_TRY(ensure_lut(c, mm));

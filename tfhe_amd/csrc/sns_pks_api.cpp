@@ -1,7 +1,6 @@
 // sns_pks_api.cpp — C ABI of the compression of squashed ciphertexts (include/tfhe_hip.h, tfhe_hip_sns_pks_*):
 // key residency, workspaces, chunked launches.  Kernels: sns_pks.hip; host key material and the CPU pack: client.cpp.
 #include <hip/hip_runtime_api.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -22,12 +21,6 @@ bool spk_valid(const tfhe_sns_pks_params* pp) {
          pp->base_log >= 2 && pp->base_log <= 63 && pp->level >= 1 && (uint64_t)pp->base_log * pp->level <= 127 &&
          pp->lwe_per_glwe >= 1 && pp->lwe_per_glwe <= pp->out_N && pp->storage_log >= 2 && pp->storage_log <= 128 &&
          pp->noise_log2 < 0 && pp->noise_log2 > -64;
-}
-
-tfhe::seeded_round_keys round_keys_of(const uint64_t seed[2]) {
-  tfhe::seeded_round_keys rk;
-  tfhe::seeded::aes_round_keys(seed, rk.w);
-  return rk;
 }
 
 constexpr size_t SPK_T_BUDGET = 512ull << 20;    // T workspace per chunk of groups
@@ -92,6 +85,25 @@ int pack_checks(tfhe_sns_pks_ctx* c, const void* in, size_t count, const void* o
   return 0;
 }
 
+// what both loaders allocate on first use: the resident key and its correction row
+int key_buffers(tfhe_sns_pks_ctx* c) {
+  if (!c->d_pksk) HIP_TRY(hipMalloc(&c->d_pksk, tfhe::client::sns_pksk_len(c->pp) * 8));
+  if (!c->d_corr) HIP_TRY(hipMalloc(&c->d_corr, (size_t)(c->pp.out_k + 1) * c->pp.out_N * 16));
+  return 0;
+}
+
+// the correction row of the key words in d_pksk, the last step of both loaders
+hipError_t launch_corr(tfhe_sns_pks_ctx* c) {
+  return tfhe::launch_sns_pks_corr(c->d_pksk, (int)(c->pp.in_dim * c->pp.level), (int)((c->pp.out_k + 1) * c->pp.out_N),
+                                   (int)c->pp.out_N, (int)c->pp.base_log, c->d_corr, c->stream);
+}
+
+// the seeded loader's expansion of the whole key in one launch, into the resident key or the expand aid's output
+hipError_t launch_rows(tfhe_sns_pks_ctx* c, const tfhe::seeded_round_keys& rk, const u64* d_bodies, u64* dst) {
+  return tfhe::launch_seeded_rows128(rk, tfhe::SEEDED128_SNS_PKSK, {c->pp.out_k, c->pp.out_N, c->pp.level}, 0,
+                                     (u64)c->pp.in_dim * c->pp.level, d_bodies, dst, c->stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -125,11 +137,7 @@ int tfhe_hip_sns_pks_create(const tfhe_sns_pks_params* pp, int device, tfhe_sns_
   if (!spk_valid(pp)) return fail(TFHE_HIP_EINVAL, "sns_pks_create: invalid parameters");
   tfhe_sns_pks_ctx* c = new tfhe_sns_pks_ctx();
   c->pp = *pp;
-  {
-    const char* e = getenv("TFHE_HIP_SNS_PKS_CHUNK");
-    const long x = e ? atol(e) : 0;
-    c->chunk_groups = x > 0 ? (size_t)x : 0;
-  }
+  c->chunk_groups = env_positive("TFHE_HIP_SNS_PKS_CHUNK", 0);
   const int rc = slot_open(*c, device, "sns_pks_create", "device setup failed");
   if (rc) {
     tfhe_hip_sns_pks_destroy(c);
@@ -149,19 +157,11 @@ int tfhe_hip_sns_pks_load_key(tfhe_sns_pks_ctx* c, const uint64_t* pksk, size_t 
   if (!c || !pksk) return fail(TFHE_HIP_EINVAL, "sns_pks_load_key: null argument");
   if (len != tfhe::client::sns_pksk_len(c->pp))
     return fail(TFHE_HIP_EINVAL, "sns_pks_load_key: length %zu, expected %zu", len, tfhe::client::sns_pksk_len(c->pp));
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  RC_TRY(ws_host_wait(*c));  // a call in flight on a caller's stream still reads the resident key
-  c->key = false;
-  const size_t Nc = (size_t)(c->pp.out_k + 1) * c->pp.out_N;
-  if (!c->d_pksk) HIP_TRY(hipMalloc(&c->d_pksk, len * 8));
-  if (!c->d_corr) HIP_TRY(hipMalloc(&c->d_corr, Nc * 16));
-  HIP_TRY(hipMemcpyAsync(c->d_pksk, pksk, len * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(tfhe::launch_sns_pks_corr(c->d_pksk, (int)(c->pp.in_dim * c->pp.level), (int)Nc, (int)c->pp.out_N,
-                                    (int)c->pp.base_log, c->d_corr, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  c->key = true;
-  return 0;
+  return side_key_load(c, [&] { return key_buffers(c); }, [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(c->d_pksk, pksk, len * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(launch_corr(c));
+    return 0;
+  });
 }
 
 size_t tfhe_hip_sns_pks_seeded_bodies_len(const tfhe_sns_pks_params* pp) {
@@ -191,70 +191,55 @@ int tfhe_hip_sns_pks_decompress_key(const tfhe_sns_pks_params* pp, const uint64_
   return 0;
 }
 
-// Every refusal and every allocation comes before the resident key is touched: a refused load, or one that cannot
-// allocate, leaves the previous key usable.  The bodies go up into a buffer of this call, the rows are expanded
-// straight into the resident key, and the correction kernel follows as in tfhe_hip_sns_pks_load_key
+// tfhe_hip_sns_pks_load_key from the seeded source: the bodies go up into a buffer of this call and the rows are
+// expanded straight into the resident key
 int tfhe_hip_sns_pks_load_key_seeded(tfhe_sns_pks_ctx* c, const uint64_t seed[2], const uint64_t* bodies, size_t len) {
   if (!c || !seed || !bodies) return fail(TFHE_HIP_EINVAL, "sns_pks_load_key_seeded: null argument");
   if (len != tfhe::seeded::sns_pks_bodies_len(c->pp))
     return fail(TFHE_HIP_EINVAL, "sns_pks_load_key_seeded: length %zu, expected %zu", len,
                 tfhe::seeded::sns_pks_bodies_len(c->pp));
   const tfhe::seeded_round_keys rk = round_keys_of(seed);
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  RC_TRY(ws_host_wait(*c));  // a call in flight on a caller's stream still reads the resident key
-  const size_t Nc = (size_t)(c->pp.out_k + 1) * c->pp.out_N;
-  call_buffer d_bodies;
-  RC_TRY(d_bodies.alloc(len * 8));
-  if (!c->d_pksk) HIP_TRY(hipMalloc(&c->d_pksk, tfhe::client::sns_pksk_len(c->pp) * 8));
-  if (!c->d_corr) HIP_TRY(hipMalloc(&c->d_corr, Nc * 16));
-  phase_timer tm(c->stream);
-  RC_TRY(tm.tick(-1));
-  HIP_TRY(hipMemcpyAsync(d_bodies.p, bodies, len * 8, hipMemcpyHostToDevice, c->stream));
-  RC_TRY(tm.tick(0));
-  c->key = false;
-  HIP_TRY(tfhe::launch_seeded_rows128(rk, tfhe::SEEDED128_SNS_PKSK, {c->pp.out_k, c->pp.out_N, c->pp.level}, 0,
-                                      (u64)c->pp.in_dim * c->pp.level, (const u64*)d_bodies.p, c->d_pksk, c->stream));
-  RC_TRY(tm.tick(1));
-  HIP_TRY(tfhe::launch_sns_pks_corr(c->d_pksk, (int)(c->pp.in_dim * c->pp.level), (int)Nc, (int)c->pp.out_N,
-                                    (int)c->pp.base_log, c->d_corr, c->stream));
-  RC_TRY(tm.tick(2));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  RC_TRY(tm.totals(c->seeded_ms, 3));
-  c->key = true;
-  return 0;
+  call_buffers tmp;
+  u64* d_bodies = nullptr;
+  phase_timer tm(c);
+  return side_key_load(
+      c,
+      [&] {
+        RC_TRY(tmp.alloc(c->device, len * 8, &d_bodies));
+        return key_buffers(c);
+      },
+      [&] {
+        RC_TRY(tm.tick(-1));
+        HIP_TRY(hipMemcpyAsync(d_bodies, bodies, len * 8, hipMemcpyHostToDevice, c->stream));
+        RC_TRY(tm.tick(0));
+        HIP_TRY(launch_rows(c, rk, d_bodies, c->d_pksk));
+        RC_TRY(tm.tick(1));
+        HIP_TRY(launch_corr(c));
+        RC_TRY(tm.tick(2));
+        return tm.totals(c->seeded_ms, 3);
+      });
 }
 
 int tfhe_hip_sns_pks_seeded_load_stats(const tfhe_sns_pks_ctx* c, double* upload_ms, double* expand_ms,
                                        double* corr_ms) {
   if (!c) return fail(TFHE_HIP_EINVAL, "sns_pks_seeded_load_stats: null ctx");
-  if (upload_ms) *upload_ms = c->seeded_ms[0];
-  if (expand_ms) *expand_ms = c->seeded_ms[1];
-  if (corr_ms) *corr_ms = c->seeded_ms[2];
-  return 0;
+  return seeded_ms_read(c->seeded_ms, upload_ms, expand_ms, corr_ms);
 }
 
-// test-facing: the loader's launcher into a fresh device buffer of the key's length + TFHE_HIP_SEEDED_GUARD_WORDS
-// words filled with 0xA5 bytes, all of which is copied back
+// test-facing: the seeded loader's upload and launch into guarded_expand's output in place of the resident key
 int tfhe_hip_sns_pks_seeded_expand_key(tfhe_sns_pks_ctx* c, const uint64_t seed[2], const uint64_t* bodies,
                                        uint64_t* out_host) {
   if (!c || !seed || !bodies || !out_host) return fail(TFHE_HIP_EINVAL, "sns_pks_seeded_expand_key: null argument");
   const tfhe::seeded_round_keys rk = round_keys_of(seed);
+  const size_t body_bytes = tfhe::seeded::sns_pks_bodies_len(c->pp) * 8;
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  const size_t len = tfhe::seeded::sns_pks_bodies_len(c->pp);
-  const size_t out_bytes = (tfhe::client::sns_pksk_len(c->pp) + TFHE_HIP_SEEDED_GUARD_WORDS) * 8;
-  call_buffer d_bodies, d_out;
-  RC_TRY(d_bodies.alloc(len * 8));
-  RC_TRY(d_out.alloc(out_bytes));
-  HIP_TRY(hipMemsetAsync(d_out.p, 0xA5, out_bytes, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_bodies.p, bodies, len * 8, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(tfhe::launch_seeded_rows128(rk, tfhe::SEEDED128_SNS_PKSK, {c->pp.out_k, c->pp.out_N, c->pp.level}, 0,
-                                      (u64)c->pp.in_dim * c->pp.level, (const u64*)d_bodies.p, (u64*)d_out.p,
-                                      c->stream));
-  HIP_TRY(hipMemcpyAsync(out_host, d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return guarded_expand(*c, body_bytes, tfhe::client::sns_pksk_len(c->pp), out_host,
+                        [&](u64* d_bodies, u64* d_out) -> int {
+                          HIP_TRY(hipMemcpyAsync(d_bodies, bodies, body_bytes, hipMemcpyHostToDevice, c->stream));
+                          HIP_TRY(launch_rows(c, rk, d_bodies, d_out));
+                          return 0;
+                        });
 }
 
 int tfhe_hip_sns_pks_pack_async(tfhe_sns_pks_ctx* c, const uint64_t* d_lwes, size_t count, uint64_t* d_glwes,
